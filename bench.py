@@ -11,13 +11,20 @@ exchange step).  `value` = edges (nonzeros) pushed through the S
 second, whole job, inputs resident in HBM.  Weak scaling: every rank owns one Reddit-shape
 vertex-range shard.
 
-One JSON line on stdout (rank 0).  Extra objects:
+One JSON line on stdout (rank 0).  A plain run sets up, warms up (--warmup), times --steps steps
+(`ms_per_step` = one timed step) and prints the line.  Extra objects:
   roofline      dominant kernel (forward SpMM): algorithmic bytes per launch
                 nnz*8 + (M+1)*4 + 2*N*d*4 / mean launch time from HIP events
                 recorded on the launch stream inside the timed region, vs the 8 TB/s HBM peak.
+and, with --full only (each of these takes runs of its own after the timed steps):
+  setup         what the column sweep's plan costs, next to the row-gather kernel.
+  roofline.traffic_live  HBM bytes counted by three rocprofv3 --pmc child runs (--pmc auto).
   cpu_baseline  the oracle's OpenMP C restatement of the same product (oracle/oracle_c.c) on a
                 bounded row sample of the same matrix, all host cores.
   train_epoch   (when available) the CVD+PP minibatch epoch on the same graph.
+  strong        (--gpus N > 1) one graph row-block sharded over the ranks.
+--dump-outputs DIR writes the last timed step's C = A.X and dX = A^T.dC (a fixed, seeded row
+sample; all-reduced gradient buffer too when a process group is up) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -35,6 +42,8 @@ if ROOT not in sys.path:
 HBM_PEAK = 8.0e12          # B/s, MI355X spec (/opt/skills/guides/MI355X_MICROARCH.md:35)
 L2_PEAK = 34.5e12          # aggregate L2 bandwidth, MI355X_MICROARCH.md "L2 (per XCD)"
 HBM_COPY = 6.29e12         # measured float4-copy ceiling (ibid.)
+DUMP_BUDGET = 48 << 20     # bytes of all --dump-outputs files together
+DUMP_SEED = 0              # row sample of the dumped outputs
 
 
 def _finish_args(args):
@@ -62,8 +71,8 @@ def parse(argv=None):
     p.add_argument("--pmc", default="auto", choices=["auto", "live", "off"],
                    help="roofline.traffic: live = three separate rocprofv3 --pmc passes of this same command, run as child "
                         "processes (FETCH_SIZE / WRITE_SIZE / TCC_HIT+MISS: MI355X_MICROARCH.md's recipe), counted in THIS run; "
-                        "auto = live for the default single-GPU column-sweep line, the committed profiles/*_traffic.json record "
-                        "otherwise or when a pass fails; off = the committed record")
+                        "auto = live for the default single-GPU column-sweep line with --full, the committed profiles/*_traffic.json "
+                        "record otherwise or when a pass fails; off = the committed record")
     p.add_argument("--no-epoch", action="store_true")
     p.add_argument("--no-strong", action="store_true", help="--gpus N > 1: skip the strong-scaling leg (ONE graph row-block sharded)")
     p.add_argument("--epoch-timeout", type=int, default=240, help="watchdog of the train-epoch leg, s")
@@ -101,6 +110,13 @@ def parse(argv=None):
                    help="[test hook] no GPU work: only the launch / rendezvous / collective skeleton of "
                         "the run (what the CPU test of `--gpus N` exercises under SGCN_DIST_BACKEND=gloo); "
                         "the JSON line carries \"dry_run\": true and no throughput")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the timed steps: the plan-setup report, the LDS kernel parts, live PMC traffic "
+                        "(--pmc auto), the CPU and sampler baselines, the train-epoch leg and (--gpus N > 1) the strong-scaling "
+                        "leg; without it a run sets up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a fixed, "
+                        "seeded row sample of C = A.X and dX = A^T.dC, at most %d MiB in all)" % (DUMP_BUDGET >> 20))
     return _finish_args(p.parse_args(argv))
 
 
@@ -128,6 +144,16 @@ def launch(args, argv):
                              "device per rank (SGCN_DIST_BACKEND=gloo shares a device for smoke tests)\n"
                              % (args.gpus, have))
             return 2, None
+    if args.dump_outputs:               # (the ranks run from ROOT: a relative --dump-outputs is the caller's)
+        keep, skip = [], False
+        for a in argv:
+            if skip:
+                skip = False
+            elif a == "--dump-outputs":
+                skip = True
+            elif not a.startswith("--dump-outputs="):
+                keep.append(a)
+        argv = keep + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.abspath(__file__)] + list(argv)
@@ -304,12 +330,12 @@ def live_traffic(argv, pace_fwd, pace_bwd, kernel_prefix, launches, timeout_s=60
         return None
     base = tempfile.mkdtemp(prefix="sgcn_pmc_", dir=os.environ.get("TMPDIR") or "/tmp")
     keep, skip = [], False
-    for a in argv:                       # (the parent's own --pmc choice does not travel)
+    for a in argv:                       # (the parent's own --pmc choice, --full and --dump-outputs do not travel)
         if skip:
             skip = False
-        elif a == "--pmc":
+        elif a in ("--pmc", "--dump-outputs"):
             skip = True
-        elif not a.startswith("--pmc="):
+        elif a != "--full" and not a.startswith(("--pmc=", "--dump-outputs=")):
             keep.append(a)
     child = [sys.executable, os.path.abspath(__file__)] + keep + \
         ["--pmc", "off", "--no-epoch", "--no-cpu-baseline", "--no-setup-report", "--steps", "4", "--warmup", "1",
@@ -392,6 +418,28 @@ def setup_report(setup, full_adj, X, C, dev, cs_ms, ops):
     rep["products_to_break_even_vs_rows_kernel"] = (int(np.ceil(max(cs_setup - rows_setup, 0.0) / gain)) if gain > 0 else None)
     rep["first_product_s"] = {"column_sweep": round(cs_setup + cs_ms * 1e-3, 4), "rows_kernel": round(rows_setup + rows_ms * 1e-3, 4)}
     return rep
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, seed=DUMP_SEED):
+    """--dump-outputs: ``arrays`` (name -> torch tensor or ndarray) written as ``path/<name>.npy`` in float32, so that two
+    builds can be compared output for output.  1-D arrays are written whole; the 2-D ones share what is left of ``budget``
+    bytes: all their rows when they fit, otherwise the rows ``np.random.RandomState(seed).choice(rows, k)`` (sorted, the
+    same for every array of that row count, so the files stay row-aligned).  Returns {name: shape written}."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    left = budget - sum(int(a.numel() if torch.is_tensor(a) else a.size) * 4 for a in arrays.values() if a.ndim == 1)
+    row_bytes = sum(int(a.shape[1]) * 4 for a in arrays.values() if a.ndim == 2)
+    assert left >= 0 and (row_bytes == 0 or left >= row_bytes), "--dump-outputs: the outputs do not fit %d bytes" % budget
+    k = left // row_bytes if row_bytes else 0
+    written = {}
+    for name, a in arrays.items():
+        if a.ndim == 2 and a.shape[0] > k:
+            rows = np.sort(np.random.RandomState(seed).choice(a.shape[0], k, replace=False))
+            a = a.index_select(0, torch.from_numpy(rows).to(a.device)) if torch.is_tensor(a) else a[rows]
+        a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = list(a.shape)
+    return written
 
 
 def reddit_grad_floats(d_in=602, hidden=128, classes=41):
@@ -824,6 +872,14 @@ def main(argv=None):
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's products (rank 0's rows), before any later leg writes into C
+        outs = {"C": C}
+        if not args.no_backward:
+            outs["dX"] = dX
+        if pg and not args.shard:
+            outs["grad"] = grad
+        sys.stderr.write("bench.py: outputs %s -> %s\n" % (dump_outputs(args.dump_outputs, outs), args.dump_outputs))
     fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     ar_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_ar])) if ev_ar else None
     edges_per_step = nnz * (1 if args.no_backward else 2)
@@ -836,7 +892,7 @@ def main(argv=None):
         bytes_alg = nnz_l * 8 + (m_l + 1) * 4 + sh.distinct_cols * d * 4 + m_l * d * 4
     achieved = bytes_alg / (fwd_ms * 1e-3)
     lds_parts = None
-    if args.kernel == "lds" and sh is None:     # the forward product's two kernels on their own (untimed region)
+    if args.full and args.kernel == "lds" and sh is None:     # the forward product's two kernels on their own (untimed region)
         def _t(fn, reps=5):
             fn()
             a_, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -900,7 +956,7 @@ def main(argv=None):
     }
     if reorder_info:
         out["config"]["reorder"] = reorder_info
-    if setup is not None and not args.no_setup_report:
+    if args.full and setup is not None and not args.no_setup_report:
         out["setup"] = setup_report(setup, full_adj, X, C, dev, fwd_ms, ops)
     gc = gather_ceiling()
     if gc is not None and args.kernel == "cs":
@@ -924,9 +980,9 @@ def main(argv=None):
                               if args.kernel == "cs" else "void sgcn::spmm", sh.local_nnz if sh is not None else nnz, d) \
             if not (args.tune or reorder != "none") else None
     # ... or, better, counted in THIS run (a committed file is the builder's number): the default single-GPU
-    # column-sweep line spends ~30 s on three child passes under rocprofv3 --pmc
+    # column-sweep line of --full spends ~30 s on three child passes under rocprofv3 --pmc
     live = None
-    want_live = args.pmc == "live" or (args.pmc == "auto" and sh is None and not args.tune and reorder == "none")
+    want_live = args.pmc == "live" or (args.pmc == "auto" and args.full and sh is None and not args.tune and reorder == "none")
     if want_live and args.kernel == "cs" and rank == 0 and world == 1 and not os.environ.get("SGCN_BENCH_CHILD") and tuned:
         pf = tuned["fwd"][1] if "fwd" in tuned else tuned.get("fwd_pace")
         pb_ = (tuned["bwd"][1] if "bwd" in tuned else tuned.get("bwd_pace")) if not args.no_backward else pf
@@ -959,7 +1015,7 @@ def main(argv=None):
         if rank == 0:
             print(json.dumps(out), flush=True)
 
-    if world > 1 and sh is None and not args.no_strong:
+    if args.full and world > 1 and sh is None and not args.no_strong:
         # the weak line above is ~N x by construction (every rank its own graph + a 0.84 MB all-reduce); the
         # informative numbers of a multi-GPU run are these.  A watchdog bounds a wedged collective (RCCL has not run on
         # hardware yet): the weak line is still printed.
@@ -981,12 +1037,12 @@ def main(argv=None):
         except Exception as e:
             out["strong"] = {"error": repr(e)}
         sdog.cancel()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(full_adj, d, args.cpu_sample_rows)
         if data10 is not None:
             out["cpu_baseline"]["sampler"] = sampler_baseline(data10)
 
-    if not args.no_epoch and data10 is not None and sh is None:
+    if args.full and not args.no_epoch and data10 is not None and sh is None:
         # the minibatch training epoch, on every rank (vertex-range shards, RCCL gradient
         # all-reduce + history exchange when N > 1).  A watchdog bounds a wedged collective: the
         # SpMM line above is still printed.

@@ -27,6 +27,8 @@ import scipy.sparse as sp
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 from oracle import ref_binding as rb  # noqa: E402
+sys.path.insert(0, os.path.join(HERE, ".."))
+import golden_util as gu  # noqa: E402
 
 
 def placeholders(L):
@@ -129,8 +131,8 @@ def make_sampler(path, graphs, big):
             key = "%s/s%d_cv%d_is%d_L%d_d%d/adj_i_after" % (gname, seed, cv, imp, L, deg)
             perm = sch.c_sch.ivec(rb.I_ADJ_I)
             out[key + ("#sha" if big else "")] = digest(perm) if big else perm
-    np.savez_compressed(path, **out)
-    print(path, len(out), "arrays", os.path.getsize(path), "bytes")
+    for p in gu.save_npz(path, out):         # (split into parts under 1 MiB when larger)
+        print(p, len(out), "arrays", os.path.getsize(p), "bytes")
 
 
 def make_mult(path):
@@ -148,8 +150,8 @@ def make_mult(path):
         out[name + "/u"] = us
         out[name + "/query_u"] = np.array([m.query_u(u) for u in us], dtype=np.int32)
         out[name + "/draws"] = np.array([m.query() for _ in range(len(p))], dtype=np.int32)
-    np.savez_compressed(path, **out)
-    print(path, len(out), "arrays", os.path.getsize(path), "bytes")
+    for p in gu.save_npz(path, out):         # (split into parts under 1 MiB when larger)
+        print(p, len(out), "arrays", os.path.getsize(p), "bytes")
 
 
 def make_slice(path):
@@ -181,8 +183,8 @@ def make_slice(path):
     out["dense/a"] = d
     for name, r in cases.items():
         out["dense/%s/out" % name] = rb.ref_dense_slice(d, r)
-    np.savez_compressed(path, **out)
-    print(path, len(out), "arrays", os.path.getsize(path), "bytes")
+    for p in gu.save_npz(path, out):         # (split into parts under 1 MiB when larger)
+        print(p, len(out), "arrays", os.path.getsize(p), "bytes")
 
 
 if __name__ == "__main__":

@@ -350,5 +350,6 @@ if __name__ == "__main__":
     det = "--det" in sys.argv[1:]
     blob = generate(det)
     out = os.path.join(HERE, "model_steps_det.npz" if det else "model_steps.npz")
-    np.savez_compressed(out, **blob)
-    print("wrote %s: %d arrays, %.2f MB" % (out, len(blob), os.path.getsize(out) / 1e6))
+    import golden_util as gu
+    for p in gu.save_npz(out, blob):                # (split into parts under 1 MiB when larger)
+        print("wrote %s: %d arrays, %.2f MB" % (p, len(blob), os.path.getsize(p) / 1e6))

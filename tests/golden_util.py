@@ -1,15 +1,109 @@
 """Helpers shared by the golden-vector tests."""
+import glob
 import hashlib
+import io
 import os
+import re
 
 import numpy as np
 import scipy.sparse as sp
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+PART_BYTES = 900 * 1024      # a fixture larger than this is stored as <name>.part<k>.npz files (committed files stay < 1 MiB)
+
+
+class NpzParts(object):
+    """The members of <name>.part0.npz, <name>.part1.npz, ... read as ONE ``np.load`` result (``files``, ``[key]``)."""
+
+    def __init__(self, paths):
+        self._parts = [np.load(p) for p in paths]
+        self._where = {}
+        for z in self._parts:
+            for k in z.files:
+                assert k not in self._where, k
+                self._where[k] = z
+        self.files = list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __iter__(self):
+        return iter(self.files)
+
+    def __len__(self):
+        return len(self.files)
+
+    def keys(self):
+        return list(self.files)
+
+    def close(self):
+        for z in self._parts:
+            z.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def part_paths(path):
+    """<stem>.part<k>.npz beside ``path`` (= <stem>.npz), in k order."""
+    stem = path[:-len(".npz")]
+    got = glob.glob(glob.escape(stem) + ".part*.npz")
+    got = [p for p in got if re.fullmatch(r"\.part\d+\.npz", p[len(stem):])]
+    return sorted(got, key=lambda p: int(p[len(stem) + 5:-4]))
+
+
+def load_npz(path):
+    """``np.load(path)``, or the union of its parts when the fixture is stored split (see ``save_npz``)."""
+    if os.path.exists(path):
+        return np.load(path)
+    parts = part_paths(path)
+    if not parts:
+        raise FileNotFoundError(path)
+    return NpzParts(parts)
 
 
 def load(name):
-    return np.load(os.path.join(GOLDEN, name))
+    return load_npz(os.path.join(GOLDEN, name))
+
+
+def save_npz(path, arrays, limit=PART_BYTES):
+    """``np.savez_compressed(path, **arrays)``; when that file would exceed ``limit`` bytes, the arrays (in order) go to
+    <stem>.part0.npz, .part1.npz, ... instead, each at most ``limit`` bytes.  Stale copies of either form are removed.
+    Returns the paths written."""
+    def packed(d):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **d)
+        return buf.getvalue()
+    for p in part_paths(path) + ([path] if os.path.exists(path) else []):
+        os.remove(p)
+    whole = packed(arrays)
+    if len(whole) <= limit:
+        chunks = [(path, whole)]
+    else:
+        # a zip archive is its members plus one 22-byte end record: members are costed one by one
+        empty = len(packed({}))
+        chunks, cur, size = [], {}, empty
+        for k, v in arrays.items():
+            cost = len(packed({k: v})) - empty
+            if cur and size + cost > limit:
+                chunks.append(packed(cur))
+                cur, size = {}, empty
+            cur[k] = v
+            size += cost
+        chunks.append(packed(cur))
+        stem = path[:-len(".npz")]
+        chunks = [("%s.part%d.npz" % (stem, i), b) for i, b in enumerate(chunks)]
+    for p, b in chunks:
+        assert len(b) <= limit, (p, len(b))
+        with open(p, "wb") as f:
+            f.write(b)
+    return [p for p, _ in chunks]
 
 
 def placeholders(L):

@@ -129,3 +129,80 @@ def test_live_pmc_passes_are_three_separate_counter_runs_of_the_same_command(mon
         raise subprocess.TimeoutExpired(a[0], k.get("timeout"))
     monkeypatch.setattr(subprocess, "run", hang)
     assert bench.live_traffic(["--gpus", "1"], 195, 192, "void sgcn::cs_spmm16", 10) is None
+
+
+def test_live_pmc_children_drop_full_and_dump_outputs(monkeypatch):
+    """The rocprofv3 child runs are plain runs: --full and --dump-outputs of the parent do not travel to them (a child
+    would otherwise run every --full leg under the profiler, and write its 4-step outputs over the parent's)."""
+    import bench
+    calls = []
+    monkeypatch.setattr(os.path, "exists", lambda p: True)
+
+    def fail(cmd, **kw):
+        calls.append(list(cmd))
+        return subprocess.CompletedProcess(cmd, 1)
+    monkeypatch.setattr(subprocess, "run", fail)
+    argv = ["--gpus", "1", "--full", "--dump-outputs", "/x/out", "--steps", "20", "--dump-outputs=/y", "--pmc=live"]
+    assert bench.live_traffic(argv, 195, 192, "void sgcn::cs_spmm16", 10) is None
+    child = calls[0][calls[0].index("--") + 1:]
+    assert "--full" not in child and not [a for a in child if "dump-outputs" in a or a in ("/x/out", "/y")]
+    assert child[2:6] == ["--gpus", "1", "--steps", "20"] and child.count("--pmc") == 1
+
+
+def test_parse_full_and_dump_outputs_default_off():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_a_fixed_row_sample_within_budget(tmp_path):
+    """bench.dump_outputs: float32 .npy files; 2-D outputs that do not fit are sampled by one fixed seeded row set
+    (row-aligned across the files, identical from run to run), 1-D ones written whole, all inside the byte budget."""
+    import bench
+    import numpy as np
+    import torch
+    rng = np.random.RandomState(5)
+    C = torch.from_numpy(rng.standard_normal((1000, 48)).astype(np.float32))
+    Cp = torch.zeros((1000, 64))
+    Cp[:, :48] = C
+    dX = Cp[:, :48]                                          # a pitched view, as bench's outputs are
+    g = torch.arange(300, dtype=torch.float32)
+    budget = 300 * 4 + 2 * 48 * 4 * 100 + 17                 # the grad buffer + 100 rows of each 2-D output
+    got = bench.dump_outputs(str(tmp_path / "a"), {"C": C, "dX": dX, "grad": g}, budget=budget)
+    assert got == {"C": [100, 48], "dX": [100, 48], "grad": [300]}
+    files = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in got}
+    assert all(f.dtype == np.float32 for f in files.values())
+    assert sum(f.nbytes for f in files.values()) <= budget
+    rows = np.sort(np.random.RandomState(bench.DUMP_SEED).choice(1000, 100, replace=False))
+    assert np.array_equal(files["C"], C.numpy()[rows]) and np.array_equal(files["dX"], files["C"])
+    assert np.array_equal(files["grad"], g.numpy())
+    bench.dump_outputs(str(tmp_path / "b"), {"C": C, "dX": dX, "grad": g}, budget=budget)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "C.npy")), files["C"])      # the same sample every run
+    # small outputs go out whole
+    got = bench.dump_outputs(str(tmp_path / "c"), {"C": C}, budget=bench.DUMP_BUDGET)
+    assert got == {"C": [1000, 48]} and np.array_equal(np.load(str(tmp_path / "c" / "C.npy")), C.numpy())
+    assert bench.DUMP_BUDGET <= 64 << 20
+
+
+def test_gpus_2_passes_dump_outputs_as_an_absolute_path(monkeypatch, tmp_path):
+    """The ranks of `--gpus N` run from the repository root: a relative --dump-outputs must still name the caller's
+    directory."""
+    import bench
+    seen = []
+
+    class P(object):
+        stdout = iter(())
+
+        def __init__(self, cmd, **kw):
+            seen.append(cmd)
+
+        def wait(self):
+            return 0
+    monkeypatch.setattr(subprocess, "Popen", P)
+    monkeypatch.chdir(tmp_path)
+    argv = ["--gpus", "2", "--dump-outputs", "out", "--steps", "3", "--dry-run"]
+    assert bench.launch(bench.parse(argv), argv) == (0, None)
+    tail = seen[0][seen[0].index(os.path.join(ROOT, "bench.py")) + 1:]
+    assert tail == ["--gpus", "2", "--steps", "3", "--dry-run", "--dump-outputs", os.path.join(os.getcwd(), "out")]

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import golden_util as gu
 import model_cases as mc
 from oracle import model_np as mnp
 from oracle import oracle_np as onp
@@ -21,7 +22,7 @@ PARAM_TOL = 5e-4        # Adam-updated weights on well-conditioned entries: lr *
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(GOLD)
+    return gu.load_npz(GOLD)
 
 
 def well_conditioned(g, prev=True):

@@ -144,8 +144,8 @@ GOLD = None
 def _gold():
     global GOLD
     if GOLD is None:
-        import os
-        GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "model_steps.npz"))
+        import golden_util as gu
+        GOLD = gu.load("model_steps.npz")
     return GOLD
 
 
