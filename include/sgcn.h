@@ -526,6 +526,19 @@ int sgcn_l2_penalty_f32(const float* dev_theta, int64_t lo, int64_t hi, float wd
 int sgcn_adam_f32(float* dev_theta, const float* dev_grad, float* dev_m, float* dev_v, int64_t n,
                   float lr_t, float beta1, float beta2, float eps, void* stream);
 
+/* ---- running statistics of the --gradvar bias / variance study (gcn/train.py:241-276) ------------------------------ */
+/* One Welford update of a running fp64 mean / sum of squared deviations by the fp32 sample x[0..n): `count` samples are
+ * already in (the caller counts; count == 0 initialises mean = x, m2 = 0 without reading them):
+ *   d = x - mean;  mean += d / (count + 1);  m2 += d (x - mean).
+ * x may sit at any float offset (vector loads where x, mean and m2 line up, element-wise otherwise).
+ * Replaces Stat.add + the np.mean / np.std of the kept draws            gcn/stats.py, gcn/train.py:241-276 */
+int sgcn_moments_add_f32(const float* dev_x, int64_t n, int64_t count, double* dev_mean, double* dev_m2, void* stream);
+/* out3[0] = mean |mean_a|,  out3[1] = mean sqrt(m2_a / count_a) (np.std, ddof 0: Stat.std),
+ * out3[2] = mean |mean_a - mean_b| (0 when mean_b is NULL).  One workgroup, fixed summation order (bitwise reproducible).
+ * The np.mean(...) scalars the study prints                             gcn/stats.py, gcn/train.py:256-276 */
+int sgcn_moments_summary_f64(const double* dev_mean_a, const double* dev_m2_a, int64_t count_a, const double* dev_mean_b,
+                             int64_t n, double* dev_out3, void* stream);
+
 /* ---- deterministic dropout (--det_dropout; gcn/layers.py:141-202, 236-248, 320-349, 425-428): the element-wise and
  * row-wise pieces of the moment-propagation variant, forward and backward (autodiff of the reference's formulas).  The
  * variant's matrix products are sgcn_gemm_f32 / sgcn_spmm_csr_f32.  All arrays dense with pitch d unless a pitch is given. */

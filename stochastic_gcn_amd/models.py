@@ -938,6 +938,14 @@ class GCN(Model):
     def get_pred_and_grad(self, sess, feed_dict):
         """Prediction and the gradient of the loss wrt the first variable (gcn/models.py:196),
         without touching weights or history."""
+        pred, _ = self.get_pred_and_grad_device(sess, feed_dict)
+        first = self.named_vars()[0][0]
+        return pred.cpu().numpy(), [self.get_grads()[first]]
+
+    def get_pred_and_grad_device(self, sess, feed_dict):
+        """``get_pred_and_grad`` with the results left on the device, for the --gradvar study (gcn/train.py:241-276):
+        (pred, gradient of the first variable) as device tensors, with no host copy or synchronisation.  The gradient
+        is a view of this model's flat gradient buffer, which the next backward pass overwrites (stream order)."""
         self.join_history()
         self.dropout = float(feed_dict.get(self.placeholders['dropout'], 0.0))
         cur = self.get_data(feed_dict)
@@ -948,6 +956,7 @@ class GCN(Model):
         finally:
             self._want_grad = False
         self.backward(dlogits)
-        first = self.named_vars()[0][0]
         self.dropout_step += 1
-        return pred.cpu().numpy(), [self.get_grads()[first]]
+        lname, pname = self._layout[0][0].rsplit('/', 1)
+        first = next(l for l in self.layers if l.name == lname)
+        return pred, first.grads[pname]

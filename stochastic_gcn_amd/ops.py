@@ -12,6 +12,8 @@ Reference seams replaced:
   dense_fwd / dense_bwd / gemm / dropout   the dense layers around the aggregators (dot + MyLayerNorm
                   + relu + tf.nn.dropout and their autodiff) gcn/layers.py:87-138,365-433
   spmm_cs         the same product as spmm for a STATIC graph (column sweep, ColumnSweepCSR)
+  moments_add / moments_summary   Stat.add + np.mean / np.std of the kept draws   gcn/stats.py,
+                  gcn/train.py:241-276 (running fp64 statistics on the device, stats.DeviceStat)
 """
 import ctypes as C
 import time
@@ -408,6 +410,34 @@ def adam_step(theta, grad, m, v, lr_t, beta1, beta2, eps=1e-8):
     check(lib.sgcn_adam_f32(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(),
                             int(theta.numel()), float(lr_t), float(beta1), float(beta2), float(eps),
                             _stream()))
+
+
+# ---- running statistics of the --gradvar study (sgcn_stats.hip; gcn/stats.py, gcn/train.py:241-276) ----
+def moments_add(x, count, mean, m2):
+    """Fold the fp32 sample x into the running fp64 (mean, m2) that already hold ``count`` samples (Welford;
+    count == 0 initialises them)   (sgcn_moments_add_f32)."""
+    xp, n = _flat(x, "x")
+    for t, name in ((mean, "mean"), (m2, "m2")):
+        _dev(t, torch.float64, name)
+        if not t.is_contiguous() or int(t.numel()) != n:
+            raise ValueError("%s must be a contiguous fp64 array of %d elements" % (name, n))
+    check(lib.sgcn_moments_add_f32(xp, n, int(count), mean.data_ptr(), m2.data_ptr(), _stream()))
+
+
+def moments_summary(mean_a, m2_a, count_a, mean_b=None, out=None):
+    """Device fp64[3] = {mean |mean_a|, mean sqrt(m2_a / count_a), mean |mean_a - mean_b| (0 without mean_b)}
+    (sgcn_moments_summary_f64)."""
+    n = int(mean_a.numel())
+    for t, name in ((mean_a, "mean_a"), (m2_a, "m2_a"), (mean_b, "mean_b")):
+        if t is not None:
+            _dev(t, torch.float64, name)
+            if not t.is_contiguous() or int(t.numel()) != n:
+                raise ValueError("%s must be a contiguous fp64 array of %d elements" % (name, n))
+    if out is None:
+        out = torch.empty(3, dtype=torch.float64, device=mean_a.device)
+    check(lib.sgcn_moments_summary_f64(mean_a.data_ptr(), m2_a.data_ptr(), int(count_a), _ptr(mean_b), n,
+                                       _dev(out, torch.float64, "out").data_ptr(), _stream()))
+    return out
 
 
 # ---- column-sweep SpMM for static graphs (sgcn_spmm_cs.hip) --------------------------------------

@@ -9,7 +9,8 @@
 
 Flow (gcn/train.py:73-383): load_data -> PP products on the GPU (K11) -> placeholders ->
 train/test models from one template (shared weights) -> two schedulers -> SGDTrain epochs with
-validation, the reference's two log lines per epoch, early stopping -> Test().
+validation, the reference's two log lines per epoch, early stopping -> (--gradvar: the bias / variance
+study, GradientVariance) -> Test().
 """
 from __future__ import division, print_function
 
@@ -585,6 +586,57 @@ class Trainer(object):
         if par.rank == 0:
             train_model.save(self.sess)
 
+    # ---- the --gradvar bias / variance study (gcn/train.py:241-276) -------------------------------
+    def GradientVariance(self, observer=None):
+        """One fixed batch (the first ``batch_size`` training ids), its prediction and first-layer gradient drawn
+        ``gradvar_draws`` times under the evaluation sampler with the test model (the 'full' estimator: every neighbour
+        under --test_degree=10000) and as often under the training sampler with the training model ('part'); prints
+        the reference's seven lines -- bias and stdev of the sampled estimator, normalised by the mean magnitude of the
+        full one -- and returns their nine values as a dict.  Same draw sequence as the reference for the same seed.
+
+        The draws are folded into running fp64 statistics on the device (stats.DeviceStat): no per-draw copy or host
+        synchronisation.  ``observer(kind, pred, grad)``, kind 'full' or 'part', sees every draw's device tensors
+        (the gradient is a view the next draw overwrites).  One rank only: a multi-rank job skips the study."""
+        from .stats import DeviceStat, summary
+        log, ph = self.log, self.placeholders
+        if self.par.world > 1:
+            log('--gradvar: the bias / variance study runs on one rank; skipped ({} ranks)'.format(self.par.world))
+            return None
+        batch = self.train_d[:FLAGS.batch_size]
+        times = int(FLAGS.gradvar_draws)
+
+        def draw(sch, model, kind, preds, grads):
+            for _ in range(times):
+                feed_dict = sch.batch(batch)
+                feed_dict[ph['dropout']] = FLAGS.dropout
+                pred, grad = model.get_pred_and_grad_device(self.sess, feed_dict)
+                preds.add(pred)
+                grads.add(grad)
+                if observer is not None:
+                    observer(kind, pred, grad)
+
+        full_preds, full_grads = DeviceStat(), DeviceStat()
+        draw(self.eval_sch, self.test_model, 'full', full_preds, full_grads)
+        full_preds_m, full_pred_std, _ = summary(full_preds)
+        full_grads_m, full_grad_std, _ = summary(full_grads)
+        res = dict(full_pred_stdev=full_pred_std / full_preds_m, full_grad_stdev=full_grad_std / full_grads_m)
+        log('Full pred stdev = {}'.format(res['full_pred_stdev']))
+        log('Full grad stdev = {}'.format(res['full_grad_stdev']))
+
+        part_preds, part_grads = DeviceStat(), DeviceStat()
+        draw(self.train_sch, self.train_model, 'part', part_preds, part_grads)
+        _, part_pred_std, part_pred_bias = summary(part_preds, full_preds)
+        part_grads_mabs, part_grad_std, part_grad_bias = summary(part_grads, full_grads)
+        res.update(part_pred_bias=part_pred_bias / full_preds_m, part_pred_stdev=part_pred_std / full_preds_m,
+                   part_grad_bias=part_grad_bias / full_grads_m, part_grad_stdev=part_grad_std / full_grads_m,
+                   full_grads_m=full_grads_m, part_grad_std_mean=part_grad_std, part_grad_mean_abs=part_grads_mabs)
+        log('Part pred bias = {}'.format(res['part_pred_bias']))
+        log('Part pred stdev = {}'.format(res['part_pred_stdev']))
+        log('Part grad bias = {}'.format(res['part_grad_bias']))
+        log('Part grad stdev = {}'.format(res['part_grad_stdev']))
+        log(full_grads_m, part_grad_std, part_grads_mabs)
+        return res
+
     def Test(self):
         test_cost, test_acc, micro, macro, test_duration = self.evaluate(self.test_d)
         self.log("Test set results:", "cost=", "{:.5f}".format(test_cost),
@@ -601,11 +653,7 @@ def main(argv=None):
     tr = Trainer()
     tr.SGDTrain()
     if FLAGS.gradvar:
-        # --gradvar keeps what belongs to the path (the test graph = the training graph, histories restored by
-        # --load: models.py, Trainer.__init__); the bias / variance study it drove in the reference
-        # (gcn/train.py:241-276) is an analysis tool, out of scope
-        tr.log('--gradvar: analysis mode set up (test graph = training graph); the bias / variance study is '
-               'not part of this package -- use model.get_pred_and_grad(sess, feed) directly')
+        tr.GradientVariance()
     num_runs = FLAGS.num_layers + 1 if FLAGS.test_cv else 1
     for _ in range(num_runs):
         tr.Test()
