@@ -32,6 +32,7 @@ struct AggArgs {
     float* out_h; float* out_mu; int64_t ldo;
     int32_t d, nvec, cvd, off, concat;
     float* ws; int64_t ldw;
+    int32_t pchunks;          // chunks of a P segment (p_chunks): the same in the fused pass and in _pre, whatever their G
     // two-phase form (sgcn_vr_aggregate_pre/post_f32): the P-sum of every row goes to / comes from
     // accP[row * ldw ...] instead of living in registers across the two halves of the fused pass
     float* accP_out; const float* accP_in;
@@ -114,6 +115,19 @@ __device__ __forceinline__ void agg_finish(const AggArgs& a, int row, int vi, in
     agg_epilogue<VW>(a, row, vi, act, accP, acc1, acc2);
 }
 
+// The P-sum's order of summation: a segment is cut into `pchunks` chunks, each summed in nonzero order, and the chunk
+// sums are added in chunk order.  The count comes from the vector width the P operands alone allow (Hbar, its pitch, the
+// plan's workspace) -- never from h / mu / the outputs, which _pre does not see -- so the fused pass and _pre sum every
+// P row in the same order even when the fused pass runs narrower vectors (more lanes per group, fewer groups): its
+// groups then take several chunks each.
+static int p_chunks(int32_t d, const float* Hbar, int64_t ldh, const float* ws) {
+    const int vw = pick_vw(d, {Hbar, ws}, {ldh, ((int64_t)d + 3) / 4 * 4});
+    return kBlock / group_lanes((d + vw - 1) / vw) - 1;
+}
+
+// chunk sums one workgroup of agg_row_kernel<G, VW> keeps: p_chunks with vectors down to a quarter of VW's lanes wider
+constexpr int agg_max_chunks(int G, int VW) { return (kBlock / G) * (4 / VW) - 1 < 31 ? (kBlock / G) * (4 / VW) - 1 : 31; }
+
 // One WORKGROUP per plan segment (= one output row unless the row is longer than the plan's T): the workgroup's
 // NG = 256 / G lane groups take consecutive chunks of the segment's nonzeros, every lane keeps up to U row pieces of
 // the history in flight, and the NG partial sums are added in group order through LDS (fixed order: deterministic).
@@ -126,7 +140,8 @@ template <int G, int VW, int U>
 __global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgs a) {
     typedef typename Vec<VW>::type VT;
     constexpr int NG = kBlock / G, NP = NG - 1;       // NP groups share the P-sum, the last one walks the sampled adjacency
-    __shared__ float part[NG + 1][G * VW];
+    constexpr int NC = agg_max_chunks(G, VW);          // chunk sums, then the two sampled-adjacency sums
+    __shared__ float part[NC + 2][G * VW];
     const int lig = threadIdx.x & (G - 1), gq = threadIdx.x / G;
     const int slab = (int)(blockIdx.x / a.nseg);
     const int64_t s = blockIdx.x % a.nseg;
@@ -144,48 +159,55 @@ __global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgs a) {
     const bool finish_here = slot < 0 && !a.accP_out;              // an unsplit row of the fused pass
     const float* Hl = a.H + (int64_t)vi * VW;
 
+    const int nc = a.pchunks;
     if (gq < NP) {
-        const int chunk = (end - start + NP - 1) / NP;
-        const int gs = start + gq * chunk, ge = min(end, gs + chunk);
-        VT accP = vzero<VW>();
-        for (int p0 = gs; p0 < ge; p0 += G) {
-            const int n = min(G, ge - p0);
-            int myrow = 0;
-            float myval = 0.f;
-            if (lig < n) {
-                myrow = a.ffield[a.f_col[p0 + lig]];
-                myval = a.f_val[p0 + lig];
-            }
-            for (int j = 0; j < n; j += U) {
-                VT b[U];
-                float v[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const bool in = j + u < n;
-                    const int c = bcast_i<G>(myrow, in ? j + u : 0);
-                    v[u] = in ? bcast_f<G>(myval, j + u) : 0.f;
-                    b[u] = (act && in) ? vload<VW>(Hl + (int64_t)c * a.ldh) : vzero<VW>();
+        const int chunk = (end - start + nc - 1) / nc;
+        for (int ck = gq; ck < nc; ck += NP) {             // (several chunks per group when nc > NP)
+            const int gs = start + ck * chunk, ge = min(end, gs + chunk);
+            VT accP = vzero<VW>();
+            for (int p0 = gs; p0 < ge; p0 += G) {
+                const int n = min(G, ge - p0);
+                int myrow = 0;
+                float myval = 0.f;
+                if (lig < n) {
+                    myrow = a.ffield[a.f_col[p0 + lig]];
+                    myval = a.f_val[p0 + lig];
                 }
+                for (int j = 0; j < n; j += U) {
+                    VT b[U];
+                    float v[U];
 #pragma unroll
-                for (int u = 0; u < U; u++) accP += v[u] * b[u];
+                    for (int u = 0; u < U; u++) {
+                        const bool in = j + u < n;
+                        const int c = bcast_i<G>(myrow, in ? j + u : 0);
+                        v[u] = in ? bcast_f<G>(myval, j + u) : 0.f;
+                        b[u] = (act && in) ? vload<VW>(Hl + (int64_t)c * a.ldh) : vzero<VW>();
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; u++) accP += v[u] * b[u];
+                }
             }
+            vstore<VW>(&part[ck][lig * VW], accP);
         }
-        vstore<VW>(&part[gq][lig * VW], accP);
     } else if (finish_here) {
         // beside the P-sum instead of after it: its index chain (rowptr -> column -> ifield -> rows) is as long as the P-sum's
         VT acc1, acc2;
         agg_apart<G, VW>(a, row, vi, lig, act, acc1, acc2);
-        vstore<VW>(&part[NP][lig * VW], acc1);
-        vstore<VW>(&part[NG][lig * VW], acc2);
+        vstore<VW>(&part[NC][lig * VW], acc1);
+        vstore<VW>(&part[NC + 1][lig * VW], acc2);
     }
     __syncthreads();
     if (gq != 0) return;
     VT accP = vload<VW>(&part[0][lig * VW]);
+    if (nc == NP) {                                    // (one chunk per group: the usual case, unrolled)
 #pragma unroll
-    for (int q = 1; q < NP; q++) accP += vload<VW>(&part[q][lig * VW]);
+        for (int q = 1; q < NP; q++) accP += vload<VW>(&part[q][lig * VW]);
+    } else {
+        for (int q = 1; q < nc; q++) accP += vload<VW>(&part[q][lig * VW]);
+    }
     if (slot >= 0) { if (act) vstore<VW>(a.ws + (int64_t)slot * a.ldw + (int64_t)vi * VW, accP); }
     else if (a.accP_out) { if (act) vstore<VW>(a.accP_out + (int64_t)row * a.ldw + (int64_t)vi * VW, accP); }
-    else agg_epilogue<VW>(a, row, vi, act, accP, vload<VW>(&part[NP][lig * VW]), vload<VW>(&part[NG][lig * VW]));
+    else agg_epilogue<VW>(a, row, vi, act, accP, vload<VW>(&part[NC][lig * VW]), vload<VW>(&part[NC + 1][lig * VW]));
 }
 
 template <int G, int VW>
@@ -249,6 +271,8 @@ static int launch_agg_post(int G, const AggArgs& a, int32_t n1, hipStream_t st) 
 template <int VW>
 static int launch_agg(int G, const AggArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
     const int nslab = (a.nvec + G - 1) / G;
+    SGCN_REQUIRE(a.pchunks >= 1 && a.pchunks <= agg_max_chunks(G, VW), "vr_aggregate: %d chunks of a P row, at most %d here",
+                 a.pchunks, agg_max_chunks(G, VW));
     const int64_t nblocks = a.nseg * nslab;                      // one workgroup per (segment, feature slab)
     SGCN_REQUIRE(nblocks < (1ll << 31), "vr_aggregate: grid too large");
 #define SGCN_AGG_CASE(GG)                                                                          \
@@ -317,6 +341,7 @@ extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_c
     if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
+    a.pchunks = p_chunks(d, Hbar, ldh, f_plan ? f_plan->dev_ws : nullptr);
     a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     hipStream_t st = (hipStream_t)stream;
     if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
@@ -330,8 +355,9 @@ extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_c
 // every output row into accP (n1 x ldw, ldw = 4*ceil(d/4)), so that it can run BESIDE the dense layers
 // that produce h / mu (the step program issues it on the auxiliary stream); _post is the rest of the
 // fused pass.  Per element the two phases perform exactly the fused kernel's operations in the fused
-// kernel's order -- accP only takes a round trip through memory -- so pre + post == sgcn_vr_aggregate_f32
-// bit for bit (tests/test_kernels_gpu.py).
+// kernel's order -- accP only takes a round trip through memory, and both cut a P row into the same chunks (p_chunks),
+// whatever vector width h / mu / the outputs allow the fused pass -- so pre + post == sgcn_vr_aggregate_f32 bit for bit
+// (tests/test_kernels_gpu.py, tests/test_sparse_exact_gpu.py).
 extern "C" int sgcn_vr_aggregate_pre_f32(const int32_t* f_rowptr, const int32_t* f_col, const float* f_val,
                                          int32_t n1, int32_t nf, int32_t d, const float* Hbar, int64_t ldh,
                                          const int32_t* ffield, float* accP, const sgcn_plan_t* f_plan,
@@ -357,6 +383,7 @@ extern "C" int sgcn_vr_aggregate_pre_f32(const int32_t* f_rowptr, const int32_t*
     const int vw = pick_vw(d, {Hbar, accP, f_plan ? f_plan->dev_ws : nullptr}, {ldh, a.ldw});
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
+    a.pchunks = p_chunks(d, Hbar, ldh, f_plan ? f_plan->dev_ws : nullptr);
     a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     hipStream_t st = (hipStream_t)stream;
     if (vw == 4) return launch_agg<4>(G, a, f_plan, st);

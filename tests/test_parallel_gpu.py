@@ -66,35 +66,49 @@ def test_sharded_spmm_two_ranks(tmp_path, kernel):
         assert onp.rel_err(got, want) <= TOL, key
 
 
-def test_sharded_spmm_blocks_tile_the_full_product(dev=None):
+def test_sharded_spmm_blocks_tile_the_full_product():
     """Four nnz-balanced row blocks of S-Reddit/10 (built one after the other on this GPU, no
-    collectives: the operand is resident) reproduce the unsharded product, forward and backward."""
+    collectives: the operand is resident), forward and backward, against an independent reference of the
+    whole product (tests/sparse_cases.py): bit for bit the exact product on dyadic inputs, and within the
+    per-element fp64 bound on the graph's own values with N(0, 1) operands."""
     import types
-    from stochastic_gcn_amd import ops, synthetic
+    import sparse_cases as sc
+    from stochastic_gcn_amd import synthetic
     from stochastic_gcn_amd.parallel import ShardedSpMM
-    from oracle import oracle_np as onp
     dev = torch.device("cuda:0")
     n, _, full_adj, *_ = synthetic.reddit_like(n=23296, m=1160000, splits=(15241, 2369, 5533), seed=3,
                                                with_features=False)
-    d = 96
-    g = torch.Generator(device=dev); g.manual_seed(0)
-    B = torch.randn((n, d), device=dev, generator=g)
-    dC = torch.randn((n, d), device=dev, generator=g)
-    whole = ops.DeviceCSR.from_scipy(full_adj, dev, with_transpose=True)
-    want_c, want_db = ops.spmm(whole, B), ops.spmm(whole.transpose, dC)
-    world, rows, nnz = 4, 0, []
-    cs, dbs = [], []
-    for r in range(world):
-        sh = ShardedSpMM(types.SimpleNamespace(rank=r, world=world, active=False), full_adj, dev)
-        assert sh.lo == rows
-        rows = sh.hi
-        nnz.append(sh.local_nnz)
-        cs.append(sh.forward(B))
-        dbs.append(sh.backward(dC))
-    assert rows == n and sum(nnz) == full_adj.nnz
-    assert max(nnz) - min(nnz) <= 2 * int(np.diff(full_adj.indptr).max())           # balanced by nonzeros
-    assert onp.rel_err(torch.cat(cs).cpu().numpy(), want_c.cpu().numpy()) <= TOL
-    assert onp.rel_err(torch.cat(dbs).cpu().numpy(), want_db.cpu().numpy()) <= TOL
+    for d, exact in ((96, True), (66, True), (96, False)):
+        rng = np.random.RandomState(d + exact)
+        a = sc.dyadic(full_adj, rng) if exact else full_adj
+        at = a.T.tocsr()
+        B = sc.ints(rng, (n, d)) if exact else rng.standard_normal((n, d)).astype(np.float32)
+        dC = sc.ints(rng, (n, d)) if exact else rng.standard_normal((n, d)).astype(np.float32)
+        pitch = (d + 3) // 4 * 4                       # (the column sweep takes 16-byte aligned rows)
+        Bd = torch.zeros((n, pitch), device=dev)[:, :d]
+        dCd = torch.zeros((n, pitch), device=dev)[:, :d]
+        Bd.copy_(torch.from_numpy(B))
+        dCd.copy_(torch.from_numpy(dC))
+        world, rows, nnz = 4, 0, []
+        cs, dbs = [], []
+        for r in range(world):
+            sh = ShardedSpMM(types.SimpleNamespace(rank=r, world=world, active=False), a, dev, d=d)
+            assert sh.lo == rows
+            rows = sh.hi
+            nnz.append(sh.local_nnz)
+            cs.append(sh.forward(Bd).double().cpu().numpy())
+            dbs.append(sh.backward(dCd).double().cpu().numpy())
+        assert rows == n and sum(nnz) == a.nnz
+        assert max(nnz) - min(nnz) <= 2 * int(np.diff(a.indptr).max())           # balanced by nonzeros
+        assert torch.equal(Bd.cpu(), torch.from_numpy(B)) and torch.equal(dCd.cpu(), torch.from_numpy(dC))
+        for m, X, got, what in ((a, B, np.concatenate(cs), "forward"), (at, dC, np.concatenate(dbs), "backward")):
+            assert got.shape == (n, d)
+            if exact:
+                bad = got != sc.spmm_exact(m, X)
+                assert not bad.any(), "%s: %d rows differ from the exact product" % (what, int(bad.any(1).sum()))
+            else:
+                bad = ~(np.abs(got - sc.spmm_f64(m, X)) <= sc.fp64_bound(m, X))
+                assert not bad.any(), "%s: %d elements outside the fp64 bound" % (what, int(bad.sum()))
 
 
 def test_sharded_spmm_rmat_eight_blocks_d256():
