@@ -639,7 +639,8 @@ extern "C" int sgcn_gemm_f32(int32_t trans_a, int32_t trans_b, int32_t M, int32_
                              const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c, void* stream) {
     SGCN_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
     if (M == 0 || N == 0) return SGCN_OK;
-    SGCN_REQUIRE(A && B && C, "gemm: null operand");
+    // (K = 0: C = 0 or C unchanged, and the operands are never read -- an empty tensor has no address)
+    SGCN_REQUIRE(C && (K == 0 || (A && B)), "gemm: null operand");
     GemmArgs g{};
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
     g.M = M; g.N = N; g.K = K; g.accumulate = accumulate; g.epi = 0;
@@ -702,7 +703,8 @@ extern "C" int sgcn_dense_fwd_f32(int32_t M, int32_t N, int32_t K, const float* 
                                   const int32_t* gidx, const int32_t* gidx2, void* stream) {
     SGCN_REQUIRE(M >= 0 && N >= 0 && K >= 0, "dense_fwd: negative size");
     if (M == 0 || N == 0) return SGCN_OK;
-    SGCN_REQUIRE(X && W && Y, "dense_fwd: null operand");
+    // (all rows from X2: X has none and is never read -- an empty tensor has no address)
+    SGCN_REQUIRE((X || (X2 && split == 0)) && W && Y, "dense_fwd: null operand");
     const int norm = (offset && scale) ? 1 : 0;
     SGCN_REQUIRE(!norm || (xhat && rstd), "dense_fwd: LayerNorm needs xhat / rstd");
     SGCN_REQUIRE(N <= kTN || (!norm && !relu), "dense_fwd: fused epilogue needs N <= 128");

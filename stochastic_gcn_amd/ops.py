@@ -1435,7 +1435,8 @@ def dense_bwd(dy, y, ctx, scale, relu, x, W, dW, doffset=None, dscale=None, need
     yp, ldy = _rows2d(y, "y") if pre else (None, 0)
     g_tmp = torch.empty((n, N), dtype=torch.float32, device=dy.device) if pre else None
     dx = torch.empty((n, K), dtype=torch.float32, device=dy.device) if need_dx else None
-    key = (n, N, K, norm)
+    # (the split-K factors, hence the sizes, follow the knob gemm_min_steps: a size cached under another value of it is short)
+    key = (n, N, K, norm, int(lib.sgcn_tune_get(b"gemm_min_steps")))
     need = _DENSE_BWD_WS.get(key)
     if need is None:
         need = ((int(lib.sgcn_ln_act_bwd_ws_floats(n, N)) + 3) // 4 * 4 if norm else 0) + \

@@ -15,6 +15,7 @@ import scipy.sparse as sp
 import torch
 
 import sparse_cases as sc
+from gpu_checks import Operand, check, f32 as _f32
 
 pytestmark = pytest.mark.gpu
 
@@ -60,57 +61,6 @@ def _scales(rng, n, exact):
 
 def _pitch(d, pad, align4):
     return ((d + 3) // 4 * 4 if align4 else d) + pad
-
-
-class Operand(object):
-    """a host array on the device inside a NaN-filled buffer (pitch padding and one row more): ``view`` is what a kernel
-    gets; ``unchanged()`` checks afterwards that no bit of the buffer moved"""
-
-    def __init__(self, x, dev, pitch):
-        rows, d = x.shape
-        self.buf = torch.full((rows + 1, max(pitch, d)), float("nan"), device=dev)
-        self.buf[:rows, :d] = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        self.view = self.buf[:rows, :d]
-        self.bits = self.buf.view(torch.int32).clone()
-
-    def unchanged(self):
-        return torch.equal(self.buf.view(torch.int32), self.bits)
-
-
-def _f32(x, dev):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-
-
-def check(call, dev, M, d, pitch, ref, bound=None, C_in=None, operands=(), what=""):
-    """Run ``call(out)`` twice on a fresh NaN-sentinelled output (holding C_in, when given) and check: the two results are
-    bit-identical, the sentinels and the operands are untouched, and the result equals ``ref`` bit for bit (bound None)
-    or lies within ``bound`` of it."""
-    outs = []
-    for _ in range(2):
-        buf = torch.full((M + 2, pitch), float("nan"), device=dev)
-        if C_in is not None:
-            buf[:M, :d] = torch.from_numpy(np.ascontiguousarray(C_in)).to(dev)
-        before = buf.view(torch.int32).clone()
-        call(buf[:M, :d])
-        torch.cuda.synchronize()
-        after = buf.view(torch.int32)
-        assert torch.equal(after[:M, d:], before[:M, d:]), "%s: the pitch padding of out was written" % what
-        assert torch.equal(after[M:], before[M:]), "%s: rows after M were written" % what
-        outs.append(buf)
-    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "%s: two calls differ" % what
-    for o in operands:
-        assert o.unchanged(), "%s: an operand was modified" % what
-    got = outs[0][:M, :d].double().cpu().numpy()
-    if bound is None:
-        bad = got != ref
-        assert not bad.any(), "%s: %d of %d elements (%d rows, first %s) differ from the exact product" % (
-            what, int(bad.sum()), bad.size, int(bad.any(axis=1).sum()), np.nonzero(bad.any(axis=1))[0][:8])
-    else:
-        err = np.abs(got - ref)
-        bad = ~(err <= bound)
-        assert not bad.any(), "%s: %d elements (rows %s) outside the fp64 bound (worst excess %g)" % (
-            what, int(bad.sum()), np.nonzero(bad.any(axis=1))[0][:8], float(np.nanmax(np.where(bad, err - bound, 0))))
-    return outs[0]
 
 
 def _reference(a, B, exact, **kw):
