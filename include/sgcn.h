@@ -48,7 +48,9 @@ const char* sgcn_last_error(void);
  *   v15 sgcn_coll_init_exchange / _has_exchange / sgcn_coll_allgather_x_i32 (a second communicator for the history exchange);
  *       step ops HIST_PACK .. HIST_APPLY: aux = 2 = the library's exchange stream, joined at the end of the run
  *   v16 packed minibatch: + the medg weights in the order of adj^T's nonzeros (descriptors behind the CSR table); step ops
- *       GEMM .. GATE (the --det_dropout stacks as step programs) */
+ *       GEMM .. GATE (the --det_dropout stacks as step programs)
+ *       (additive, still v16: sgcn_moments_*; the bfloat16 history -- sgcn_vr_aggregate_h16 / _pre_h16 / _post_h16,
+ *       sgcn_scatter_rows_h16, sgcn_gather_rows_h16, sgcn_hist_apply_h16, step ops 48 .. 53) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -356,6 +358,48 @@ int sgcn_gather_rows_f32(const float* dev_in, int64_t ldi, const int32_t* dev_r,
  * r[i] < 0 skips row i (padding of the fixed-capacity multi-GPU history exchange). */
 int sgcn_scatter_rows_f32(float* dev_H, int64_t ldh, const int32_t* dev_r, int32_t n,
                           int32_t d, const float* dev_src, int64_t lds, void* stream);
+
+/* ---- bfloat16 history (--history_dtype bf16; additive exports, no reference counterpart) -------------------------------
+ * The history is the one operand of the step whose storage precision does not bias the estimator: both terms of
+ *   mu_nbr = A (mu - Hbar[ifield]) + P Hbar[ffield]
+ * read the same stored rows, so its expectation over the sampled A is P mu for ANY table.  A bfloat16 table is
+ * N x ldh uint16 with ldh in ELEMENTS, ldh % 8 == 0, ldh >= d and a 16-byte aligned base (SGCN_ERR_INVALID otherwise);
+ * columns [d, ldh) are never written.
+ *   store = round-to-nearest-even of the fp32 bits u: ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF  (+-0, +-inf kept,
+ *           subnormals rounded, not flushed; finite values above the largest bfloat16 become inf; a NaN stays a NaN)
+ *   load  = bits << 16, exact
+ * All arithmetic stays fp32: sgcn_vr_aggregate_h16 / _pre_h16 / _post_h16 give, bit for bit, what sgcn_vr_aggregate_f32 /
+ * _pre_f32 / _post_f32 give on a 16-byte aligned fp32 table of the same element pitch that holds the widened values (the
+ * same kernels, instantiated with a widening load; same vector width, lane groups and p_chunks cut of a P row).
+ * sgcn_scatter_rows_h16 / sgcn_gather_rows_h16 mirror sgcn_scatter_rows_f32 / sgcn_gather_rows_f32 with an fp32 source /
+ * destination; dev_r == NULL means rows 0 .. n-1 in place (a whole table is saved / loaded without an N-long index).
+ * sgcn_hist_apply_h16 mirrors sgcn_hist_apply_f32: the payload stays sgcn_hist_pack_f32's fp32 row bits. */
+int sgcn_vr_aggregate_h16(const int32_t* dev_a_rowptr, const int32_t* dev_a_col,
+                          const float* dev_a_val, const int32_t* dev_f_rowptr,
+                          const int32_t* dev_f_col, const float* dev_f_val,
+                          int32_t n1, int32_t n0, int32_t nf, int32_t d,
+                          const float* dev_h, const float* dev_mu, int64_t ldx,
+                          const uint16_t* dev_Hbar, int64_t ldh,
+                          const int32_t* dev_ifield, const int32_t* dev_ffield,
+                          const float* dev_s,
+                          float* dev_out_h, float* dev_out_mu, int64_t ldo,
+                          int32_t cvd, int32_t concat_self,
+                          const sgcn_plan_t* f_plan, void* stream);
+int sgcn_vr_aggregate_pre_h16(const int32_t* dev_f_rowptr, const int32_t* dev_f_col, const float* dev_f_val,
+                              int32_t n1, int32_t nf, int32_t d, const uint16_t* dev_Hbar, int64_t ldh,
+                              const int32_t* dev_ffield, float* dev_accP, const sgcn_plan_t* f_plan,
+                              void* stream);
+int sgcn_vr_aggregate_post_h16(const int32_t* dev_a_rowptr, const int32_t* dev_a_col, const float* dev_a_val,
+                               int32_t n1, int32_t n0, int32_t d, const float* dev_h, const float* dev_mu,
+                               int64_t ldx, const uint16_t* dev_Hbar, int64_t ldh, const int32_t* dev_ifield,
+                               const float* dev_s, float* dev_out_h, float* dev_out_mu, int64_t ldo,
+                               int32_t cvd, int32_t concat_self, const float* dev_accP, void* stream);
+int sgcn_gather_rows_h16(const uint16_t* dev_H, int64_t ldh, const int32_t* dev_r, int32_t n,
+                         int32_t d, float* dev_out, int64_t ldo, void* stream);
+int sgcn_scatter_rows_h16(uint16_t* dev_H, int64_t ldh, const int32_t* dev_r, int32_t n,
+                          int32_t d, const float* dev_src, int64_t lds, void* stream);
+int sgcn_hist_apply_h16(uint16_t* dev_H, int64_t ldh, const int32_t* dev_recv, int32_t world, int32_t cap, int32_t d,
+                        int32_t* dev_owner, void* stream);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-
@@ -769,6 +813,15 @@ enum {
     SGCN_OP_DET_AGG_PREP_BWD = 45, /* sgcn_det_agg_prep_bwd_f32 (var, ds, sbar, g_ds2, g_msig2, n0, d, add, ldadd, add_rows, d_var) */
     SGCN_OP_RELU_EPS = 46,      /* sgcn_relu_eps_f32 (raw, ldr, n, d, eps, y, ldy) */
     SGCN_OP_GATE = 47,          /* sgcn_gate_f32 (raw, ldr, g, ldg, n, d, out) */
+    /* bfloat16 history (ABI v16, additive): the argument lists of ops 3 / 14 / 15 / 7 / 16 / 32, the table a uint16 pointer
+     * with its leading dimension in elements; joins, forks and `aux` exactly as for their fp32 forms.  (The fp32 scatter
+     * behind ADAM rides in the optimizer's launch; SCATTER_ROWS_H16 is a launch of its own behind it.) */
+    SGCN_OP_VR_AGG_H16 = 48,          /* sgcn_vr_aggregate_h16 */
+    SGCN_OP_VR_AGG_PRE_H16 = 49,      /* sgcn_vr_aggregate_pre_h16, on the auxiliary stream */
+    SGCN_OP_VR_AGG_POST_H16 = 50,     /* sgcn_vr_aggregate_post_h16 behind the auxiliary stream */
+    SGCN_OP_SCATTER_ROWS_H16 = 51,    /* sgcn_scatter_rows_h16 */
+    SGCN_OP_AUX_SCATTER_ROWS_H16 = 52,/* sgcn_scatter_rows_h16 on the auxiliary stream */
+    SGCN_OP_HIST_APPLY_H16 = 53,      /* sgcn_hist_apply_h16 (H, ldh, recv, world, cap, d, owner, aux) */
     SGCN_OP_GRAD_STORE = 22     /* no arguments, anywhere in the program: the run is in gradient-STORE mode -- every DENSE_BWD
                                  * writes its dW / doffset / dscale instead of adding to them, so the program zeroes nothing
                                  * (it must write every parameter gradient exactly once per step); and the statistics

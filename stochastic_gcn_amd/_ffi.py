@@ -134,6 +134,17 @@ SIGNATURES = {
                                              P, P, P, P, C.c_int64, C.c_int32, C.c_int32, P, P]),
     "sgcn_gather_rows_f32": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "sgcn_scatter_rows_f32": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
+    # bfloat16 history (--history_dtype bf16): the same argument lists, the table a uint16 pointer with ldh in elements
+    "sgcn_vr_aggregate_h16": (C.c_int, [P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, P, P, C.c_int64, P, C.c_int64, P, P, P, P, P,
+                                        C.c_int64, C.c_int32, C.c_int32, C.POINTER(Plan), P]),
+    "sgcn_vr_aggregate_pre_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, P,
+                                            C.POINTER(Plan), P]),
+    "sgcn_vr_aggregate_post_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, P, C.c_int64, P, C.c_int64,
+                                             P, P, P, P, C.c_int64, C.c_int32, C.c_int32, P, P]),
+    "sgcn_gather_rows_h16": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
+    "sgcn_scatter_rows_h16": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
+    "sgcn_hist_apply_h16": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, C.c_int32, P, P]),
     "sgcn_coll_available": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgcn_coll_retain": (C.c_int, []),
     "sgcn_coll_abort": (C.c_int, []),

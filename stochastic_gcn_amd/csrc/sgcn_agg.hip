@@ -17,17 +17,20 @@
 // 16-byte vector per lane (G = 32 for d = 128, 8 for d = 32), feature slabs of G vectors
 // for wider rows.
 #include "sgcn_dev.h"
+#include <type_traits>
 
 namespace sgcn {
 
 int group_lanes(int nvec);  // sgcn_spmm.hip
 
-struct AggArgs {
+// HT: the history's element -- float, or uint16_t for a bfloat16 table (sgcn_vr_aggregate_*_h16); everything else is fp32
+template <class HT>
+struct AggArgsT {
     const int32_t* a_rowptr; const int32_t* a_col; const float* a_val;
     const int32_t* f_rowptr; const int32_t* f_col; const float* f_val;
     const sgcn_seg_t* seg; int64_t nseg; int64_t nsegblk;
     const float* h; const float* mu; int64_t ldx;
-    const float* H; int64_t ldh;
+    const HT* H; int64_t ldh;     // ldh in elements of HT
     const int32_t* ifield; const int32_t* ffield; const float* s;
     float* out_h; float* out_mu; int64_t ldo;
     int32_t d, nvec, cvd, off, concat;
@@ -37,6 +40,59 @@ struct AggArgs {
     // accP[row * ldw ...] instead of living in registers across the two halves of the fused pass
     float* accP_out; const float* accP_in;
 };
+typedef AggArgsT<float> AggArgs;
+
+// VW history elements: `hraw` is the load (4 * VW bytes of an fp32 table, 2 * VW bytes of a bfloat16 one, kept as the
+// dwords it fetched), `hwiden` makes fp32 of what it returned (nothing to do; bits << 16, exact) -- the ONLY places where
+// the two instantiations of the kernels below differ.  They are two steps so that agg_row_kernel can request its U rows
+// first and widen them when it adds them; `hpin` keeps the compiler from moving the widening back up to the load, where
+// every load is followed by a wait for it and the U requests in flight are gone (measured: 12.8 us per launch of the
+// Reddit step against 9.3 for the fp32 table).
+template <class HT, int VW> struct HRaw;
+template <int VW> struct HRaw<float, VW> { typedef typename Vec<VW>::type type; };
+template <> struct HRaw<uint16_t, 4> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
+template <> struct HRaw<uint16_t, 2> { typedef uint32_t type; };
+template <> struct HRaw<uint16_t, 1> { typedef uint32_t type; };
+
+template <int VW>
+__device__ __forceinline__ typename HRaw<float, VW>::type hraw(const float* p) { return vload<VW>(p); }
+template <int VW>
+__device__ __forceinline__ typename HRaw<uint16_t, VW>::type hraw(const uint16_t* p) {
+    if constexpr (VW == 1) return *p;
+    else return *reinterpret_cast<const typename HRaw<uint16_t, VW>::type*>(p);
+}
+template <class HT, int VW>
+__device__ __forceinline__ typename HRaw<HT, VW>::type hraw_zero() {
+    typename HRaw<HT, VW>::type z = {};
+    return z;
+}
+// (not for scalar lanes, VW == 1: there the compiler contracts SOME of the fp32 form's U products into fused multiply-adds,
+// and only the unpinned bf16 form gets the same ones -- tests/test_history_bf16_gpu.py compares the bits for d = 7, 25, 41)
+template <class HT, int VW, class RT>
+__device__ __forceinline__ void hpin(RT& r) {
+    if constexpr (!std::is_same<HT, float>::value && VW > 1) asm volatile("" : "+v"(r));
+}
+template <int VW>
+__device__ __forceinline__ typename Vec<VW>::type hwiden(typename Vec<VW>::type r) { return r; }
+__device__ __forceinline__ float hwiden1(uint32_t r) { return __uint_as_float(r << 16); }
+template <int VW>
+__device__ __forceinline__ typename Vec<VW>::type hwiden(uint32_t r) {
+    static_assert(VW <= 2, "two bfloat16 per dword");
+    if constexpr (VW == 1) {
+        return hwiden1(r);
+    } else {
+        typename Vec<2>::type v = {hwiden1(r), __uint_as_float(r & 0xffff0000u)};
+        return v;
+    }
+}
+template <int VW>
+__device__ __forceinline__ typename Vec<VW>::type hwiden(typename HRaw<uint16_t, 4>::type r) {
+    static_assert(VW == 4, "four bfloat16 per dword pair");
+    typename Vec<4>::type v = {hwiden1(r.x), __uint_as_float(r.x & 0xffff0000u), hwiden1(r.y), __uint_as_float(r.y & 0xffff0000u)};
+    return v;
+}
+template <int VW, class HT>
+__device__ __forceinline__ typename Vec<VW>::type hload(const HT* p) { return hwiden<VW>(hraw<VW>(p)); }
 
 template <int VW>
 __device__ __forceinline__ void store_masked(float* p, typename Vec<VW>::type v, int left) {
@@ -45,8 +101,8 @@ __device__ __forceinline__ void store_masked(float* p, typename Vec<VW>::type v,
 }
 
 // Sampled-adjacency part of one (row, vector): acc1 = A (mu - Hbar[ifield]) | A x,  acc2 = A (h - mu) | A Hbar[ifield]
-template <int G, int VW>
-__device__ __forceinline__ void agg_apart(const AggArgs& a, int row, int vi, int lig, bool act,
+template <int G, int VW, class HT>
+__device__ __forceinline__ void agg_apart(const AggArgsT<HT>& a, int row, int vi, int lig, bool act,
                                           typename Vec<VW>::type& acc1, typename Vec<VW>::type& acc2) {
     typedef typename Vec<VW>::type VT;
     acc1 = vzero<VW>(); acc2 = vzero<VW>();
@@ -66,9 +122,22 @@ __device__ __forceinline__ void agg_apart(const AggArgs& a, int row, int vi, int
             const int hr = bcast_i<G>(myhist, j);
             const float v = bcast_f<G>(myval, j);
             if (!act) continue;
-            const VT hb = vload<VW>(a.H + (int64_t)hr * a.ldh + voff);
+            const VT hb = hload<VW>(a.H + (int64_t)hr * a.ldh + voff);
             const VT xv = vload<VW>(a.h + (int64_t)c * a.ldx + voff);
-            if (a.cvd) {
+            if constexpr (VW == 1 && !std::is_same<HT, float>::value) {
+                // The compiler contracts the scalar fp32 form below into ONE fused multiply-add per sum (v_pk_fma_f32 on the
+                // pair, every G) and leaves the vector forms as multiply + add; with the widening shift in front of it, it
+                // stops doing so for G < 64 (multiply in the branch, add behind it).  Spell the fp32 instantiation's
+                // rounding out, so that the two agree bit for bit whatever it decides here.
+                if (a.cvd) {
+                    const float mv = a.mu[(int64_t)c * a.ldx + voff];
+                    acc1 = __builtin_fmaf(v, mv - hb, acc1);
+                    acc2 = __builtin_fmaf(v, xv - mv, acc2);
+                } else {
+                    acc1 = __builtin_fmaf(v, xv, acc1);
+                    acc2 = __builtin_fmaf(v, hb, acc2);
+                }
+            } else if (a.cvd) {
                 const VT mv = vload<VW>(a.mu + (int64_t)c * a.ldx + voff);
                 acc1 += v * (mv - hb);   // A (mu - Hbar[ifield])
                 acc2 += v * (xv - mv);   // A (h - mu)
@@ -81,8 +150,8 @@ __device__ __forceinline__ void agg_apart(const AggArgs& a, int row, int vi, int
 }
 
 // The three sums combined in the reference's order, and the (self | neighbour) concat written in place.
-template <int VW>
-__device__ __forceinline__ void agg_epilogue(const AggArgs& a, int row, int vi, bool act, typename Vec<VW>::type accP,
+template <int VW, class HT>
+__device__ __forceinline__ void agg_epilogue(const AggArgsT<HT>& a, int row, int vi, bool act, typename Vec<VW>::type accP,
                                              typename Vec<VW>::type acc1, typename Vec<VW>::type acc2) {
     typedef typename Vec<VW>::type VT;
     if (!act) return;
@@ -107,8 +176,8 @@ __device__ __forceinline__ void agg_epilogue(const AggArgs& a, int row, int vi, 
 }
 
 // Sampled-adjacency part + epilogue for one (row, vector) given the finished P-sum.
-template <int G, int VW>
-__device__ __forceinline__ void agg_finish(const AggArgs& a, int row, int vi, int lig, bool act,
+template <int G, int VW, class HT>
+__device__ __forceinline__ void agg_finish(const AggArgsT<HT>& a, int row, int vi, int lig, bool act,
                                            typename Vec<VW>::type accP) {
     typename Vec<VW>::type acc1, acc2;
     agg_apart<G, VW>(a, row, vi, lig, act, acc1, acc2);
@@ -136,8 +205,8 @@ constexpr int agg_max_chunks(int G, int VW) { return (kBlock / G) * (4 / VW) - 1
 // kernel every row then needed; this form has the whole 26 MB requested at once and needs the fix-up only for the rows
 // longer than T = 128 (one round of 8 groups x U = 16; a longer segment would make the launch wait for its extra rounds:
 // T = 1,024 measured 29-34 us, set by the one hub row half of the batches contain).
-template <int G, int VW, int U>
-__global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgs a) {
+template <int G, int VW, int U, class HT>
+__global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgsT<HT> a) {
     typedef typename Vec<VW>::type VT;
     constexpr int NG = kBlock / G, NP = NG - 1;       // NP groups share the P-sum, the last one walks the sampled adjacency
     constexpr int NC = agg_max_chunks(G, VW);          // chunk sums, then the two sampled-adjacency sums
@@ -157,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgs a) {
     const int vi = slab * G + lig;
     const bool act = vi < a.nvec;
     const bool finish_here = slot < 0 && !a.accP_out;              // an unsplit row of the fused pass
-    const float* Hl = a.H + (int64_t)vi * VW;
+    const HT* Hl = a.H + (int64_t)vi * VW;
 
     const int nc = a.pchunks;
     if (gq < NP) {
@@ -173,18 +242,19 @@ __global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgs a) {
                     myrow = a.ffield[a.f_col[p0 + lig]];
                     myval = a.f_val[p0 + lig];
                 }
+                hpin<HT, VW>(myrow); hpin<HT, VW>(myval);     // (bf16: the waits for these two land here, not between the U requests)
                 for (int j = 0; j < n; j += U) {
-                    VT b[U];
+                    typename HRaw<HT, VW>::type b[U];
                     float v[U];
 #pragma unroll
                     for (int u = 0; u < U; u++) {
                         const bool in = j + u < n;
                         const int c = bcast_i<G>(myrow, in ? j + u : 0);
                         v[u] = in ? bcast_f<G>(myval, j + u) : 0.f;
-                        b[u] = (act && in) ? vload<VW>(Hl + (int64_t)c * a.ldh) : vzero<VW>();
+                        b[u] = (act && in) ? hraw<VW>(Hl + (int64_t)c * a.ldh) : hraw_zero<HT, VW>();
                     }
 #pragma unroll
-                    for (int u = 0; u < U; u++) accP += v[u] * b[u];
+                    for (int u = 0; u < U; u++) { hpin<HT, VW>(b[u]); accP += v[u] * hwiden<VW>(b[u]); }
                 }
             }
             vstore<VW>(&part[ck][lig * VW], accP);
@@ -210,8 +280,8 @@ __global__ __launch_bounds__(kBlock) void agg_row_kernel(AggArgs a) {
     else agg_epilogue<VW>(a, row, vi, act, accP, vload<VW>(&part[NC][lig * VW]), vload<VW>(&part[NC + 1][lig * VW]));
 }
 
-template <int G, int VW>
-__global__ __launch_bounds__(kBlock) void agg_fix_kernel(AggArgs a, const sgcn_fix_t* fix, int64_t nfix) {
+template <int G, int VW, class HT>
+__global__ __launch_bounds__(kBlock) void agg_fix_kernel(AggArgsT<HT> a, const sgcn_fix_t* fix, int64_t nfix) {
     typedef typename Vec<VW>::type VT;
     constexpr int GPB = kBlock / G;
     const int lig = threadIdx.x & (G - 1);
@@ -232,8 +302,8 @@ __global__ __launch_bounds__(kBlock) void agg_fix_kernel(AggArgs a, const sgcn_f
 }
 
 // second phase of the two-phase form: one group per output row, P-sum read back from accP_in
-template <int G, int VW>
-__global__ __launch_bounds__(kBlock) void agg_post_kernel(AggArgs a, int32_t n1) {
+template <int G, int VW, class HT>
+__global__ __launch_bounds__(kBlock) void agg_post_kernel(AggArgsT<HT> a, int32_t n1) {
     typedef typename Vec<VW>::type VT;
     constexpr int GPB = kBlock / G;
     const int lig = threadIdx.x & (G - 1);
@@ -247,13 +317,13 @@ __global__ __launch_bounds__(kBlock) void agg_post_kernel(AggArgs a, int32_t n1)
     agg_finish<G, VW>(a, uniform_i<G>((int)row), vi, lig, act, accP);
 }
 
-template <int VW>
-static int launch_agg_post(int G, const AggArgs& a, int32_t n1, hipStream_t st) {
+template <int VW, class HT>
+static int launch_agg_post(int G, const AggArgsT<HT>& a, int32_t n1, hipStream_t st) {
     const int nslab = (a.nvec + G - 1) / G;
 #define SGCN_AGGP_CASE(GG)                                                                               \
     case GG: {                                                                                           \
         const int64_t nrblk = ((int64_t)n1 + (kBlock / GG) - 1) / (kBlock / GG);                          \
-        hipLaunchKernelGGL((agg_post_kernel<GG, VW>), dim3((unsigned)(nrblk * nslab)), dim3(kBlock), 0, st, a, n1); \
+        hipLaunchKernelGGL((agg_post_kernel<GG, VW, HT>), dim3((unsigned)(nrblk * nslab)), dim3(kBlock), 0, st, a, n1); \
         break;                                                                                           \
     }
     switch (G) {
@@ -268,8 +338,8 @@ static int launch_agg_post(int G, const AggArgs& a, int32_t n1, hipStream_t st) 
     return SGCN_OK;
 }
 
-template <int VW>
-static int launch_agg(int G, const AggArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
+template <int VW, class HT>
+static int launch_agg(int G, const AggArgsT<HT>& a, const sgcn_plan_t* plan, hipStream_t st) {
     const int nslab = (a.nvec + G - 1) / G;
     SGCN_REQUIRE(a.pchunks >= 1 && a.pchunks <= agg_max_chunks(G, VW), "vr_aggregate: %d chunks of a P row, at most %d here",
                  a.pchunks, agg_max_chunks(G, VW));
@@ -277,11 +347,11 @@ static int launch_agg(int G, const AggArgs& a, const sgcn_plan_t* plan, hipStrea
     SGCN_REQUIRE(nblocks < (1ll << 31), "vr_aggregate: grid too large");
 #define SGCN_AGG_CASE(GG)                                                                          \
     case GG: {                                                                                     \
-        hipLaunchKernelGGL((agg_row_kernel<GG, VW, 16>), dim3((unsigned)nblocks), dim3(kBlock), 0,  \
+        hipLaunchKernelGGL((agg_row_kernel<GG, VW, 16, HT>), dim3((unsigned)nblocks), dim3(kBlock), 0,  \
                            st, a);                                                                 \
         if (plan && plan->nfix > 0) {                                                              \
             const int64_t nfblk = (plan->nfix + (kBlock / GG) - 1) / (kBlock / GG);               \
-            hipLaunchKernelGGL((agg_fix_kernel<GG, VW>), dim3((unsigned)(nfblk * nslab)),          \
+            hipLaunchKernelGGL((agg_fix_kernel<GG, VW, HT>), dim3((unsigned)(nfblk * nslab)),          \
                                dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);                 \
         }                                                                                          \
         break;                                                                                     \
@@ -411,6 +481,131 @@ extern "C" int sgcn_vr_aggregate_post_f32(const int32_t* a_rowptr, const int32_t
     a.ldw = ((int64_t)d + 3) / 4 * 4;
     a.accP_in = accP;
     int vw = pick_vw(d, {h, mu, Hbar, out_h, out_mu, accP}, {ldx, ldh, ldo, a.ldw});
+    if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
+    a.nvec = (d + vw - 1) / vw;
+    const int G = group_lanes(a.nvec);
+    hipStream_t st = (hipStream_t)stream;
+    if (vw == 4) return launch_agg_post<4>(G, a, n1, st);
+    if (vw == 2) return launch_agg_post<2>(G, a, n1, st);
+    return launch_agg_post<1>(G, a, n1, st);
+}
+
+// ---- the same three entry points on a bfloat16 history (--history_dtype bf16) ----------------------------------------
+// The table is N x ldh uint16 (ldh in ELEMENTS, a multiple of 8, base 16-byte aligned), read by 2 * VW-byte loads and
+// widened in registers; the kernels are the instantiations above with HT = uint16_t, so every sum is taken in the order
+// sgcn_vr_aggregate_f32 (resp. _pre_f32 + _post_f32) takes it on an fp32 table that holds the widened values.  A table of
+// that layout never limits the vector width, so VW, G and p_chunks are what the fp32 call picks for a 16-byte aligned fp32
+// table of the same element pitch (the table's pointer is left out of pick_vw, its pitch is not).
+static int h16_table_ok(const char* who, const uint16_t* Hbar, int64_t ldh, int32_t d) {
+    SGCN_REQUIRE(Hbar, "%s: null history", who);
+    SGCN_REQUIRE(ldh >= d && ldh % 8 == 0, "%s: a bfloat16 history needs ldh >= d and ldh %% 8 == 0 (ldh %lld, d %d)", who,
+                 (long long)ldh, d);
+    SGCN_REQUIRE(aligned16(Hbar), "%s: a bfloat16 history needs a 16-byte aligned base", who);
+    return SGCN_OK;
+}
+
+/* mirrors sgcn_vr_aggregate_f32 */
+extern "C" int sgcn_vr_aggregate_h16(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
+                                     const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
+                                     int32_t n0, int32_t nf, int32_t d, const float* h, const float* mu, int64_t ldx,
+                                     const uint16_t* Hbar, int64_t ldh, const int32_t* ifield, const int32_t* ffield,
+                                     const float* s, float* out_h, float* out_mu, int64_t ldo, int32_t cvd,
+                                     int32_t concat_self, const sgcn_plan_t* f_plan, void* stream) {
+    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && nf >= 0 && d >= 0, "vr_aggregate_h16: negative size");
+    if (int rc = h16_table_ok("vr_aggregate_h16", Hbar, ldh, d)) return rc;
+    if (n1 == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(a_rowptr && f_rowptr && h && ifield && out_h, "vr_aggregate_h16: null operand");
+    SGCN_REQUIRE(nf == 0 || ffield, "vr_aggregate_h16: null ffield");
+    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "vr_aggregate_h16: cvd needs mu, s, out_mu");
+    SGCN_REQUIRE(n1 <= n0 || !concat_self, "vr_aggregate_h16: concat_self needs n1 <= n0");
+    const int64_t width = concat_self ? 2 * (int64_t)d : d;
+    SGCN_REQUIRE(ldx >= d && ldo >= width, "vr_aggregate_h16: leading dimension too small");
+
+    AggArgsT<uint16_t> a{};
+    a.a_rowptr = a_rowptr; a.a_col = a_col; a.a_val = a_val;
+    a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
+    a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh;
+    a.ifield = ifield; a.ffield = ffield; a.s = s;
+    a.out_h = out_h; a.out_mu = out_mu; a.ldo = ldo;
+    a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
+    a.nseg = n1;
+    if (f_plan) {
+        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "vr_aggregate_h16: malformed plan");
+        a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg;
+        a.ws = f_plan->dev_ws; a.ldw = ((int64_t)d + 3) / 4 * 4;
+        if (f_plan->nfix > 0) {
+            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "vr_aggregate_h16: plan needs dev_fix/dev_ws");
+            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "vr_aggregate_h16: workspace too small");
+        }
+    }
+    int vw = pick_vw(d, {h, mu, out_h, out_mu, f_plan ? f_plan->dev_ws : nullptr}, {ldx, ldh, ldo});
+    if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
+    a.nvec = (d + vw - 1) / vw;
+    const int G = group_lanes(a.nvec);
+    a.pchunks = p_chunks(d, nullptr, ldh, f_plan ? f_plan->dev_ws : nullptr);
+    a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
+    hipStream_t st = (hipStream_t)stream;
+    if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
+    if (vw == 2) return launch_agg<2>(G, a, f_plan, st);
+    return launch_agg<1>(G, a, f_plan, st);
+}
+
+/* mirrors sgcn_vr_aggregate_pre_f32 */
+extern "C" int sgcn_vr_aggregate_pre_h16(const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
+                                         int32_t nf, int32_t d, const uint16_t* Hbar, int64_t ldh, const int32_t* ffield,
+                                         float* accP, const sgcn_plan_t* f_plan, void* stream) {
+    SGCN_REQUIRE(n1 >= 0 && nf >= 0 && d >= 0, "vr_aggregate_pre_h16: negative size");
+    if (int rc = h16_table_ok("vr_aggregate_pre_h16", Hbar, ldh, d)) return rc;
+    if (n1 == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(f_rowptr && accP, "vr_aggregate_pre_h16: bad operand");
+    SGCN_REQUIRE(nf == 0 || ffield, "vr_aggregate_pre_h16: null ffield");
+    AggArgsT<uint16_t> a{};
+    a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
+    a.H = Hbar; a.ldh = ldh; a.ffield = ffield; a.d = d;
+    a.ldw = ((int64_t)d + 3) / 4 * 4;
+    a.accP_out = accP;
+    a.nseg = n1;
+    if (f_plan) {
+        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "vr_aggregate_pre_h16: malformed plan");
+        a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg; a.ws = f_plan->dev_ws;
+        if (f_plan->nfix > 0) {
+            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "vr_aggregate_pre_h16: plan needs dev_fix/dev_ws");
+            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "vr_aggregate_pre_h16: workspace too small");
+        }
+    }
+    const int vw = pick_vw(d, {accP, f_plan ? f_plan->dev_ws : nullptr}, {ldh, a.ldw});
+    a.nvec = (d + vw - 1) / vw;
+    const int G = group_lanes(a.nvec);
+    a.pchunks = p_chunks(d, nullptr, ldh, f_plan ? f_plan->dev_ws : nullptr);
+    a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
+    hipStream_t st = (hipStream_t)stream;
+    if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
+    if (vw == 2) return launch_agg<2>(G, a, f_plan, st);
+    return launch_agg<1>(G, a, f_plan, st);
+}
+
+/* mirrors sgcn_vr_aggregate_post_f32 */
+extern "C" int sgcn_vr_aggregate_post_h16(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int32_t n1,
+                                          int32_t n0, int32_t d, const float* h, const float* mu, int64_t ldx,
+                                          const uint16_t* Hbar, int64_t ldh, const int32_t* ifield, const float* s,
+                                          float* out_h, float* out_mu, int64_t ldo, int32_t cvd, int32_t concat_self,
+                                          const float* accP, void* stream) {
+    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && d >= 0, "vr_aggregate_post_h16: negative size");
+    if (int rc = h16_table_ok("vr_aggregate_post_h16", Hbar, ldh, d)) return rc;
+    if (n1 == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(a_rowptr && h && ifield && out_h && accP, "vr_aggregate_post_h16: null operand");
+    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "vr_aggregate_post_h16: cvd needs mu, s, out_mu");
+    SGCN_REQUIRE(n1 <= n0 || !concat_self, "vr_aggregate_post_h16: concat_self needs n1 <= n0");
+    const int64_t width = concat_self ? 2 * (int64_t)d : d;
+    SGCN_REQUIRE(ldx >= d && ldo >= width, "vr_aggregate_post_h16: leading dimension too small");
+    AggArgsT<uint16_t> a{};
+    a.a_rowptr = a_rowptr; a.a_col = a_col; a.a_val = a_val;
+    a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh; a.ifield = ifield; a.s = s;
+    a.out_h = out_h; a.out_mu = out_mu; a.ldo = ldo;
+    a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
+    a.ldw = ((int64_t)d + 3) / 4 * 4;
+    a.accP_in = accP;
+    int vw = pick_vw(d, {h, mu, out_h, out_mu, accP}, {ldx, ldh, ldo, a.ldw});
     if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);

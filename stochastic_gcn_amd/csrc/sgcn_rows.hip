@@ -54,6 +54,88 @@ static int launch_rows(const float* in, int64_t ldi, const int32_t* r, int32_t n
     return SGCN_OK;
 }
 
+// ---- rows of a bfloat16 history (--history_dtype bf16): N x ldh uint16, ldh % 8 == 0, base 16-byte aligned -----------
+// store: round-to-nearest-even of the fp32 bits (+-0, +-inf kept, subnormals rounded, overflow to inf; a NaN stays a NaN);
+// load: bits << 16.  Integer arithmetic only, so the result does not depend on the float mode of the wavefront.
+__device__ __forceinline__ uint16_t bf16_round(float x) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);       // NaN: quiet, sign kept
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+// SCATTER: H[r[i], :] = round(src[i, :]) with r[i] < 0 skipped; else out[i, :] = widen(H[r[i], :]).  r == nullptr: rows
+// 0 .. n-1 in place.  VW is what the fp32 side allows (the table's layout never limits it): VW fp32 elements move as one
+// 4 * VW-byte vector, VW table elements as one 2 * VW-byte vector.
+template <int VW, bool SCATTER>
+__global__ __launch_bounds__(kBlock) void rows_h16_kernel(uint16_t* __restrict__ H, int64_t ldh, const int32_t* __restrict__ r,
+                                                          int32_t n, int32_t d, int32_t nvec, int32_t G, float* __restrict__ x,
+                                                          int64_t ldx) {
+    typedef typename Vec<VW>::type VT;
+    const int gpb = kBlock / G;
+    const int lig = threadIdx.x % G;
+    const int64_t i = (int64_t)blockIdx.x * gpb + threadIdx.x / G;
+    if (i >= n) return;
+    const int64_t ri = r ? (int64_t)r[i] : i;
+    if (SCATTER && ri < 0) return;          // negative row id: padding slot, nothing to write
+    uint16_t* hrow = H + ri * ldh;
+    float* xrow = x + i * ldx;
+    for (int vi = lig; vi < nvec; vi += G) {
+        const int64_t c0 = (int64_t)vi * VW;
+        const int left = d - vi * VW;
+        if (left >= VW) {
+            if constexpr (VW == 1) {
+                if (SCATTER) hrow[c0] = bf16_round(xrow[c0]);
+                else xrow[c0] = __uint_as_float((uint32_t)hrow[c0] << 16);
+            } else {
+                typedef uint16_t BT __attribute__((ext_vector_type(VW)));
+                if (SCATTER) {
+                    const VT v = vload<VW>(xrow + c0);
+                    BT b;
+#pragma unroll
+                    for (int e = 0; e < VW; e++) b[e] = bf16_round(v[e]);
+                    *reinterpret_cast<BT*>(hrow + c0) = b;
+                } else {
+                    const BT b = *reinterpret_cast<const BT*>(hrow + c0);
+                    VT v;
+#pragma unroll
+                    for (int e = 0; e < VW; e++) v[e] = __uint_as_float((uint32_t)b[e] << 16);
+                    vstore<VW>(xrow + c0, v);
+                }
+            }
+        } else {
+            for (int e = 0; e < left; e++) {
+                if (SCATTER) hrow[c0 + e] = bf16_round(xrow[c0 + e]);
+                else xrow[c0 + e] = __uint_as_float((uint32_t)hrow[c0 + e] << 16);
+            }
+        }
+    }
+}
+
+template <bool SCATTER>
+static int launch_rows_h16(uint16_t* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, float* x, int64_t ldx,
+                           hipStream_t st) {
+    int vw = 1;
+    if (ldx % 4 == 0 && aligned16(x)) vw = 4;
+    else if (ldx % 2 == 0 && aligned8(x)) vw = 2;
+    const int nvec = (d + vw - 1) / vw;
+    const int G = group_lanes(nvec);
+    const int64_t blocks = ((int64_t)n + (kBlock / G) - 1) / (kBlock / G);
+    dim3 grid((unsigned)blocks), block(kBlock);
+    if (vw == 4) hipLaunchKernelGGL((rows_h16_kernel<4, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
+    else if (vw == 2) hipLaunchKernelGGL((rows_h16_kernel<2, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
+    else hipLaunchKernelGGL((rows_h16_kernel<1, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
+    SGCN_HIP_TRY(hipGetLastError());
+    return SGCN_OK;
+}
+
+static int h16_table_ok(const char* who, const uint16_t* H, int64_t ldh, int32_t d) {
+    SGCN_REQUIRE(H, "%s: null history", who);
+    SGCN_REQUIRE(ldh >= d && ldh % 8 == 0, "%s: a bfloat16 history needs ldh >= d and ldh %% 8 == 0 (ldh %lld, d %d)", who,
+                 (long long)ldh, d);
+    SGCN_REQUIRE(aligned16(H), "%s: a bfloat16 history needs a 16-byte aligned base", who);
+    return SGCN_OK;
+}
+
 // One wavefront per output row: copies values and column ids, optionally writes COO row ids.
 __global__ __launch_bounds__(kBlock) void csr_slice_kernel(int32_t n, const int32_t* __restrict__ r,
                                                            const float* __restrict__ a_d,
@@ -264,6 +346,26 @@ extern "C" int sgcn_scatter_rows_f32(float* H, int64_t ldh, const int32_t* r, in
     return launch_rows<true>(src, lds, r, n, d, H, ldh, (hipStream_t)stream);
 }
 
+/* mirrors sgcn_gather_rows_f32: out[i, :] = widen(H[r[i], :]); r == NULL: rows 0 .. n-1 */
+extern "C" int sgcn_gather_rows_h16(const uint16_t* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, float* out,
+                                    int64_t ldo, void* stream) {
+    SGCN_REQUIRE(n >= 0 && d >= 0, "gather_rows_h16: negative size");
+    if (int rc = h16_table_ok("gather_rows_h16", H, ldh, d)) return rc;
+    if (n == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(out && ldo >= d, "gather_rows_h16: bad operand");
+    return launch_rows_h16<false>(const_cast<uint16_t*>(H), ldh, r, n, d, out, ldo, (hipStream_t)stream);
+}
+
+/* mirrors sgcn_scatter_rows_f32: H[r[i], :] = round(src[i, :]), r[i] < 0 skipped; r == NULL: rows 0 .. n-1 */
+extern "C" int sgcn_scatter_rows_h16(uint16_t* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, const float* src,
+                                     int64_t lds, void* stream) {
+    SGCN_REQUIRE(n >= 0 && d >= 0, "scatter_rows_h16: negative size");
+    if (int rc = h16_table_ok("scatter_rows_h16", H, ldh, d)) return rc;
+    if (n == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(src && lds >= d, "scatter_rows_h16: bad operand");
+    return launch_rows_h16<true>(H, ldh, r, n, d, const_cast<float*>(src), lds, (hipStream_t)stream);
+}
+
 // ---- the multi-GPU history exchange (policy H-a) as two launches around one all-gather ---------------------
 // pack : send = [cap ids | cap x d row bits] of this rank's update -- ids[0..n) and their rows, ids[n..cap) = -1
 // apply: every rank's block of the gathered buffer scattered into the local replica, in RANK ORDER (a vertex that two
@@ -339,6 +441,49 @@ extern "C" int sgcn_hist_apply_f32(float* H, int64_t ldh, const int32_t* recv, i
     for (int32_t r = 0; r < world; r++) {
         const int32_t* blk = recv + r * per;
         const int rc = launch_rows<true>(reinterpret_cast<const float*>(blk + cap), d, blk, cap, d, H, ldh, (hipStream_t)stream);
+        if (rc != SGCN_OK) return rc;
+    }
+    return SGCN_OK;
+}
+
+// the owners' copy of sgcn_hist_apply_f32 into a bfloat16 table: the fp32 payload row is rounded on the way in
+__global__ __launch_bounds__(kBlock) void hist_write_h16_kernel(uint16_t* __restrict__ H, int64_t ldh, const int32_t* __restrict__ recv,
+                                                                int32_t world, int32_t cap, int32_t d, int64_t per,
+                                                                int32_t* __restrict__ owner) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t k = (int64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    if (k >= (int64_t)world * cap) return;
+    const int32_t r = (int32_t)(k / cap), i = (int32_t)(k % cap);
+    const int32_t id = recv[r * per + i];
+    if (id < 0 || owner[id] != (int32_t)k + 1) return;
+    const float* src = reinterpret_cast<const float*>(recv + r * per + cap) + (int64_t)i * d;
+    uint16_t* dst = H + (int64_t)id * ldh;
+    for (int c = lane; c < d; c += kWave) dst[c] = bf16_round(src[c]);
+    if (lane == 0) owner[id] = 0;                     // (only the owner of a vertex touches its word in this launch)
+}
+
+/* mirrors sgcn_hist_apply_f32: the payload is what sgcn_hist_pack_f32 makes (fp32 row bits), the table bfloat16 -- every
+ * replica rounds the same fp32 rows, so the replicas stay bit-identical */
+extern "C" int sgcn_hist_apply_h16(uint16_t* H, int64_t ldh, const int32_t* recv, int32_t world, int32_t cap, int32_t d,
+                                   int32_t* owner, void* stream) {
+    SGCN_REQUIRE(world >= 1 && cap >= 0 && d >= 0, "hist_apply_h16: bad size");
+    if (int rc = h16_table_ok("hist_apply_h16", H, ldh, d)) return rc;
+    if (cap == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(recv, "hist_apply_h16: bad operand");
+    const int64_t per = (int64_t)cap * (d + 1);
+    if (owner && world > 2) {
+        const int64_t n = (int64_t)world * cap;
+        hipLaunchKernelGGL(hist_claim_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                           recv, world, cap, per, owner);
+        hipLaunchKernelGGL(hist_write_h16_kernel, dim3((unsigned)((n + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0,
+                           (hipStream_t)stream, H, ldh, recv, world, cap, d, per, owner);
+        SGCN_HIP_TRY(hipGetLastError());
+        return SGCN_OK;
+    }
+    for (int32_t r = 0; r < world; r++) {
+        const int32_t* blk = recv + r * per;
+        float* rows = const_cast<float*>(reinterpret_cast<const float*>(blk + cap));
+        const int rc = launch_rows_h16<true>(H, ldh, blk, cap, d, rows, d, (hipStream_t)stream);
         if (rc != SGCN_OK) return rc;
     }
     return SGCN_OK;

@@ -359,14 +359,16 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
         sgcn_plan_t pl;
         // weight-gradient work forked onto the auxiliary stream (DENSE_BWD) is joined before anything that
         // reads or writes gradients outside the backward chain
-        if (op.op == SGCN_OP_ADAM || op.op == SGCN_OP_L2_PENALTY || op.op == SGCN_OP_SCATTER_ROWS ||
-            op.op == SGCN_OP_MEMSET0 || op.op == SGCN_OP_VR_AGG_POST || (op.op == SGCN_OP_DENSE_BWD && memset_on_aux)) {
+        if (op.op == SGCN_OP_ADAM || op.op == SGCN_OP_L2_PENALTY || op.op == SGCN_OP_SCATTER_ROWS || op.op == SGCN_OP_SCATTER_ROWS_H16 ||
+            op.op == SGCN_OP_MEMSET0 || op.op == SGCN_OP_VR_AGG_POST || op.op == SGCN_OP_VR_AGG_POST_H16 ||
+            (op.op == SGCN_OP_DENSE_BWD && memset_on_aux)) {
             rc = sgcn::aux_join(stream);
             if (rc != SGCN_OK) return rc;
             memset_on_aux = false;
         }
         void* side = stream;                 // where an AUX_* / *_PRE op runs
-        if (overlap && (op.op == SGCN_OP_VR_AGG_PRE || op.op == SGCN_OP_AUX_SCATTER_ROWS || op.op == SGCN_OP_AUX_MEMSET0)) {
+        if (overlap && (op.op == SGCN_OP_VR_AGG_PRE || op.op == SGCN_OP_AUX_SCATTER_ROWS || op.op == SGCN_OP_AUX_MEMSET0 ||
+                        op.op == SGCN_OP_VR_AGG_PRE_H16 || op.op == SGCN_OP_AUX_SCATTER_ROWS_H16)) {
             rc = sgcn::aux_fork(stream, &side);
             if (rc != SGCN_OK) return rc;
         }
@@ -778,6 +780,61 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
             const int32_t cvd = a.i(), concat = a.i();
             const float* accP = a.p<const float>();
             rc = sgcn_vr_aggregate_post_f32(arp, ac, av, n1, n0, d, h, mu, ldx, H, ldh, ifi, s, oh, om, ldo, cvd, concat, accP, stream);
+            break;
+        }
+        // ---- the same ops on a bfloat16 history (argument lists as above, the table's leading dimension in elements) ----
+        case SGCN_OP_VR_AGG_H16: {
+            const int32_t* arp = a.p<const int32_t>(); const int32_t* ac = a.p<const int32_t>(); const float* av = a.p<const float>();
+            const int32_t* frp = a.p<const int32_t>(); const int32_t* fc = a.p<const int32_t>(); const float* fv = a.p<const float>();
+            const int32_t n1 = a.i(), n0 = a.i(), nf = a.i(), d = a.i();
+            const float* h = a.p<const float>(); const float* mu = a.p<const float>(); const int64_t ldx = a.next();
+            const uint16_t* H = a.p<const uint16_t>(); const int64_t ldh = a.next();
+            const int32_t* ifi = a.p<const int32_t>(); const int32_t* ffi = a.p<const int32_t>();
+            const float* s = a.p<const float>();
+            float* oh = a.p<float>(); float* om = a.p<float>(); const int64_t ldo = a.next();
+            const int32_t cvd = a.i(), concat = a.i();
+            const sgcn_plan_t* p = a.plan(&pl);
+            rc = sgcn_vr_aggregate_h16(arp, ac, av, frp, fc, fv, n1, n0, nf, d, h, mu, ldx, H, ldh, ifi, ffi, s, oh, om, ldo,
+                                       cvd, concat, p, stream);
+            break;
+        }
+        case SGCN_OP_VR_AGG_PRE_H16: {
+            const int32_t* frp = a.p<const int32_t>(); const int32_t* fc = a.p<const int32_t>(); const float* fv = a.p<const float>();
+            const int32_t n1 = a.i(), nf = a.i(), d = a.i();
+            const uint16_t* H = a.p<const uint16_t>(); const int64_t ldh = a.next();
+            const int32_t* ffi = a.p<const int32_t>();
+            float* accP = a.p<float>();
+            const sgcn_plan_t* p = a.plan(&pl);
+            rc = sgcn_vr_aggregate_pre_h16(frp, fc, fv, n1, nf, d, H, ldh, ffi, accP, p, side);
+            break;
+        }
+        case SGCN_OP_VR_AGG_POST_H16: {
+            const int32_t* arp = a.p<const int32_t>(); const int32_t* ac = a.p<const int32_t>(); const float* av = a.p<const float>();
+            const int32_t n1 = a.i(), n0 = a.i(), d = a.i();
+            const float* h = a.p<const float>(); const float* mu = a.p<const float>(); const int64_t ldx = a.next();
+            const uint16_t* H = a.p<const uint16_t>(); const int64_t ldh = a.next();
+            const int32_t* ifi = a.p<const int32_t>(); const float* s = a.p<const float>();
+            float* oh = a.p<float>(); float* om = a.p<float>(); const int64_t ldo = a.next();
+            const int32_t cvd = a.i(), concat = a.i();
+            const float* accP = a.p<const float>();
+            rc = sgcn_vr_aggregate_post_h16(arp, ac, av, n1, n0, d, h, mu, ldx, H, ldh, ifi, s, oh, om, ldo, cvd, concat, accP, stream);
+            break;
+        }
+        case SGCN_OP_SCATTER_ROWS_H16:
+        case SGCN_OP_AUX_SCATTER_ROWS_H16: {
+            uint16_t* H = a.p<uint16_t>(); const int64_t ldh = a.next();
+            const int32_t* r = a.p<const int32_t>(); const int32_t n = a.i(), d = a.i();
+            const float* src = a.p<const float>(); const int64_t lds = a.next();
+            rc = sgcn_scatter_rows_h16(H, ldh, r, n, d, src, lds, side);
+            break;
+        }
+        case SGCN_OP_HIST_APPLY_H16: {
+            uint16_t* H = a.p<uint16_t>(); const int64_t ldh = a.next();
+            const int32_t* recv = a.p<const int32_t>(); const int32_t world = a.i(), cap = a.i(), d = a.i();
+            int32_t* owner = a.p<int32_t>();
+            const int64_t where = a.next();
+            if (where != 0) { rc = where == 2 ? xchg_fork(stream, &side) : sgcn::aux_fork(stream, &side); if (rc != SGCN_OK) break; }
+            rc = sgcn_hist_apply_h16(H, ldh, recv, world, cap, d, owner, side);
             break;
         }
         case SGCN_OP_GATHER_ROWS: {

@@ -286,7 +286,8 @@ class Model(object):
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         blob = {"var/" + n: v.detach().cpu().numpy() for n, v in self.named_vars()}
         for i, h in enumerate(self.history_vars):
-            blob["history/%d" % i] = h.detach().cpu().numpy()
+            # (a bfloat16 history is stored WIDENED -- exact --, so fp32 and bf16 runs read each other's checkpoints)
+            blob["history/%d" % i] = (h if h.dtype == torch.float32 else ops.history_widen(h)).detach().cpu().numpy()
         np.savez(path, **blob)
         print("Model saved in file: %s" % path)
         return path
@@ -299,7 +300,11 @@ class Model(object):
         if load_history:
             self.join_history()
             for i, h in enumerate(self.history_vars):
-                h.copy_(torch.from_numpy(z["history/%d" % i]).to(self.device))
+                src = torch.from_numpy(z["history/%d" % i]).to(self.device)
+                if h.dtype == torch.float32:
+                    h.copy_(src)
+                else:                      # rounded to nearest even by the library (sgcn_scatter_rows_h16)
+                    ops.history_assign(h, src)
         print("Model restored from file: %s" % path)
 
 

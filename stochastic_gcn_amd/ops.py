@@ -71,6 +71,17 @@ def _rows2d(t, name):
     return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
 
 
+def _hist2d(t, name):
+    """(ptr, ld, bf16?) of a history table: fp32, or bfloat16 (--history_dtype bf16; ld in elements, the layout
+    include/sgcn.h asks for is checked by the library)."""
+    if t.dtype == torch.float32:
+        return _rows2d(t, name) + (False,)
+    _dev(t, torch.bfloat16, name)
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("%s must be 2-D with unit column stride" % name)
+    return t.data_ptr(), t.stride(0), True
+
+
 class DevArray(object):
     """A typed window ``base[off : off + n]`` of a 1-D device buffer that is NOT a tensor: the ops
     only need its address and length, and a torch slice costs ~2.5 us of host time -- a packed
@@ -204,7 +215,7 @@ def spmm(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=None, 
 
 
 def vr_aggregate(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_self, out_h=None, out_mu=None):
-    """Fused control-variate aggregator forward (sgcn_vr_aggregate_f32)."""
+    """Fused control-variate aggregator forward (sgcn_vr_aggregate_f32; sgcn_vr_aggregate_h16 on a bfloat16 history)."""
     n1, n0 = A.shape
     nf = P.shape[1]
     hptr, ldx = _rows2d(h, "h")
@@ -216,7 +227,7 @@ def vr_aggregate(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_self, out_h=N
             raise ValueError("h and mu must share shape and row pitch")
     else:
         mptr = None
-    Hptr, ldh = _rows2d(Hbar, "Hbar")
+    Hptr, ldh, h16 = _hist2d(Hbar, "Hbar")
     if out_h is None:
         out_h = torch.empty((n1, width), dtype=torch.float32, device=h.device)
     if cvd and out_mu is None:
@@ -228,7 +239,7 @@ def vr_aggregate(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_self, out_h=N
         if ldo2 != ldo:
             raise ValueError("out_h and out_mu must share row pitch")
     plan = P.plan.struct(d) if P.plan is not None else None
-    check(lib.sgcn_vr_aggregate_f32(
+    check((lib.sgcn_vr_aggregate_h16 if h16 else lib.sgcn_vr_aggregate_f32)(
         A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), P.rowptr.data_ptr(), _ptr(P.col),
         _ptr(P.val), n1, n0, nf, d, hptr, mptr, ldx, Hptr, ldh,
         _ptr(_dev(ifield, torch.int32, "ifield")), _ptr(_dev(ffield, torch.int32, "ffield")),
@@ -245,16 +256,16 @@ def vr_aggregate_two_phase(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_sel
     hptr, ldx = _rows2d(h, "h")
     d = int(h.shape[1])
     width = 2 * d if concat_self else d
-    Hptr, ldh = _rows2d(Hbar, "Hbar")
+    Hptr, ldh, h16 = _hist2d(Hbar, "Hbar")
     ldw = (d + 3) // 4 * 4
     accP = torch.empty((n1, ldw), dtype=torch.float32, device=h.device)
     plan = P.plan.struct(d) if P.plan is not None else None
-    check(lib.sgcn_vr_aggregate_pre_f32(P.rowptr.data_ptr(), _ptr(P.col), _ptr(P.val), n1, nf, d, Hptr, ldh,
+    check((lib.sgcn_vr_aggregate_pre_h16 if h16 else lib.sgcn_vr_aggregate_pre_f32)(P.rowptr.data_ptr(), _ptr(P.col), _ptr(P.val), n1, nf, d, Hptr, ldh,
                                         _ptr(_dev(ffield, torch.int32, "ffield")), accP.data_ptr(),
                                         C.byref(plan) if plan is not None else None, _stream()))
     out_h = torch.empty((n1, width), dtype=torch.float32, device=h.device)
     out_mu = torch.empty((n1, width), dtype=torch.float32, device=h.device) if cvd else None
-    check(lib.sgcn_vr_aggregate_post_f32(A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), n1, n0, d, hptr,
+    check((lib.sgcn_vr_aggregate_post_h16 if h16 else lib.sgcn_vr_aggregate_post_f32)(A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), n1, n0, d, hptr,
                                          _rows2d(mu, "mu")[0] if cvd else None, ldx, Hptr, ldh,
                                          _ptr(_dev(ifield, torch.int32, "ifield")), _ptr(_dev(s, torch.float32, "s")),
                                          out_h.data_ptr(), _ptr(out_mu), width, int(bool(cvd)), int(bool(concat_self)),
@@ -263,27 +274,58 @@ def vr_aggregate_two_phase(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_sel
 
 
 def gather_rows(inp, idx, out=None, d=None):
-    """out[i, :d] = inp[idx[i], :d]   (sgcn_gather_rows_f32)."""
-    iptr, ldi = _rows2d(inp, "inp")
+    """out[i, :d] = inp[idx[i], :d]   (sgcn_gather_rows_f32).  A bfloat16 ``inp`` (a history table) is widened on the way
+    out (sgcn_gather_rows_h16); there ``idx=None`` reads rows 0 .. n-1."""
+    iptr, ldi, h16 = _hist2d(inp, "inp")
+    if idx is None and not h16:
+        raise TypeError("gather_rows: idx=None is for a bfloat16 table")
     _dev(idx, torch.int32, "idx")
-    n = int(idx.shape[0])
+    n = int(inp.shape[0] if idx is None else idx.shape[0])
     d = int(inp.shape[1] if d is None else d)
     if out is None:
         out = torch.empty((n, d), dtype=torch.float32, device=inp.device)
     optr, ldo = _rows2d(out, "out")
-    check(lib.sgcn_gather_rows_f32(iptr, ldi, idx.data_ptr(), n, d, optr, ldo, _stream()))
+    check((lib.sgcn_gather_rows_h16 if h16 else lib.sgcn_gather_rows_f32)(iptr, ldi, _ptr(idx), n, d, optr, ldo, _stream()))
     return out
 
 
 def scatter_rows(H, idx, src, d=None):
-    """H[idx[i], :d] = src[i, :d]  (idx unique)   (sgcn_scatter_rows_f32)."""
-    hptr, ldh = _rows2d(H, "H")
+    """H[idx[i], :d] = src[i, :d]  (idx unique)   (sgcn_scatter_rows_f32).  A bfloat16 ``H`` (a history table) takes the
+    fp32 rows rounded to nearest even (sgcn_scatter_rows_h16); there ``idx=None`` writes rows 0 .. n-1."""
+    hptr, ldh, h16 = _hist2d(H, "H")
+    if idx is None and not h16:
+        raise TypeError("scatter_rows: idx=None is for a bfloat16 table")
     sptr, lds = _rows2d(src, "src")
     _dev(idx, torch.int32, "idx")
-    n = int(idx.shape[0])
+    n = int(src.shape[0] if idx is None else idx.shape[0])
     d = int(src.shape[1] if d is None else d)
-    check(lib.sgcn_scatter_rows_f32(hptr, ldh, idx.data_ptr(), n, d, sptr, lds, _stream()))
+    check((lib.sgcn_scatter_rows_h16 if h16 else lib.sgcn_scatter_rows_f32)(hptr, ldh, _ptr(idx), n, d, sptr, lds, _stream()))
     return H
+
+
+def history_alloc(n, d, device, bf16=False):
+    """A zeroed ``n x d`` history table.  bfloat16: ``n x pitch`` with pitch = 8 * ceil(d / 8) elements, handed out as its
+    ``[:, :d]`` view -- the layout the *_h16 entry points require; the pad columns stay zero."""
+    if not bf16:
+        return torch.zeros((n, d), dtype=torch.float32, device=device)
+    return torch.zeros((n, (d + 7) // 8 * 8), dtype=torch.bfloat16, device=device)[:, :d]
+
+
+def history_widen(H, out=None):
+    """The whole table as fp32 (a copy): exact for a bfloat16 table."""
+    if H.dtype == torch.float32:
+        return H.clone() if out is None else out.copy_(H)
+    return gather_rows(H, None, out=out)
+
+
+def history_assign(H, src):
+    """H[:, :] = src (fp32, same shape), rounded when H is bfloat16."""
+    if H.dtype == torch.float32:
+        H.copy_(src)
+        return H
+    if src.shape[0] > 1 and (src.stride(1) != 1):
+        src = src.contiguous()
+    return scatter_rows(H, None, src)
 
 
 def csr_slice(A, rows_host, rows_dev=None, with_coo_rows=False):

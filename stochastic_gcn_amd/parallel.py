@@ -306,8 +306,10 @@ class DataParallel(object):
         owner = self._hist_bufs.get(okey)
         if owner is None:
             owner = self._hist_bufs[okey] = torch.zeros(int(history.shape[0]), dtype=torch.int32, device=dev)
-        check(lib.sgcn_hist_apply_f32(history.data_ptr(), int(history.stride(0)), recv.data_ptr(), self.world, cap, d,
-                                      owner.data_ptr(), st))
+        # (the payload is fp32 row bits whatever the table holds: a bfloat16 replica rounds the rows it receives, the same
+        # rows on every rank, so the replicas stay bit-identical)
+        apply = lib.sgcn_hist_apply_h16 if history.dtype == torch.bfloat16 else lib.sgcn_hist_apply_f32
+        check(apply(history.data_ptr(), int(history.stride(0)), recv.data_ptr(), self.world, cap, d, owner.data_ptr(), st))
 
     def join_history(self):
         """Wait for the history exchanges in flight and apply them (rank order, issue order).  On RCCL the wait is a

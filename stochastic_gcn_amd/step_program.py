@@ -33,7 +33,10 @@ OP = dict(DENSE_FWD=1, DENSE_BWD=2, VR_AGG=3, SPMM=4, SOFTMAX_CE=5, ADAM=6, SCAT
           ALLREDUCE_AVG=29, HIST_PACK=30, ALLGATHER_I32=31, HIST_APPLY=32,
           # the --det_dropout stacks (ABI v16)
           GEMM=33, DET_PRE=34, DET_PRE_BWD=35, SQUARE=36, ADDMUL=37, DET_LNVAR_FWD=38, DET_LNVAR_BWD=39, DET_RELU_FWD=40,
-          DET_RELU_BWD=41, GAUSS=42, GAUSS_BWD=43, DET_AGG_PREP=44, DET_AGG_PREP_BWD=45, RELU_EPS=46, GATE=47)
+          DET_RELU_BWD=41, GAUSS=42, GAUSS_BWD=43, DET_AGG_PREP=44, DET_AGG_PREP_BWD=45, RELU_EPS=46, GATE=47,
+          # the same ops on a bfloat16 history (--history_dtype bf16): argument lists as their fp32 forms
+          VR_AGG_H16=48, VR_AGG_PRE_H16=49, VR_AGG_POST_H16=50, SCATTER_ROWS_H16=51, AUX_SCATTER_ROWS_H16=52,
+          HIST_APPLY_H16=53)
 MAX_ARGS = 48
 GEMM_WS_BOUND = 256 * 32 * 128 + 64    # sgcn_gemm_ws_floats(M, N, K) = S * M * N with S <= 256 / (tiles of 32 x 128): never above this
 ARENA_LIMIT_BYTES = 2 << 30
@@ -261,6 +264,11 @@ class StepProgram(object):
             raise Unsupported("too many arguments")
         self._cur.append((OP[op], list(args)))
 
+    @staticmethod
+    def _hop(op, hist):
+        """the op that touches history table `hist`: its *_H16 form for a bfloat16 table"""
+        return op + '_H16' if hist.dtype == torch.bfloat16 else op
+
     def _p(self, t):
         return NULL if t is None else (t.ptr if isinstance(t, ST) else t)
 
@@ -421,7 +429,7 @@ class StepProgram(object):
         self._emit('HIST_PACK', [self._field_ptr(l), self.rows[l].op(), self._p(nh), K(nh.ld), K(d), K(cap), send, K(aux)])
         self._emit('ALLGATHER_I32', [send, recv, K(cap * (d + 1)), K(aux)])
         owner = self._owner_words(hist)
-        self._emit('HIST_APPLY', [K(hist.data_ptr()), K(hist.stride(0)), recv, K(self.native_world), K(cap), K(d),
+        self._emit(self._hop('HIST_APPLY', hist), [K(hist.data_ptr()), K(hist.stride(0)), recv, K(self.native_world), K(cap), K(d),
                                   K(owner.data_ptr()), K(aux)])
 
     def _sparse_dropout(self, xs, site):
@@ -548,7 +556,7 @@ class StepProgram(object):
                 d = int(hist.shape[1])
                 ldw = (d + 3) // 4 * 4
                 buf = self._alloc(self.rows[l + 1], ldw)
-                self._emit('VR_AGG_PRE', [self._ip(bf + 3), self._ip(bf + 4), self._fp(bf + 5), self.rows[l + 1].op(), self._n(bf + 1),
+                self._emit(self._hop('VR_AGG_PRE', hist), [self._ip(bf + 3), self._ip(bf + 4), self._fp(bf + 5), self.rows[l + 1].op(), self._n(bf + 1),
                                           K(d), K(hist.data_ptr()), K(int(hist.stride(0))), self._ip(self._pb.o_ffields + 2 * l),
                                           self._p(buf)] + self._plan(bf, d))
                 accP[l] = buf
@@ -731,16 +739,16 @@ class StepProgram(object):
                     if d != int(hist.shape[1]):
                         raise Unsupported("aggregator width differs from its history")
                     if two_phase:
-                        self._emit('VR_AGG_POST', [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), n1.op(), self.rows[l].op(), K(d),
+                        self._emit(self._hop('VR_AGG_POST', hist), [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), n1.op(), self.rows[l].op(), K(d),
                                                    self._p(h), self._p(mu), K(h.ld), self._p(H), K(H.ld), self._field_ptr(l), sptr,
                                                    self._p(out_h), self._p(out_mu), K(width), K(1), K(int(concat)), self._p(accP[l])])
                     else:
-                        self._emit('VR_AGG', [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), self._ip(bf + 3), self._ip(bf + 4),
+                        self._emit(self._hop('VR_AGG', hist), [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), self._ip(bf + 3), self._ip(bf + 4),
                                               self._fp(bf + 5), n1.op(), self.rows[l].op(), self._n(bf + 1), K(d), self._p(h), self._p(mu),
                                               K(h.ld), self._p(H), K(H.ld), self._field_ptr(l), self._ip(self._pb.o_ffields + 2 * l), sptr,
                                               self._p(out_h), self._p(out_mu), K(width), K(1), K(int(concat))] + self._plan(bf, d))
                     if local_hist and not self._hist_last:
-                        self._emit('AUX_SCATTER_ROWS', [K(hist.data_ptr()), K(hist.stride(0)), self._field_ptr(l), self.rows[l].op(),
+                        self._emit(self._hop('AUX_SCATTER_ROWS', hist), [K(hist.data_ptr()), K(hist.stride(0)), self._field_ptr(l), self.rows[l].op(),
                                                         K(mu.cols), self._p(mu), K(mu.ld)])
                     self.new_history[l] = mu
                     if self.exchange_overlap:
@@ -756,16 +764,16 @@ class StepProgram(object):
                     if d != int(hist.shape[1]):
                         raise Unsupported("aggregator width differs from its history")
                     if two_phase:
-                        self._emit('VR_AGG_POST', [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), n1.op(), self.rows[l].op(), K(d),
+                        self._emit(self._hop('VR_AGG_POST', hist), [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), n1.op(), self.rows[l].op(), K(d),
                                                    self._p(x), NULL, K(x.ld), self._p(H), K(H.ld), self._field_ptr(l), NULL,
                                                    self._p(out_h), NULL, K(width), K(0), K(int(concat)), self._p(accP[l])])
                     else:
-                        self._emit('VR_AGG', [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), self._ip(bf + 3), self._ip(bf + 4),
+                        self._emit(self._hop('VR_AGG', hist), [self._ip(ba + 3), self._ip(ba + 4), self._fp(ba + 5), self._ip(bf + 3), self._ip(bf + 4),
                                               self._fp(bf + 5), n1.op(), self.rows[l].op(), self._n(bf + 1), K(d), self._p(x), NULL,
                                               K(x.ld), self._p(H), K(H.ld), self._field_ptr(l), self._ip(self._pb.o_ffields + 2 * l), NULL,
                                               self._p(out_h), NULL, K(width), K(0), K(int(concat))] + self._plan(bf, d))
                     if local_hist and not self._hist_last:
-                        self._emit('AUX_SCATTER_ROWS', [K(hist.data_ptr()), K(hist.stride(0)), self._field_ptr(l), self.rows[l].op(),
+                        self._emit(self._hop('AUX_SCATTER_ROWS', hist), [K(hist.data_ptr()), K(hist.stride(0)), self._field_ptr(l), self.rows[l].op(),
                                                         K(x.cols), self._p(x), K(x.ld)])
                     self.new_history[l] = x
                     if self.exchange_overlap:
@@ -948,7 +956,7 @@ class StepProgram(object):
                 continue
             # (a det-dropout aggregator updates a mean AND a variance history: models.update_history's zip)
             for hist, src in zip(m.history[l], nh if isinstance(nh, list) else [nh]):
-                self._emit('SCATTER_ROWS', [K(hist.data_ptr()), K(hist.stride(0)), self._field_ptr(l), self.rows[l].op(),
+                self._emit(self._hop('SCATTER_ROWS', hist), [K(hist.data_ptr()), K(hist.stride(0)), self._field_ptr(l), self.rows[l].op(),
                                             K(src.cols), self._p(src), K(src.ld)])
 
     # ---- build the ctypes program ------------------------------------------------------------------

@@ -24,7 +24,7 @@ import scipy.sparse as sp
 import torch
 
 from . import ops
-from .flags import FLAGS
+from .flags import FLAGS, check_history_dtype
 from .models import make_template
 from .parallel import DataParallel
 from .plaingcn import PlainGCN
@@ -266,6 +266,7 @@ class Trainer(object):
         torch.manual_seed(FLAGS.seed)
         if not torch.cuda.is_available():
             raise RuntimeError("training needs an MI355X (no CPU fallback for the SpMM/history path)")
+        check_history_dtype()             # (--history_dtype bf16 with --det_dropout: refused before anything is built)
         par = DataParallel(device=None, init=False)
         dev_index = par.local_rank % torch.cuda.device_count()
         torch.cuda.set_device(dev_index)

@@ -12,15 +12,19 @@ class VRGCN(GCN):
                                     **kwargs)
 
     def _build_history(self):
-        """One zero-initialised, non-trainable N x dims fp32 history per aggregation layer,
-        resident in HBM (gcn/vrgcn.py:23-36).  Train and test models own separate histories."""
+        """One zero-initialised, non-trainable N x dims history per aggregation layer, resident in HBM
+        (gcn/vrgcn.py:23-36): fp32, or bfloat16 under --history_dtype bf16 (ops.history_alloc: N x pitch with
+        pitch = 8 * ceil(dims / 8), handed out as its [:, :dims] view).  Train and test models own separate histories."""
+        from . import ops
+        from .flags import check_history_dtype
+        bf16 = check_history_dtype()          # (refuses --det_dropout with a bfloat16 history)
         self.history = []
         for i in range(self.L):
             dims = self.agg0_dim if i == 0 else FLAGS.hidden1
             n_history = 2 if FLAGS.det_dropout else 1        # (mean, variance) under det-dropout, gcn/vrgcn.py:28
-            self.history.append([torch.zeros((self.num_data, dims), dtype=torch.float32, device=self.device)
-                                 for _ in range(n_history)])
-            print('History size = {} GB'.format(self.num_data * dims * 4 * n_history / 1024.0 / 1024.0 / 1024.0))
+            self.history.append([ops.history_alloc(self.num_data, dims, self.device, bf16) for _ in range(n_history)])
+            row_bytes = (dims + 7) // 8 * 8 * 2 if bf16 else dims * 4
+            print('History size = {} GB'.format(self.num_data * row_bytes * n_history / 1024.0 / 1024.0 / 1024.0))
 
     def _build_aggregators(self):
         for l in range(self.L):
