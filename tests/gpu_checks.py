@@ -1,6 +1,8 @@
 """Device-side checking helpers shared by the exact GPU tests (test_sparse_exact_gpu.py, test_dense_exact_gpu.py): operands
 and outputs inside NaN-filled buffers, so that a write outside a view or a changed operand is seen, and the comparison
-of a result with an exact fp64 value or with a per-element bound."""
+of a result with an exact fp64 value or with a per-element bound.  ``Slab`` (test_rows_exact_gpu.py) is the same idea for
+kernels that copy bits or write integers: 32-bit words at any pitch and base offset inside sentinel-filled guards, compared
+whole and bit for bit."""
 import numpy as np
 import torch
 
@@ -81,3 +83,62 @@ def check(call, dev, M, d, pitch, ref, bound=None, C_in=None, operands=(), what=
         assert op.unchanged(), "%s: an operand was modified" % what
     compare(outs[0].host(), ref, bound, what)
     return outs[0].buf
+
+
+NAN_BITS = 0x7fc05a5a                               # a NaN with a payload, as an int32
+FILL_INT = -7
+
+
+def _words(x):
+    """fp32 or int32 data as int32 words (integers of another width must fit)"""
+    x = np.ascontiguousarray(x)
+    if x.dtype.kind in "iu" and x.dtype.itemsize != 4:
+        assert x.size == 0 or (x.min() >= -2 ** 31 and x.max() < 2 ** 31)
+        x = x.astype(np.int32)
+    assert x.dtype.itemsize == 4, x.dtype
+    return x.view(np.int32)
+
+
+class Slab(object):
+    """``rows x d`` 32-bit words (int32, or the bits of fp32) at a pitch of ``ld`` words, starting ``off`` words past a
+    16-byte aligned address, inside a flat buffer filled with a sentinel (a NaN's bits, or -7 for integer outputs): guard
+    words in front and behind, the pitch padding, and every row a kernel is not to write.  ``same_as(ref_rows)`` compares
+    the WHOLE buffer -- view, padding and guards -- with the start state in which the view holds ``ref_rows``, bit for bit."""
+
+    GUARD = 64
+
+    def __init__(self, dev, rows, d, ld=None, off=0, data=None, fill=NAN_BITS):
+        ld = d if ld is None else ld
+        assert ld >= d and off >= 0
+        self.rows, self.d, self.ld, self.lo = rows, d, ld, self.GUARD + off
+        self.start = np.full(self.lo + rows * ld + self.GUARD, fill, np.int32)
+        if data is not None:
+            self.inside(self.start)[...] = _words(data).reshape(rows, d)
+        self.flat = torch.from_numpy(self.start).to(dev)
+        assert self.flat.data_ptr() % 16 == 0
+        self.ptr = self.flat.data_ptr() + 4 * self.lo
+
+    def inside(self, flat):
+        """the rows x d view of a host copy of the buffer"""
+        return flat[self.lo:self.lo + self.rows * self.ld].reshape(self.rows, self.ld)[:, :self.d]
+
+    def view(self, dtype=torch.float32):
+        v = self.flat[self.lo:self.lo + self.rows * self.ld].view(self.rows, self.ld)[:, :self.d]
+        return v.view(dtype) if dtype != torch.int32 else v
+
+    def expected(self, ref_rows=None):
+        want = self.start.copy()
+        if ref_rows is not None:
+            self.inside(want)[...] = _words(ref_rows).reshape(self.rows, self.d)
+        return want
+
+    def same_as(self, ref_rows=None, what=""):
+        got = self.flat.cpu().numpy()
+        want = self.expected(ref_rows)
+        if not np.array_equal(got, want):
+            bad = got != want
+            ins = self.inside(bad.copy())
+            n_in = int(ins.sum())
+            raise AssertionError("%s: %d words differ, %d inside the view (rows %s), %d in padding, guards or rows after it" % (
+                what, int(bad.sum()), n_in, np.nonzero(ins.any(axis=1))[0][:8], int(bad.sum()) - n_in))
+        return got
