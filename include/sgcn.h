@@ -50,7 +50,8 @@ const char* sgcn_last_error(void);
  *   v16 packed minibatch: + the medg weights in the order of adj^T's nonzeros (descriptors behind the CSR table); step ops
  *       GEMM .. GATE (the --det_dropout stacks as step programs)
  *       (additive, still v16: sgcn_moments_*; the bfloat16 history -- sgcn_vr_aggregate_h16 / _pre_h16 / _post_h16,
- *       sgcn_scatter_rows_h16, sgcn_gather_rows_h16, sgcn_hist_apply_h16, step ops 48 .. 53) */
+ *       sgcn_scatter_rows_h16, sgcn_gather_rows_h16, sgcn_hist_apply_h16, step ops 48 .. 53; the losses over a row
+ *       subset of N-row tables -- sgcn_softmax_ce_rows_f32 / sgcn_sigmoid_ce_rows_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -559,6 +560,21 @@ int sgcn_softmax_ce_f32(const float* dev_logits, int64_t ldz, const float* dev_l
 int sgcn_sigmoid_ce_f32(const float* dev_logits, int64_t ldz, const float* dev_labels, int64_t ldl,
                         int32_t n, int32_t c, float* dev_dlogits, int64_t lddz, float* dev_pred, int64_t ldp,
                         float* dev_stats, float* dev_rowstat, void* stream);
+/* The two losses over a SUBSET of the rows of N-row tables (exact full-graph training: logits for every vertex, the loss
+ * over the training ids).  logits, labels and dlogits (nullable) are N-row tables indexed by vertex; rows: n ascending,
+ * unique ids < N (the caller's promise: the device does not check it); pred (nullable) and rowstat are compact, in subset
+ * order.  With Z = logits[rows], Y = labels[rows]: stats, rowstat and pred are bit for bit what sgcn_softmax_ce_f32 /
+ * sgcn_sigmoid_ce_f32 give on (Z, Y, n), dlogits[rows[i]] is their dlogits[i], and every other row of dlogits is +0.0
+ * (columns < c; pad columns of a pitched table are not touched).  n == 0, n > N, a null rows or a pitch < c:
+ * SGCN_ERR_INVALID, nothing written.  No reference counterpart (the reference has no full-graph mode). */
+int sgcn_softmax_ce_rows_f32(const float* dev_logits, int64_t ldz, const float* dev_labels, int64_t ldl,
+                             int32_t N, int32_t c, const int32_t* dev_rows, int32_t n,
+                             float* dev_dlogits, int64_t lddz, float* dev_pred, int64_t ldp,
+                             float* dev_stats, float* dev_rowstat, void* stream);
+int sgcn_sigmoid_ce_rows_f32(const float* dev_logits, int64_t ldz, const float* dev_labels, int64_t ldl,
+                             int32_t N, int32_t c, const int32_t* dev_rows, int32_t n,
+                             float* dev_dlogits, int64_t lddz, float* dev_pred, int64_t ldp,
+                             float* dev_stats, float* dev_rowstat, void* stream);
 /* Weight decay on the flat-buffer range [lo, hi) (the vars of the first parametrised layer):
  * grad[i] += wd * theta[i] (grad nullable) and loss[0] += 0.5 * wd * sum theta[i]^2 (loss nullable),
  * deterministic.  Replaces FLAGS.weight_decay * tf.nn.l2_loss(var) and its gradient  gcn/models.py:68-75 */

@@ -196,6 +196,10 @@ SIGNATURES = {
                                       P, C.c_int64, P, P, P]),
     "sgcn_sigmoid_ce_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64,
                                       P, C.c_int64, P, P, P]),
+    "sgcn_softmax_ce_rows_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64,
+                                           P, C.c_int64, P, P, P]),
+    "sgcn_sigmoid_ce_rows_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64,
+                                           P, C.c_int64, P, P, P]),
     "sgcn_l2_penalty_f32": (C.c_int, [P, C.c_int64, C.c_int64, C.c_float, P, P, P]),
     "sgcn_csr_transpose_ws_ints": (C.c_int64, [C.c_int32, C.c_int64]),
     "sgcn_csr_transpose_index": (C.c_int, [C.c_int32, C.c_int64, P, P, P, P, P, P, P]),

@@ -476,42 +476,58 @@ __device__ __forceinline__ void ce_dx_tail(const CeDx& t, const float* wl, int64
     }
 }
 
+// The loss over a SUBSET of the rows of N-row tables (sgcn_*_ce_rows_f32; exact full-graph training, where the logits
+// cover every vertex and the loss the training ids): wave i of the grid works on table row rows[i]; pred and rowstat stay
+// compact, in subset order.  The kernels below are templates on it; <false> is the code of the plain entry points.
+struct CeRows {
+    const int32_t* rows;     // n ascending, unique row ids < N
+    int32_t N;               // rows of the tables
+};
+
+template <bool kRows>
+__device__ __forceinline__ int64_t ce_vertex(const CeRows& rs, int64_t row, bool live) {
+    if (!kRows) return row;
+    return live ? (int64_t)rs.rows[row] : 0;
+}
+
 // One wavefront per row, as many workgroups as rows need (a single-workgroup version spent
 // 277 us on 512 x 41 logits: ~40 dependent cross-lane shuffles per row, 128 rows per wave).
 // Per-row CE and hit flags go to `rowstat`; softmax_stats_kernel adds them in a fixed order
 // (deterministic loss / accuracy).
+template <bool kRows>
 __global__ __launch_bounds__(kBlock) void softmax_ce_kernel(
     const float* __restrict__ z, int64_t ldz, const float* __restrict__ lab, int64_t ldl, int32_t n,
     int32_t c, float* __restrict__ dz, int64_t lddz, float* __restrict__ pred, int64_t ldp,
-    float* __restrict__ rowstat /* [2][n], [3][n] with pred */, CeDx tail) {
+    float* __restrict__ rowstat /* [2][n], [3][n] with pred */, CeDx tail, CeRows rs) {
     extern __shared__ __attribute__((aligned(1024))) float ce_lds[];
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    const bool head = tail.hx != nullptr || tail.PW != nullptr;            // c <= 64: logit k lives in lane k
+    const bool head = !kRows && (tail.hx != nullptr || tail.PW != nullptr);            // c <= 64: logit k lives in lane k
     // everything the row pass reads from memory is requested before the weight matrix is staged (one round trip, not four)
     const bool live = row < n;
-    const float* lr = lab + (live ? row : 0) * ldl;
+    const int64_t vtx = ce_vertex<kRows>(rs, row, live);     // the row of the logits / labels / dlogits tables
+    const float* lr = lab + (live ? vtx : 0) * ldl;
     const float lab0 = (live && lane < c) ? lr[lane] : 0.f;
     float hx0 = 0.f, hx1 = 0.f, pin[4] = {0.f, 0.f, 0.f, 0.f};
     if (head && live && !tail.PW) {
         const float* xr = tail.hx + row * tail.ldhx;
         hx0 = lane < tail.K ? xr[lane] : 0.f; hx1 = lane + kWave < tail.K ? xr[lane + kWave] : 0.f;
     }
-    if (tail.PW && live) {
+    if (!kRows && tail.PW && live) {
         const float* xr = tail.px + row * tail.ldpx;
 #pragma unroll
         for (int e = 0; e < 4; e++) pin[e] = lane + e * kWave < tail.PK ? xr[lane + e * kWave] : 0.f;
     }
-    if (tail.K > 0) ce_dx_stage(tail, c, ce_lds);
+    if (!kRows && tail.K > 0) ce_dx_stage(tail, c, ce_lds);
     if (!live) return;
     const float inv_n = 1.0f / (float)n;
-    if (tail.PW) {
+    if (!kRows && tail.PW) {
         float o[2];
         ce_pre_layer(tail, ce_lds + ce_w_region(tail.K, c), row, lane, pin, o);
         hx0 = o[0]; hx1 = o[1];
     }
     const float myz = head ? ce_head(tail, ce_lds, row, lane, c, hx0, hx1) : 0.f;
-    const float* zr = z + row * ldz;
+    const float* zr = z + vtx * ldz;
     auto zv = [&](int k) { return head ? myz : zr[k]; };
     auto lv = [&](int k) { return k < kWave ? lab0 : lr[k]; };     // k == lane in the first trip of every loop below
     float m = -INFINITY, lm = -INFINITY;
@@ -538,7 +554,7 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_kernel(
         const float logp = zv(k) - lse, p = __expf(logp);
         l -= lv(k) * logp;
         mydz = (p * sl - lv(k)) * inv_n;
-        if (dz) dz[row * lddz + k] = mydz;
+        if (dz) dz[vtx * lddz + k] = mydz;
         if (pred) { pred[row * ldp + k] = p; if (p > pm) { pm = p; apm = k; } }
     }
     l = wave_sum(l);
@@ -553,7 +569,7 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_kernel(
         }
         if (lane == 0) rowstat[2 * (int64_t)n + row] = (float)(apm + 4096 * alm);
     }
-    if (tail.dx) ce_dx_tail(tail, ce_lds, row, lane, c, mydz);
+    if (!kRows && tail.dx) ce_dx_tail(tail, ce_lds, row, lane, c, mydz);
 }
 
 // stats = {sum_i CE_i, #correct, mean CE, accuracy}: one workgroup, fixed summation order
@@ -578,30 +594,32 @@ __global__ __launch_bounds__(kBlock) void softmax_stats_kernel(const float* __re
 // max(z,0) - z*y + log1p(exp(-|z|)) (tf.nn.sigmoid_cross_entropy_with_logits, gcn/models.py:77-79);
 // accuracy = mean((z > 0) == (y > 0.5)) (gcn/models.py:86-90); pred = sigmoid(z) (:198-200);
 // dlogits = (sigmoid(z) - y) / (n*c).  One wave per row; per-row sums -> sigmoid_stats_kernel.
+template <bool kRows>
 __global__ __launch_bounds__(kBlock) void sigmoid_ce_kernel(
     const float* __restrict__ z, int64_t ldz, const float* __restrict__ lab, int64_t ldl, int32_t n,
     int32_t c, float* __restrict__ dz, int64_t lddz, float* __restrict__ pred, int64_t ldp,
-    float* __restrict__ rowstat /* [2][n] */, CeDx tail) {
+    float* __restrict__ rowstat /* [2][n] */, CeDx tail, CeRows rs) {
     extern __shared__ __attribute__((aligned(1024))) float ce_lds[];
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    const bool head = tail.hx != nullptr || tail.PW != nullptr;
+    const bool head = !kRows && (tail.hx != nullptr || tail.PW != nullptr);
     const bool live = row < n;
-    const float lab0 = (live && lane < c) ? lab[row * ldl + lane] : 0.f;      // requested before the weights are staged
+    const int64_t vtx = ce_vertex<kRows>(rs, row, live);
+    const float lab0 = (live && lane < c) ? lab[vtx * ldl + lane] : 0.f;      // requested before the weights are staged
     float hx0 = 0.f, hx1 = 0.f, pin[4] = {0.f, 0.f, 0.f, 0.f};
     if (head && live && !tail.PW) {
         const float* xr = tail.hx + row * tail.ldhx;
         hx0 = lane < tail.K ? xr[lane] : 0.f; hx1 = lane + kWave < tail.K ? xr[lane + kWave] : 0.f;
     }
-    if (tail.PW && live) {
+    if (!kRows && tail.PW && live) {
         const float* xr = tail.px + row * tail.ldpx;
 #pragma unroll
         for (int e = 0; e < 4; e++) pin[e] = lane + e * kWave < tail.PK ? xr[lane + e * kWave] : 0.f;
     }
-    if (tail.K > 0) ce_dx_stage(tail, c, ce_lds);
+    if (!kRows && tail.K > 0) ce_dx_stage(tail, c, ce_lds);
     if (!live) return;
     const float inv = 1.0f / ((float)n * (float)c);
-    if (tail.PW) {
+    if (!kRows && tail.PW) {
         float o[2];
         ce_pre_layer(tail, ce_lds + ce_w_region(tail.K, c), row, lane, pin, o);
         hx0 = o[0]; hx1 = o[1];
@@ -609,18 +627,18 @@ __global__ __launch_bounds__(kBlock) void sigmoid_ce_kernel(
     const float myz = head ? ce_head(tail, ce_lds, row, lane, c, hx0, hx1) : 0.f;
     float l = 0.f, hit = 0.f, mydz = 0.f;
     for (int k = lane; k < c; k += kWave) {
-        const float x = head ? myz : z[row * ldz + k], y = k < kWave ? lab0 : lab[row * ldl + k];
+        const float x = head ? myz : z[vtx * ldz + k], y = k < kWave ? lab0 : lab[vtx * ldl + k];
         const float e = __expf(-fabsf(x));
         l += fmaxf(x, 0.f) - x * y + log1pf(e);
         const float p = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
         hit += ((x > 0.f) == (y > 0.5f)) ? 1.f : 0.f;
         mydz = (p - y) * inv;
-        if (dz) dz[row * lddz + k] = mydz;
+        if (dz) dz[vtx * lddz + k] = mydz;
         if (pred) pred[row * ldp + k] = p;
     }
     l = wave_sum(l); hit = wave_sum(hit);
     if (lane == 0) { rowstat[row] = l; rowstat[n + row] = hit; }
-    if (tail.dx) ce_dx_tail(tail, ce_lds, row, lane, c, mydz);
+    if (!kRows && tail.dx) ce_dx_tail(tail, ce_lds, row, lane, c, mydz);
 }
 
 // stats = {sum CE, #correct elements, mean CE, accuracy} over n*c elements, fixed summation order
@@ -990,17 +1008,17 @@ int ce_impl(bool softmax, const float* logits, int64_t ldz, const float* labels,
         SGCN_REQUIRE(lds <= 160 * 1024, "ce: the two weight matrices do not fit the LDS");
         static bool raised = false;        // > 64 KB of dynamic LDS needs the attribute, once per kernel
         if (lds > 64 * 1024 && !raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&softmax_ce_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sigmoid_ce_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&softmax_ce_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sigmoid_ce_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             raised = true;
         }
     }
     if (softmax)
-        hipLaunchKernelGGL(softmax_ce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kBlock), lds, st, logits, ldz, labels, ldl,
-                           n, c, dlogits, lddz, pred, ldp, rowstat, tail);
+        hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(kBlock), lds, st, logits, ldz, labels, ldl,
+                           n, c, dlogits, lddz, pred, ldp, rowstat, tail, CeRows{});
     else
-        hipLaunchKernelGGL(sigmoid_ce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kBlock), lds, st, logits, ldz, labels, ldl,
-                           n, c, dlogits, lddz, pred, ldp, rowstat, tail);
+        hipLaunchKernelGGL(sigmoid_ce_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(kBlock), lds, st, logits, ldz, labels, ldl,
+                           n, c, dlogits, lddz, pred, ldp, rowstat, tail, CeRows{});
     if (pending_stats().on) {            // parked for the optimizer's launch
         PendingStats& p = pending_stats();
         p.armed = 1; p.softmax = softmax ? 1 : 0; p.rowstat = rowstat; p.n = n; p.c = c; p.stats = stats;
@@ -1019,7 +1037,46 @@ int ce_impl(bool softmax, const float* logits, int64_t ldz, const float* labels,
     SGCN_HIP_TRY(hipGetLastError());
     return SGCN_OK;
 }
+
+// The off-subset rows of dlogits get their zeros from ONE hipMemset2DAsync over the table in front of the kernel.  (Zeroing
+// the gap in front of each row by that row's wave was 2 - 3 % faster on a uniformly random subset, but serial in the gap's
+// length: a subset that is a prefix of the ids leaves N - n rows to one wave.  DESIGN.md 3.7.)
+int ce_rows_impl(bool softmax, const float* logits, int64_t ldz, const float* labels, int64_t ldl, int32_t N, int32_t c,
+                 const int32_t* rows, int32_t n, float* dlogits, int64_t lddz, float* pred, int64_t ldp, float* stats,
+                 float* rowstat, void* stream) {
+    SGCN_REQUIRE(N > 0 && c > 0 && n > 0 && n <= N, "ce_rows: need 0 < n <= N and c > 0 (N = %d, n = %d, c = %d)", N, n, c);
+    SGCN_REQUIRE(logits && labels && rows && stats && rowstat, "ce_rows: null operand");
+    SGCN_REQUIRE(ldz >= c && ldl >= c && (!dlogits || lddz >= c) && (!pred || ldp >= c), "ce_rows: bad pitch");
+    hipStream_t st = (hipStream_t)stream;
+    if (dlogits)
+        SGCN_HIP_TRY(hipMemset2DAsync(dlogits, (size_t)lddz * sizeof(float), 0, (size_t)c * sizeof(float), (size_t)N, st));
+    const CeRows rs{rows, N};
+    const dim3 grid((unsigned)((n + 3) / 4));
+    if (softmax)
+        hipLaunchKernelGGL(softmax_ce_kernel<true>, grid, dim3(kBlock), 0, st, logits, ldz, labels, ldl, n, c, dlogits, lddz,
+                           pred, ldp, rowstat, CeDx{}, rs);
+    else
+        hipLaunchKernelGGL(sigmoid_ce_kernel<true>, grid, dim3(kBlock), 0, st, logits, ldz, labels, ldl, n, c, dlogits, lddz,
+                           pred, ldp, rowstat, CeDx{}, rs);
+    if (softmax) hipLaunchKernelGGL(softmax_stats_kernel, dim3(1), dim3(kBlock), 0, st, rowstat, n, stats);
+    else hipLaunchKernelGGL(sigmoid_stats_kernel, dim3(1), dim3(kBlock), 0, st, rowstat, n, c, stats);
+    SGCN_HIP_TRY(hipGetLastError());
+    return SGCN_OK;
+}
 }  // namespace sgcn
+
+extern "C" int sgcn_softmax_ce_rows_f32(const float* logits, int64_t ldz, const float* labels, int64_t ldl, int32_t N,
+                                        int32_t c, const int32_t* rows, int32_t n, float* dlogits, int64_t lddz,
+                                        float* pred, int64_t ldp, float* stats, float* rowstat, void* stream) {
+    SGCN_REQUIRE(!(pred && rowstat) || c <= 4096, "softmax_ce_rows: the class plane of rowstat holds at most 4096 classes (c = %d)", c);
+    return sgcn::ce_rows_impl(true, logits, ldz, labels, ldl, N, c, rows, n, dlogits, lddz, pred, ldp, stats, rowstat, stream);
+}
+
+extern "C" int sgcn_sigmoid_ce_rows_f32(const float* logits, int64_t ldz, const float* labels, int64_t ldl, int32_t N,
+                                        int32_t c, const int32_t* rows, int32_t n, float* dlogits, int64_t lddz,
+                                        float* pred, int64_t ldp, float* stats, float* rowstat, void* stream) {
+    return sgcn::ce_rows_impl(false, logits, ldz, labels, ldl, N, c, rows, n, dlogits, lddz, pred, ldp, stats, rowstat, stream);
+}
 
 extern "C" int sgcn_softmax_ce_f32(const float* logits, int64_t ldz, const float* labels,
                                    int64_t ldl, int32_t n, int32_t c, float* dlogits, int64_t lddz,

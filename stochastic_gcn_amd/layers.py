@@ -356,7 +356,8 @@ def _squared(A):
 
 
 class PlainAggregator(Layer):
-    """gcn/layers.py:214-257: Z = A.H, or concat(H[:n1], A.H); on (mu, var): A.mu and A^2.var."""
+    """gcn/layers.py:214-257: Z = A.H, or concat(H[:n1], A.H); on (mu, var): A.mu and A^2.var.  The products go through the
+    adjacency object (``A.product``): ops.spmm for a minibatch DeviceCSR, a static-graph kernel for a full-graph matrix."""
 
     def __init__(self, model, l, **kw):
         super(PlainAggregator, self).__init__(**kw)
@@ -382,10 +383,10 @@ class PlainAggregator(Layer):
         n1, d = A.shape[0], x.shape[1]
         self._A, self._concat, self._d = A, concat, d
         if not concat:
-            return ops.spmm(A, x)
+            return A.product(x)
         out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
         out[:, :d] = x[:n1]
-        ops.spmm(A, x, out=out[:, d:])
+        A.product(x, out=out[:, d:])
         return out
 
     def backward(self, g):
@@ -397,9 +398,10 @@ class PlainAggregator(Layer):
             return (ops.spmm(A.transpose, g[0][:, d:], add=g[0][:, :d], add_rows=n1),
                     ops.spmm(A2.transpose, g[1][:, d:], add=g[1][:, :d], add_rows=n1))
         if not self._concat:
-            return ops.spmm(A.transpose, g)
-        # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch)
-        return ops.spmm(A.transpose, g[:, d:], add=g[:, :d], add_rows=A.shape[0])
+            return A.transpose.product(g)
+        # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep
+        # kernel stores it first and multiplies with beta = 1 (full_batch.StaticMatrix.product)
+        return A.transpose.product(g[:, d:], add=g[:, :d], add_rows=A.shape[0])
 
 
 class VRAggregator(Layer):

@@ -30,6 +30,7 @@ from . import ops
 from ._ffi import check, lib as _lib
 from .flags import FLAGS
 from .layers import (AugmentedDropoutDense, Dense, DetDropoutFC, Dropout, SparseInput)
+from .full_batch import StaticBatch
 from .scheduler import PackedBatch, build_plan
 
 
@@ -572,6 +573,8 @@ class GCN(Model):
     def upload(self, feed_dict):
         """feed-dict -> DevFeed (two H2D copies) and the input feature rows."""
         cv = bool(self._history)        # (structure only: no join, see ``history``)
+        if isinstance(feed_dict, StaticBatch):
+            return self._upload_static(feed_dict)
         if isinstance(feed_dict, PackedBatch):
             cur = DevFeed.from_packed(feed_dict, self.device)
         else:
@@ -585,6 +588,22 @@ class GCN(Model):
         else:       # gathered by the first dense layer's GEMMs, or on demand (ops.GatheredRows)
             cur.inputs = ops.GatheredRows(self.features_dev, f0)
         return cur
+
+    def _upload_static(self, sb):
+        """A full-graph batch (full_batch.StaticBatch): nothing to copy -- the input is the resident feature table itself,
+        all N rows in vertex order (dense: hstack(X, A.X) under --preprocess; sparse: the whole feature CSR)."""
+        if self._history or sb.L != self.L or sb.N != self.num_data:
+            raise ValueError("a static batch needs a model without history, with %d aggregation layer(s) over %d vertices"
+                             % (sb.L, sb.N))
+        if self.sparse_input and self.sparse_mm:
+            inp = self.__dict__.get('_static_input')
+            if inp is None:
+                f = self.features_dev
+                f.coo_rows = torch.from_numpy(np.repeat(np.arange(f.shape[0], dtype=np.int32),
+                                                        np.diff(self.features.indptr))).to(self.device)
+                inp = self._static_input = SparseInput(f)
+            return sb.cur(inp)              # (one object for the run: its transpose index is built once)
+        return sb.cur(self.features_dev)
 
     def _madj(self, feed_dict, l):
         """The det-dropout aggregator's third matrix (placeholders['madj'], gcn/train.py:92): the minibatch adjacency's
@@ -611,9 +630,12 @@ class GCN(Model):
         want_grad = self.is_training or self._want_grad
         want_pred = not self.is_training or self._want_grad
         ce = ops.sigmoid_ce if self.multitask else ops.softmax_ce
-        stats, dlogits, pred = ce(z, labels, want_grad=want_grad, want_pred=want_pred)
+        # a static batch: the logits cover every vertex, the loss the rows of ``cur.rows`` (pred, the per-row scratch and the
+        # classes are then compact, in subset order; dlogits covers all rows, zero off the subset)
+        rows = getattr(self.cur, 'rows', None)
+        stats, dlogits, pred = ce(z, labels, want_grad=want_grad, want_pred=want_pred, rows=rows)
         # the rows' classes for the F1 scores (sgcn_softmax_ce_f32: argmax(pred) + 4096 * argmax(labels)), single-label only
-        n = int(z.shape[0])
+        n = int(z.shape[0] if rows is None else rows.shape[0])
         self.eval_classes = stats[4 + 2 * n:4 + 3 * n] if (want_pred and not self.multitask) else None
         if FLAGS.weight_decay and self._wd_range[1] > self._wd_range[0]:
             ops.l2_penalty(self.theta, self._wd_range[0], self._wd_range[1], FLAGS.weight_decay, loss=stats[2:3])
@@ -661,7 +683,7 @@ class GCN(Model):
 
     def get_data(self, feed_dict):
         cur = self.upload(feed_dict)
-        if isinstance(feed_dict, PackedBatch):
+        if isinstance(feed_dict, (PackedBatch, StaticBatch)):
             self._count_sizes(cur.sizes)
         else:
             self._count(feed_dict)
@@ -911,7 +933,7 @@ class GCN(Model):
         t = time()
         if not self.is_training:
             self.dropout = 0.0
-        elif isinstance(feed_dict, PackedBatch):
+        elif isinstance(feed_dict, (PackedBatch, StaticBatch)):
             self.dropout = float(getattr(feed_dict, 'dropout', 0.0) or 0.0)
         else:
             self.dropout = float(feed_dict.get(self.placeholders['dropout'], 0.0))

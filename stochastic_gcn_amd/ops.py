@@ -147,6 +147,11 @@ class DeviceCSR(object):
     def nnz(self):
         return int(self.col.shape[0])
 
+    def product(self, x, out=None, add=None, add_rows=0):
+        """out = A x (+ add on the first ``add_rows`` rows): what an aggregator calls on its adjacency object (a
+        full_batch.StaticMatrix answers the same call with a static-graph kernel)."""
+        return spmm(self, x, out=out, add=add, add_rows=add_rows)
+
     @staticmethod
     def from_arrays(shape, rowptr, col, val, device, plan_T=0, with_plan=True):
         rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
@@ -386,33 +391,55 @@ def ln_act_bwd(dy, y, ctx, scale, relu, doffset=None, dscale=None):
     return dx
 
 
-def softmax_ce(logits, labels, want_grad=True, want_pred=False):
-    """(stats[4] = {sum CE, #correct, mean CE, accuracy}, dlogits or None, pred or None)
-    (sgcn_softmax_ce_f32)."""
+def check_loss_rows(rows, N):
+    """The host check of a loss subset (the device trusts it): int32 ids in [0, N), ascending and unique."""
+    r = np.asarray(rows)
+    if r.ndim != 1 or r.size == 0 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("loss rows must be a non-empty 1-D integer array")
+    if int(r[0]) < 0 or int(r[-1]) >= N or (r.size > 1 and not bool(np.all(r[1:] > r[:-1]))):
+        raise ValueError("loss rows must be ascending, unique and in [0, %d)" % N)
+    return np.ascontiguousarray(r, dtype=np.int32)
+
+
+def _ce(fn, fn_rows, planes, logits, labels, want_grad, want_pred, rows):
     zp, ldz = _rows2d(logits, "logits")
     lp, ldl = _rows2d(labels, "labels")
-    n, c = int(logits.shape[0]), int(logits.shape[1])
+    N, c = int(logits.shape[0]), int(logits.shape[1])
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor):       # host ids: checked here, then uploaded
+            rows = torch.from_numpy(check_loss_rows(rows, N)).to(logits.device)
+        _dev(rows, torch.int32, "rows")
+        if labels.shape[0] != N:
+            raise ValueError("with rows, labels is the table of all %d rows (got %d)" % (N, labels.shape[0]))
+    n = N if rows is None else int(rows.shape[0])
     # [stats | per-row scratch | with pred: the rows' classes, argmax(pred) + 4096 * argmax(labels)]
-    stats = torch.empty(4 + (3 if want_pred else 2) * n, dtype=torch.float32, device=logits.device)
-    dz = torch.empty((n, c), dtype=torch.float32, device=logits.device) if want_grad else None
+    stats = torch.empty(4 + planes * n, dtype=torch.float32, device=logits.device)
+    dz = torch.empty((N, c), dtype=torch.float32, device=logits.device) if want_grad else None
     pred = torch.empty((n, c), dtype=torch.float32, device=logits.device) if want_pred else None
-    check(lib.sgcn_softmax_ce_f32(zp, ldz, lp, ldl, n, c, _ptr(dz), c, _ptr(pred), c, stats.data_ptr(),
-                                  stats.data_ptr() + 16, _stream()))
+    if rows is None:
+        check(fn(zp, ldz, lp, ldl, n, c, _ptr(dz), c, _ptr(pred), c, stats.data_ptr(), stats.data_ptr() + 16, _stream()))
+    else:
+        check(fn_rows(zp, ldz, lp, ldl, N, c, rows.data_ptr(), n, _ptr(dz), c, _ptr(pred), c, stats.data_ptr(),
+                      stats.data_ptr() + 16, _stream()))
     return stats, dz, pred
 
 
-def sigmoid_ce(logits, labels, want_grad=True, want_pred=False):
+def softmax_ce(logits, labels, want_grad=True, want_pred=False, rows=None):
+    """(stats[4] = {sum CE, #correct, mean CE, accuracy}, dlogits or None, pred or None)
+    (sgcn_softmax_ce_f32).  ``rows``: the loss over that subset of the rows of N-row tables -- dlogits covers all N rows,
+    +0.0 off the subset; pred and the per-row scratch are compact, in subset order (sgcn_softmax_ce_rows_f32).  Host ids
+    (a NumPy array or list) are checked by check_loss_rows -- ascending, unique, in [0, N) -- and uploaded.  An int32
+    DEVICE tensor is trusted, because reading it back would cost a synchronisation per call: its ids MUST have passed
+    check_loss_rows (StaticBatch does that), an id >= N is an out-of-bounds access on the device."""
+    return _ce(lib.sgcn_softmax_ce_f32, lib.sgcn_softmax_ce_rows_f32, 3 if want_pred else 2, logits, labels,
+               want_grad, want_pred, rows)
+
+
+def sigmoid_ce(logits, labels, want_grad=True, want_pred=False, rows=None):
     """Multitask (ppi) loss: (stats[4] = {sum CE, #correct elements, mean CE, element accuracy}, dlogits
-    or None, pred = sigmoid(logits) or None)   (sgcn_sigmoid_ce_f32)."""
-    zp, ldz = _rows2d(logits, "logits")
-    lp, ldl = _rows2d(labels, "labels")
-    n, c = int(logits.shape[0]), int(logits.shape[1])
-    stats = torch.empty(4 + 2 * n, dtype=torch.float32, device=logits.device)
-    dz = torch.empty((n, c), dtype=torch.float32, device=logits.device) if want_grad else None
-    pred = torch.empty((n, c), dtype=torch.float32, device=logits.device) if want_pred else None
-    check(lib.sgcn_sigmoid_ce_f32(zp, ldz, lp, ldl, n, c, _ptr(dz), c, _ptr(pred), c, stats.data_ptr(),
-                                  stats.data_ptr() + 16, _stream()))
-    return stats, dz, pred
+    or None, pred = sigmoid(logits) or None)   (sgcn_sigmoid_ce_f32; with ``rows`` as softmax_ce:
+    sgcn_sigmoid_ce_rows_f32)."""
+    return _ce(lib.sgcn_sigmoid_ce_f32, lib.sgcn_sigmoid_ce_rows_f32, 2, logits, labels, want_grad, want_pred, rows)
 
 
 def l2_penalty(theta, lo, hi, wd, grad=None, loss=None):

@@ -14,6 +14,7 @@ study, GradientVariance) -> Test().
 """
 from __future__ import division, print_function
 
+import os
 import queue
 import sys
 import threading
@@ -25,6 +26,7 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_history_dtype
+from .full_batch import StaticBatch, StaticMatrix, check_full_batch
 from .models import make_template
 from .parallel import DataParallel
 from .plaingcn import PlainGCN
@@ -93,6 +95,13 @@ def static_kernel_for(nnz, d, products):
     rows = products * t_rows
     cs = CS_PLAN_S_PER_NNZ * nnz + (CS_AUTOTUNE_PRODUCTS + products) * CS_TIME_RATIO * t_rows
     return 'cs' if cs < rows else 'rows'
+
+
+def full_batch_products(which):
+    """How many times the plan of a full-graph matrix will run (what static_kernel_for weighs its setup against).  SGDTrain
+    leaves on `epoch > FLAGS.epochs` (gcn/train.py:234), i.e. after epochs + 2 epochs: 'train' -- one step in each of them;
+    'full' -- one evaluation in each of them and the test."""
+    return int(FLAGS.epochs) + 2 if which == 'train' else int(FLAGS.epochs) + 3
 
 
 def pp_products(train_adj, full_adj, features, device, cache=(None, None), stats=None, products=1):
@@ -264,6 +273,8 @@ class Trainer(object):
     def __init__(self, data=None, verbose=True):
         np.random.seed(FLAGS.seed)
         torch.manual_seed(FLAGS.seed)
+        # (--full_batch / --test_full_batch with an estimator, a sampler option or several ranks: refused before a device is touched)
+        self.full_batch, self.test_full_batch = check_full_batch(world=int(os.environ.get("WORLD_SIZE", "1")))
         if not torch.cuda.is_available():
             raise RuntimeError("training needs an MI355X (no CPU fallback for the SpMM/history path)")
         check_history_dtype()             # (--history_dtype bf16 with --det_dropout: refused before anything is built)
@@ -336,33 +347,106 @@ class Trainer(object):
 
         train_degrees = np.array([FLAGS.degree] * L, dtype=np.int32)
         test_degrees = np.array([FLAGS.test_degree] * test_L, dtype=np.int32)
-        self.train_sch = PyScheduler(train_adj, labels, L, train_degrees, placeholders,
-                                     par.sampler_seed(FLAGS.seed), self.train_d, cv=FLAGS.cv,
-                                     importance=FLAGS.importance)
-        # the evaluation sampler is seeded IDENTICALLY on every rank: all ranks evaluate the same
-        # vertices with the same (all-reduced) weights, so validation cost -- and with it the
-        # early-stopping decision -- agrees across the job
-        self.eval_sch = PyScheduler(full_adj, labels, test_L, test_degrees, placeholders,
-                                    int(FLAGS.seed), cv=FLAGS.test_cv,
-                                    importance=FLAGS.test_importance)
         self.sess = None   # API compatibility: run_one_step(sess, feed_dict)
         from .scheduler import StagingSlot
         nthr = max(1, int(FLAGS.sampler_threads))
-        self.train_schs, self.eval_schs = [self.train_sch], [self.eval_sch]
-        for k in range(1, nthr):           # non-parity fast mode: extra sampler instances
-            self.train_schs.append(PyScheduler(train_adj, labels, L, train_degrees, placeholders,
-                                               par.sampler_seed(FLAGS.seed) + 1000 * k, cv=FLAGS.cv,
-                                               importance=FLAGS.importance))
-            self.eval_schs.append(PyScheduler(full_adj, labels, test_L, test_degrees, placeholders,
-                                              int(FLAGS.seed) + 1000 * k, cv=FLAGS.test_cv,
-                                              importance=FLAGS.test_importance))
         ring = max(FLAGS.prefetch, 1) * nthr + 3
-        self.slots = [StagingSlot(pin=True) for _ in range(ring)]
-        self.eval_slots = [StagingSlot(pin=True) for _ in range(ring if nthr > 1 else 4)]
+        self.train_sch = self.eval_sch = None
+        self.train_schs, self.eval_schs, self.slots, self.eval_slots = [], [], [], []
+        self.static_setup_s = 0.0
+        caches = plan_cache_paths(FLAGS.dataset)
+        if self.full_batch:
+            # exact full-graph training: no sampler, no prefetcher, no staging slots -- one static batch over train_adj
+            t = time()
+            self.train_static = self._static_batch(train_adj, 'train', caches[0], self.train_model, self.train_d)
+            self.static_setup_s += time() - t
+        else:
+            self.train_sch = PyScheduler(train_adj, labels, L, train_degrees, placeholders,
+                                         par.sampler_seed(FLAGS.seed), self.train_d, cv=FLAGS.cv,
+                                         importance=FLAGS.importance)
+            self.train_schs = [self.train_sch]
+            for k in range(1, nthr):           # non-parity fast mode: extra sampler instances
+                self.train_schs.append(PyScheduler(train_adj, labels, L, train_degrees, placeholders,
+                                                   par.sampler_seed(FLAGS.seed) + 1000 * k, cv=FLAGS.cv,
+                                                   importance=FLAGS.importance))
+            self.slots = [StagingSlot(pin=True) for _ in range(ring)]
+        if self.test_full_batch:
+            t = time()
+            self.eval_static = self._static_batch(full_adj, 'full', caches[1], self.test_model,
+                                                  val_d if len(val_d) else test_d)
+            self._eval_rows, self._eval_logits_key = {}, None
+            self.static_setup_s += time() - t
+        else:
+            # the evaluation sampler is seeded IDENTICALLY on every rank: all ranks evaluate the same
+            # vertices with the same (all-reduced) weights, so validation cost -- and with it the
+            # early-stopping decision -- agrees across the job
+            self.eval_sch = PyScheduler(full_adj, labels, test_L, test_degrees, placeholders,
+                                        int(FLAGS.seed), cv=FLAGS.test_cv,
+                                        importance=FLAGS.test_importance)
+            self.eval_schs = [self.eval_sch]
+            for k in range(1, nthr):
+                self.eval_schs.append(PyScheduler(full_adj, labels, test_L, test_degrees, placeholders,
+                                                  int(FLAGS.seed) + 1000 * k, cv=FLAGS.test_cv,
+                                                  importance=FLAGS.test_importance))
+            self.eval_slots = [StagingSlot(pin=True) for _ in range(ring if nthr > 1 else 4)]
         self.cost_val = []
         self.avg_loss = Averager(1)
         self.avg_acc = Averager(1)
         self.last_epoch = {}
+
+    # ---- the full-graph modes (full_batch.py) -----------------------------------------------------
+    def _static_batch(self, adj, which, cache_path, model, rows):
+        """The static batch of one adjacency for one model: the matrix with its plan (kernel by --full_batch_kernel; auto:
+        static_kernel_for on the number of times the plan will run), the label table, the loss rows."""
+        widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(model.L)]
+        mat = StaticMatrix(adj, self.device, FLAGS.full_batch_kernel, full_batch_products(which),
+                           max(widths or [FLAGS.hidden1]), cache_path)
+        labels = self.__dict__.get('_labels_dev')          # ONE N x C table on the device for both static batches
+        if labels is None:
+            labels = self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
+        return StaticBatch(mat, labels, np.sort(np.asarray(rows)), model.L, self.device)
+
+    def _weights_version(self):
+        """Changes whenever the shared weights do: Adam steps (either model class steps through adam_t) and in-place torch
+        writes (checkpoint load, set_params)."""
+        return (int(getattr(self.train_model, 'adam_t', 0)), int(self.test_model.theta._version),
+                self.test_model.theta.data_ptr())
+
+    def evaluate_full_batch(self, data):
+        """evaluate() under --test_full_batch: ONE exact forward of the test model over the full adjacency -- cached per
+        weight version, so validation and test after the same epoch share it -- and the loss over rows = sort(data)."""
+        t_test = time()
+        model, N = self.test_model, len(data)
+        if N == 0:
+            return 0.0, 0.0, 0.0, 0.0, time() - t_test
+        key = np.asarray(data).tobytes()
+        sb = self._eval_rows.get(key)
+        if sb is None:
+            sb = self._eval_rows[key] = self.eval_static.with_rows(np.sort(np.asarray(data)))
+        model.join_history()
+        model.dropout = 0.0
+        ops.pin_stream()
+        try:
+            ver = self._weights_version()
+            if self._eval_logits_key != ver or model.cur is None or model.outputs is None:
+                model.forward(model.get_data(sb))
+                self._eval_logits_key = ver
+            model.cur.rows = sb.rows
+            model.eval_light = not self.multitask
+            try:
+                los, acc, prd, _ = model.loss_and_grad(model.cur.labels)
+            finally:
+                model.eval_light = False
+        finally:
+            ops.unpin_stream()
+        vec = model.__dict__.pop('eval_vec', None)
+        if vec is not None:       # single-label: [stats | CE | hit | classes per row], 4 bytes per row for the F1 scores
+            hv = vec.cpu().numpy()
+            v = hv[4 + 2 * N:4 + 3 * N].astype(np.int64)
+            micro, macro = f1_from_classes(v // 4096, v % 4096)
+            return float(hv[2]), float(hv[3]), micro, macro, (time() - t_test)
+        micro, macro = calc_f1(prd.cpu().numpy(), np.asarray(self.labels)[sb.host_rows], self.multitask)
+        return float(los), float(acc), micro, macro, (time() - t_test)
 
     # ---- evaluation (gcn/train.py:133-160) ------------------------------------------------------
     class _EvalSink(object):
@@ -383,6 +467,8 @@ class Trainer(object):
             return out
 
     def evaluate(self, data):
+        if self.test_full_batch:
+            return self.evaluate_full_batch(data)
         total_pred, total_labs, total_cls, stats = [], [], [], []
         t_test = time()
         N = len(data)
@@ -476,7 +562,30 @@ class Trainer(object):
         return float(tot[0]), float(tot[1]), micro, macro, (time() - t_test)
 
     # ---- one training epoch (gcn/train.py:182-209) ----------------------------------------------
+    def train_epoch_full_batch(self):
+        """One eager step over the whole graph: forward, loss over the train ids, backward, Adam.  No step program: at N
+        rows the launch chain is not the bound.  The dropout keys come from the model's step counter, as in any step."""
+        model = self.train_model
+        t = time()
+        model.init_counts()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        self.train_static.dropout = FLAGS.dropout
+        outs = model.run_one_step(self.sess, self.train_static, sync=False)
+        host_loop_s = time() - t
+        ev1.record()
+        torch.cuda.synchronize()
+        model.run_t = max(model.run_t, ev0.elapsed_time(ev1) * 1e-3)
+        self.avg_loss.add(float(outs[1]))
+        self.avg_acc.add(float(outs[2]))
+        self.last_epoch = dict(train_wall_s=time() - t, steps=1, sch_wait_s=0.0, host_loop_s=host_loop_s, producer_s=None,
+                               sampled_edges=float(model.adj_sizes.sum()), full_edges=0.0,
+                               field0=float(model.field_sizes[0]))
+        return t, 0.0
+
     def train_epoch(self):
+        if self.full_batch:
+            return self.train_epoch_full_batch()
         par, train_model, train_sch = self.par, self.train_model, self.train_sch
         train_sch.shuffle()
         t = time()
