@@ -51,7 +51,8 @@ const char* sgcn_last_error(void);
  *       GEMM .. GATE (the --det_dropout stacks as step programs)
  *       (additive, still v16: sgcn_moments_*; the bfloat16 history -- sgcn_vr_aggregate_h16 / _pre_h16 / _post_h16,
  *       sgcn_scatter_rows_h16, sgcn_gather_rows_h16, sgcn_hist_apply_h16, step ops 48 .. 53; the losses over a row
- *       subset of N-row tables -- sgcn_softmax_ce_rows_f32 / sgcn_sigmoid_ce_rows_f32) */
+ *       subset of N-row tables -- sgcn_softmax_ce_rows_f32 / sgcn_sigmoid_ce_rows_f32; a bfloat16 dense operand for the
+ *       static-graph products -- sgcn_spmm_csr_b16 / _csr_add_b16 / sgcn_spmm_cs_b16 / sgcn_spmm_cs_variant_b16) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -401,6 +402,38 @@ int sgcn_scatter_rows_h16(uint16_t* dev_H, int64_t ldh, const int32_t* dev_r, in
                           int32_t d, const float* dev_src, int64_t lds, void* stream);
 int sgcn_hist_apply_h16(uint16_t* dev_H, int64_t ldh, const int32_t* dev_recv, int32_t world, int32_t cap, int32_t d,
                         int32_t* dev_owner, void* stream);
+
+/* ---- bfloat16 dense operand of the static-graph products (--full_batch_dtype bf16; additive exports, no reference
+ * counterpart) --------------------------------------------------------------------------------------------------------
+ * The cost of A B on a static graph is the bytes of B that every nonzero pulls from an L2 (and, where B does not fit
+ * the L2s, over the fabric; between GPUs, the all-gather's payload).  These entries take B as a bfloat16 table in the
+ * storage contract of the bfloat16 history above: K x ldb uint16 with ldb in ELEMENTS, ldb % 8 == 0, ldb >= d and a
+ * 16-byte aligned base (SGCN_ERR_INVALID otherwise); columns [d, ldb) may hold anything and never influence a stored
+ * output column; load = bits << 16, exact.  The table is made from fp32 rows by sgcn_scatter_rows_h16(..., dev_r = NULL,
+ * ...) (round to nearest even on the bits); a bfloat16 history is such a table.  C, the plan's values, the accumulators
+ * and the split-row workspace stay fp32.
+ * Contract: each _b16 entry gives, bit for bit on every row, what its _f32 entry gives on a 16-byte aligned fp32 table of
+ * the same element pitch that holds the widened values -- the same plan, gidx, rscale, cscale, beta, addend and tuning
+ * knobs; the same kernels instantiated with an 8-byte (2-byte for a scalar column) gather and the widening in front of
+ * the multiply-adds; every other argument and the status conventions as in the _f32 entry.  A lane's piece of a B row
+ * halves: 1.2 KB instead of 2.4 KB per nonzero at d = 602.  (The LDS-staged sweep, sgcn_spmm_lds_f32, has no such form.) */
+int sgcn_spmm_csr_b16(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val,
+                      int32_t M, int32_t K, int32_t d,
+                      const uint16_t* dev_B, int64_t ldb, const int32_t* dev_gidx,
+                      const float* dev_rscale, const float* dev_cscale,
+                      float* dev_C, int64_t ldc, float beta,
+                      const sgcn_plan_t* plan, void* stream);
+int sgcn_spmm_csr_add_b16(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val,
+                          int32_t M, int32_t K, int32_t d, const uint16_t* dev_B, int64_t ldb,
+                          const int32_t* dev_gidx, const float* dev_rscale, const float* dev_cscale,
+                          float* dev_C, int64_t ldc, float beta, const sgcn_plan_t* plan,
+                          const float* dev_add, int64_t ldadd, int32_t add_rows, void* stream);
+int sgcn_spmm_cs_b16(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
+                     const uint16_t* dev_B, int64_t ldb, const int32_t* dev_gidx,
+                     const float* dev_rscale, const float* dev_cscale,
+                     float* dev_C, int64_t ldc, float beta, void* stream);
+/* sgcn_spmm_cs_variant for sgcn_spmm_cs_b16: the same kernel and geometry, marked "[bf16 operand]". */
+int sgcn_spmm_cs_variant_b16(const sgcn_csplan_t* plan, int32_t d, char* buf, int32_t buflen);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-

@@ -145,6 +145,14 @@ SIGNATURES = {
     "sgcn_gather_rows_h16": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "sgcn_scatter_rows_h16": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, P]),
     "sgcn_hist_apply_h16": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, C.c_int32, P, P]),
+    # bfloat16 dense operand of the static-graph products (--full_batch_dtype bf16): the fp32 entries' argument lists
+    "sgcn_spmm_csr_b16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
+                                    P, P, P, C.c_int64, C.c_float, C.POINTER(Plan), P]),
+    "sgcn_spmm_csr_add_b16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
+                                        P, P, P, C.c_int64, C.c_float, C.POINTER(Plan), P, C.c_int64, C.c_int32, P]),
+    "sgcn_spmm_cs_b16": (C.c_int, [C.POINTER(CsPlan), C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
+                                   P, P, P, C.c_int64, C.c_float, P]),
+    "sgcn_spmm_cs_variant_b16": (C.c_int, [C.POINTER(CsPlan), C.c_int32, C.c_char_p, C.c_int32]),
     "sgcn_coll_available": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgcn_coll_retain": (C.c_int, []),
     "sgcn_coll_abort": (C.c_int, []),

@@ -42,57 +42,8 @@ struct AggArgsT {
 };
 typedef AggArgsT<float> AggArgs;
 
-// VW history elements: `hraw` is the load (4 * VW bytes of an fp32 table, 2 * VW bytes of a bfloat16 one, kept as the
-// dwords it fetched), `hwiden` makes fp32 of what it returned (nothing to do; bits << 16, exact) -- the ONLY places where
-// the two instantiations of the kernels below differ.  They are two steps so that agg_row_kernel can request its U rows
-// first and widen them when it adds them; `hpin` keeps the compiler from moving the widening back up to the load, where
-// every load is followed by a wait for it and the U requests in flight are gone (measured: 12.8 us per launch of the
-// Reddit step against 9.3 for the fp32 table).
-template <class HT, int VW> struct HRaw;
-template <int VW> struct HRaw<float, VW> { typedef typename Vec<VW>::type type; };
-template <> struct HRaw<uint16_t, 4> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
-template <> struct HRaw<uint16_t, 2> { typedef uint32_t type; };
-template <> struct HRaw<uint16_t, 1> { typedef uint32_t type; };
-
-template <int VW>
-__device__ __forceinline__ typename HRaw<float, VW>::type hraw(const float* p) { return vload<VW>(p); }
-template <int VW>
-__device__ __forceinline__ typename HRaw<uint16_t, VW>::type hraw(const uint16_t* p) {
-    if constexpr (VW == 1) return *p;
-    else return *reinterpret_cast<const typename HRaw<uint16_t, VW>::type*>(p);
-}
-template <class HT, int VW>
-__device__ __forceinline__ typename HRaw<HT, VW>::type hraw_zero() {
-    typename HRaw<HT, VW>::type z = {};
-    return z;
-}
-// (not for scalar lanes, VW == 1: there the compiler contracts SOME of the fp32 form's U products into fused multiply-adds,
-// and only the unpinned bf16 form gets the same ones -- tests/test_history_bf16_gpu.py compares the bits for d = 7, 25, 41)
-template <class HT, int VW, class RT>
-__device__ __forceinline__ void hpin(RT& r) {
-    if constexpr (!std::is_same<HT, float>::value && VW > 1) asm volatile("" : "+v"(r));
-}
-template <int VW>
-__device__ __forceinline__ typename Vec<VW>::type hwiden(typename Vec<VW>::type r) { return r; }
-__device__ __forceinline__ float hwiden1(uint32_t r) { return __uint_as_float(r << 16); }
-template <int VW>
-__device__ __forceinline__ typename Vec<VW>::type hwiden(uint32_t r) {
-    static_assert(VW <= 2, "two bfloat16 per dword");
-    if constexpr (VW == 1) {
-        return hwiden1(r);
-    } else {
-        typename Vec<2>::type v = {hwiden1(r), __uint_as_float(r & 0xffff0000u)};
-        return v;
-    }
-}
-template <int VW>
-__device__ __forceinline__ typename Vec<VW>::type hwiden(typename HRaw<uint16_t, 4>::type r) {
-    static_assert(VW == 4, "four bfloat16 per dword pair");
-    typename Vec<4>::type v = {hwiden1(r.x), __uint_as_float(r.x & 0xffff0000u), hwiden1(r.y), __uint_as_float(r.y & 0xffff0000u)};
-    return v;
-}
-template <int VW, class HT>
-__device__ __forceinline__ typename Vec<VW>::type hload(const HT* p) { return hwiden<VW>(hraw<VW>(p)); }
+// hraw / hwiden / hpin / hload -- the load of a bfloat16 table and its widening -- live in sgcn_dev.h (shared with the
+// static-graph SpMM kernels)
 
 template <int VW>
 __device__ __forceinline__ void store_masked(float* p, typename Vec<VW>::type v, int left) {

@@ -82,8 +82,8 @@ struct SpmmArgs {
     const sgcn_seg_t* seg;   // nullable: implicit one segment per row
     int64_t nseg;
     int64_t nsegblk;         // blocks per slab
-    const float* B;
-    int64_t ldb;
+    const void* B;           // fp32, or uint16 for a bfloat16 operand (sgcn_spmm_csr_b16): the kernel's BT says which
+    int64_t ldb;             // in elements of B
     const int32_t* gidx;
     const float* rscale;
     const float* cscale;
@@ -131,9 +131,21 @@ __device__ __forceinline__ void epilogue_store(const SpmmArgs& a, int row, int v
     else vstore_head<VW>(out, r, left);
 }
 
-template <int G, int NV, int VW, int U>
+// BT: the dense operand's element -- float, or uint16_t for a bfloat16 table (sgcn_spmm_csr_b16).  The two instantiations
+// differ in the load (hraw: 2 * VW bytes per lane instead of 4 * VW), the byte offsets that go with it and the widening in
+// front of the multiply-add (hwiden: bits << 16, exact); lanes, order of the sums and epilogue are the same, so the bf16
+// form gives the bits of the fp32 form on the widened table.  As in sgcn_agg.hip the raw dwords stay pinned (hpin)
+// between the U requests and the updates, or every load would be followed by its wait; and the multiply-add the fp32
+// form gets by contraction is spelled out, because the compiler does not contract across the widening shift.  Scalar
+// lanes (VW == 1) are the exception, as in sgcn_agg.hip: there the fp32 form's U products are only PARTLY contracted
+// (packed multiplies, then adds), and the plain, unpinned expression is what gets the same ones.  That is the compiler's
+// choice, not the source's: after a toolchain change tests/test_spmm_b16_gpu.py (d = 1, 3, odd output pitches) says whether
+// it still holds, as tests/test_history_bf16_gpu.py does for the aggregator.
+template <int G, int NV, int VW, int U, class BT>
 __global__ __launch_bounds__(kBlock) void spmm_seg_kernel(SpmmArgs a) {
     typedef typename Vec<VW>::type VT;
+    typedef typename HRaw<BT, VW>::type RT;
+    constexpr bool kB16 = !std::is_same<BT, float>::value;
     constexpr int GPB = kBlock / G;
     const int lig = threadIdx.x & (G - 1);
     const int gib = threadIdx.x / G;
@@ -166,10 +178,10 @@ __global__ __launch_bounds__(kBlock) void spmm_seg_kernel(SpmmArgs a) {
         const int vi = vbase + k * G;
         act[k] = vi < a.nvec;
         acc[k] = vzero<VW>();
-        loff[k] = (uint32_t)min(vi, a.nvec - 1) * (uint32_t)(VW * sizeof(float));
+        loff[k] = (uint32_t)min(vi, a.nvec - 1) * (uint32_t)(VW * sizeof(BT));
     }
     const char* Bb = reinterpret_cast<const char*>(a.B);
-    const int64_t ldb_bytes = a.ldb * (int64_t)sizeof(float);
+    const int64_t ldb_bytes = a.ldb * (int64_t)sizeof(BT);
 
     for (int p0 = start; p0 < end; p0 += G) {
         const int n = min(G, end - p0);
@@ -183,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void spmm_seg_kernel(SpmmArgs a) {
         }
         int j = 0;
         for (; j + U <= n; j += U) {
-            VT b[U][NV];
+            RT b[U][NV];
             float v[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -192,19 +204,25 @@ __global__ __launch_bounds__(kBlock) void spmm_seg_kernel(SpmmArgs a) {
                 const char* src = Bb + (int64_t)c * ldb_bytes;   // G == 64: scalar base
 #pragma unroll
                 for (int k = 0; k < NV; k++)
-                    b[u][k] = *reinterpret_cast<const VT*>(src + loff[k]);
+                    b[u][k] = hraw<VW>(reinterpret_cast<const BT*>(src + loff[k]));
             }
 #pragma unroll
             for (int u = 0; u < U; u++)
 #pragma unroll
-                for (int k = 0; k < NV; k++) acc[k] += v[u] * b[u][k];
+                for (int k = 0; k < NV; k++) {
+                    if constexpr (kB16 && VW > 1) { hpin<BT, VW>(b[u][k]); acc[k] = vfma<VW>(v[u], hwiden<VW>(b[u][k]), acc[k]); }
+                    else acc[k] += v[u] * hwiden<VW>(b[u][k]);
+                }
         }
         for (; j < n; j++) {
             const int c = bcast_i<G>(mycol, j);
             const float v = bcast_f<G>(myval, j);
             const char* src = Bb + (int64_t)c * ldb_bytes;
 #pragma unroll
-            for (int k = 0; k < NV; k++) acc[k] += v * *reinterpret_cast<const VT*>(src + loff[k]);
+            for (int k = 0; k < NV; k++) {
+                if constexpr (kB16 && VW > 1) acc[k] = vfma<VW>(v, hload<VW>(reinterpret_cast<const BT*>(src + loff[k])), acc[k]);
+                else acc[k] += v * hload<VW>(reinterpret_cast<const BT*>(src + loff[k]));
+            }
         }
     }
 
@@ -239,34 +257,34 @@ __global__ __launch_bounds__(kBlock) void spmm_fix_kernel(SpmmArgs a, const sgcn
     epilogue_store<VW>(a, fx.row, vi, acc, rs);
 }
 
-template <int G, int NV, int VW, int U>
+template <int G, int NV, int VW, int U, class BT>
 static void launch_seg(const SpmmArgs& a, int64_t nblocks, hipStream_t st) {
-    hipLaunchKernelGGL((spmm_seg_kernel<G, NV, VW, U>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL((spmm_seg_kernel<G, NV, VW, U, BT>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
 }
 
-template <int VW, int U>
+template <int VW, int U, class BT>
 static bool dispatch_gnv(int G, int NV, const SpmmArgs& a, int64_t nblocks, hipStream_t st) {
     switch (G) {
-        case 8: launch_seg<8, 1, VW, U>(a, nblocks, st); return true;
-        case 16: launch_seg<16, 1, VW, U>(a, nblocks, st); return true;
-        case 32: launch_seg<32, 1, VW, U>(a, nblocks, st); return true;
+        case 8: launch_seg<8, 1, VW, U, BT>(a, nblocks, st); return true;
+        case 16: launch_seg<16, 1, VW, U, BT>(a, nblocks, st); return true;
+        case 32: launch_seg<32, 1, VW, U, BT>(a, nblocks, st); return true;
         case 64:
             switch (NV) {
-                case 1: launch_seg<64, 1, VW, U>(a, nblocks, st); return true;
-                case 2: launch_seg<64, 2, VW, U>(a, nblocks, st); return true;
-                case 3: launch_seg<64, 3, VW, U>(a, nblocks, st); return true;
-                case 4: launch_seg<64, 4, VW, U>(a, nblocks, st); return true;
+                case 1: launch_seg<64, 1, VW, U, BT>(a, nblocks, st); return true;
+                case 2: launch_seg<64, 2, VW, U, BT>(a, nblocks, st); return true;
+                case 3: launch_seg<64, 3, VW, U, BT>(a, nblocks, st); return true;
+                case 4: launch_seg<64, 4, VW, U, BT>(a, nblocks, st); return true;
             }
     }
     return false;
 }
 
-template <int VW>
+template <int VW, class BT>
 static bool dispatch_u(int U, int G, int NV, const SpmmArgs& a, int64_t nblocks, hipStream_t st) {
     switch (U) {
-        case 2: return dispatch_gnv<VW, 2>(G, NV, a, nblocks, st);
-        case 4: return dispatch_gnv<VW, 4>(G, NV, a, nblocks, st);
-        case 8: return dispatch_gnv<VW, 8>(G, NV, a, nblocks, st);
+        case 2: return dispatch_gnv<VW, 2, BT>(G, NV, a, nblocks, st);
+        case 4: return dispatch_gnv<VW, 4, BT>(G, NV, a, nblocks, st);
+        case 8: return dispatch_gnv<VW, 8, BT>(G, NV, a, nblocks, st);
     }
     return false;
 }
@@ -313,30 +331,25 @@ extern "C" int sgcn_tune(const char* key, int64_t value) {
     return fail(SGCN_ERR_INVALID, "sgcn_tune: unknown key '%s'", key);
 }
 
-extern "C" int sgcn_spmm_csr_add_f32(const int32_t* rowptr, const int32_t* col, const float* val,
-                                     int32_t M, int32_t K, int32_t d, const float* B, int64_t ldb,
-                                     const int32_t* gidx, const float* rscale, const float* cscale,
-                                     float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
-                                     const float* add, int64_t ldadd, int32_t add_rows, void* stream);
-
-extern "C" int sgcn_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
-                                 int32_t M, int32_t K, int32_t d, const float* B, int64_t ldb,
-                                 const int32_t* gidx, const float* rscale, const float* cscale,
-                                 float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
-                                 void* stream) {
-    return sgcn_spmm_csr_add_f32(rowptr, col, val, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, plan,
-                                 nullptr, 0, 0, stream);
-}
-
-extern "C" int sgcn_spmm_csr_add_f32(const int32_t* rowptr, const int32_t* col, const float* val,
-                                     int32_t M, int32_t K, int32_t d, const float* B, int64_t ldb,
-                                     const int32_t* gidx, const float* rscale, const float* cscale,
-                                     float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
-                                     const float* add, int64_t ldadd, int32_t add_rows, void* stream) {
+// BT = float: sgcn_spmm_csr_add_f32.  BT = uint16_t: sgcn_spmm_csr_add_b16 -- the operand is K x ldb uint16 (ldb in ELEMENTS,
+// a multiple of 8, base 16-byte aligned), which never limits the vector width: VW, G, NV and U are what the fp32 call
+// picks for a 16-byte aligned fp32 table of the same element pitch (the table's pointer is left out of pick_vw, its pitch
+// is not), and every sum is taken in that call's order.
+template <class BT>
+static int spmm_csr_add(const int32_t* rowptr, const int32_t* col, const float* val,
+                        int32_t M, int32_t K, int32_t d, const BT* B, int64_t ldb,
+                        const int32_t* gidx, const float* rscale, const float* cscale,
+                        float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
+                        const float* add, int64_t ldadd, int32_t add_rows, void* stream) {
+    constexpr bool kB16 = !std::is_same<BT, float>::value;
     SGCN_REQUIRE(M >= 0 && K >= 0 && d >= 0, "spmm: negative size");
     if (M == 0 || d == 0) return SGCN_OK;
     SGCN_REQUIRE(rowptr && C && (B || K == 0), "spmm: null operand");
     SGCN_REQUIRE(ldb >= d && ldc >= d, "spmm: leading dimension smaller than d");
+    if (kB16) {
+        SGCN_REQUIRE(ldb % 8 == 0, "spmm: a bfloat16 operand needs ldb %% 8 == 0 (ldb %lld, d %d)", (long long)ldb, d);
+        SGCN_REQUIRE(aligned16(B), "spmm: a bfloat16 operand needs a 16-byte aligned base");
+    }
     hipStream_t st = (hipStream_t)stream;
 
     SpmmArgs a{};
@@ -360,7 +373,8 @@ extern "C" int sgcn_spmm_csr_add_f32(const int32_t* rowptr, const int32_t* col, 
                          (long long)(plan->nslots * a.ldw));
         }
     }
-    const int vw = pick_vw(d, {B, C, plan ? plan->dev_ws : nullptr, a.add}, {ldb, ldc, a.add ? a.ldadd : ldc});
+    const int vw = pick_vw(d, {kB16 ? nullptr : (const void*)B, C, plan ? plan->dev_ws : nullptr, a.add},
+                           {ldb, ldc, a.add ? a.ldadd : ldc});
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
     int NV = 1;
@@ -377,9 +391,9 @@ extern "C" int sgcn_spmm_csr_add_f32(const int32_t* rowptr, const int32_t* col, 
     SGCN_REQUIRE(nblocks < (1ll << 31), "spmm: grid too large");
 
     bool ok = false;
-    if (vw == 4) ok = dispatch_u<4>(U, G, NV, a, nblocks, st);
-    else if (vw == 2) ok = dispatch_u<2>(U, G, NV, a, nblocks, st);
-    else ok = dispatch_u<1>(U, G, NV, a, nblocks, st);
+    if (vw == 4) ok = dispatch_u<4, BT>(U, G, NV, a, nblocks, st);
+    else if (vw == 2) ok = dispatch_u<2, BT>(U, G, NV, a, nblocks, st);
+    else ok = dispatch_u<1, BT>(U, G, NV, a, nblocks, st);
     SGCN_REQUIRE(ok, "spmm: no kernel for G=%d NV=%d U=%d", G, NV, U);
     SGCN_HIP_TRY(hipGetLastError());
 
@@ -393,4 +407,42 @@ extern "C" int sgcn_spmm_csr_add_f32(const int32_t* rowptr, const int32_t* col, 
         SGCN_HIP_TRY(hipGetLastError());
     }
     return SGCN_OK;
+}
+
+extern "C" int sgcn_spmm_csr_add_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                                     int32_t M, int32_t K, int32_t d, const float* B, int64_t ldb,
+                                     const int32_t* gidx, const float* rscale, const float* cscale,
+                                     float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
+                                     const float* add, int64_t ldadd, int32_t add_rows, void* stream) {
+    return spmm_csr_add<float>(rowptr, col, val, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, plan,
+                               add, ldadd, add_rows, stream);
+}
+
+extern "C" int sgcn_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                                 int32_t M, int32_t K, int32_t d, const float* B, int64_t ldb,
+                                 const int32_t* gidx, const float* rscale, const float* cscale,
+                                 float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
+                                 void* stream) {
+    return spmm_csr_add<float>(rowptr, col, val, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, plan,
+                               nullptr, 0, 0, stream);
+}
+
+/* mirrors sgcn_spmm_csr_add_f32 on a bfloat16 operand */
+extern "C" int sgcn_spmm_csr_add_b16(const int32_t* rowptr, const int32_t* col, const float* val,
+                                     int32_t M, int32_t K, int32_t d, const uint16_t* B, int64_t ldb,
+                                     const int32_t* gidx, const float* rscale, const float* cscale,
+                                     float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
+                                     const float* add, int64_t ldadd, int32_t add_rows, void* stream) {
+    return spmm_csr_add<uint16_t>(rowptr, col, val, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, plan,
+                                  add, ldadd, add_rows, stream);
+}
+
+/* mirrors sgcn_spmm_csr_f32 on a bfloat16 operand */
+extern "C" int sgcn_spmm_csr_b16(const int32_t* rowptr, const int32_t* col, const float* val,
+                                 int32_t M, int32_t K, int32_t d, const uint16_t* B, int64_t ldb,
+                                 const int32_t* gidx, const float* rscale, const float* cscale,
+                                 float* C, int64_t ldc, float beta, const sgcn_plan_t* plan,
+                                 void* stream) {
+    return spmm_csr_add<uint16_t>(rowptr, col, val, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, plan,
+                                  nullptr, 0, 0, stream);
 }

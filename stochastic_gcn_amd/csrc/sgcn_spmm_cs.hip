@@ -47,7 +47,7 @@ struct CsArgs {
     const int32_t* tile_rows;
     const int32_t* tile_slots;
     int64_t tile_base, tile_end;
-    const float* B; int64_t ldb;
+    const void* B; int64_t ldb;   // fp32, or uint16 for a bfloat16 operand (sgcn_spmm_cs_b16: the kernels' BT); ldb in elements
     const int32_t* gidx; const float* rscale; const float* cscale;
     float* C; int64_t ldc; float beta;
     int32_t d, nvec, slab;
@@ -105,9 +105,18 @@ __device__ __forceinline__ void static_for(F&& f) {
 // EXTRA every lane carries one more fp32 column next to its float4 -- a slab is 64 float4 + up to
 // 64 floats = up to 320 columns -- and d = 602 (pitch 608) is covered by TWO passes of 304.
 // Planes: x,y,z,w (+ e) of 16 registers each at v[64:127] (v[48:127] with EXTRA).
-template <int U, bool EXTRA, bool WARP = false>
+//
+// BT (all three sweep kernels): the dense operand's element -- float, or uint16_t for a bfloat16 table.  The bf16 forms
+// gather 8 bytes per lane instead of 16 (2 for the extra column), take their byte offsets from ldb * 2, keep the raw dwords
+// in the register buffers (hpin: the widening must not move up to the load, where every request would be followed by its
+// wait) and widen -- bits << 16, exact -- right in front of the FMA group.  Lanes, passes, accumulators, pad masks, pacing
+// and epilogues are the fp32 form's, and the FMAs are the same instructions: the same bits as the fp32 form on the widened table.
+template <int U, bool EXTRA, bool WARP = false, class BT = float>
 __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
     typedef Vec<4>::type VT;
+    typedef typename HRaw<BT, 4>::type RT;
+    typedef typename HRaw<BT, 1>::type RT1;
+    constexpr uint32_t kEsz = (uint32_t)sizeof(BT);
     constexpr int kShift = 28;
     constexpr uint32_t kColMask = (1u << kShift) - 1u;
     const int lane = threadIdx.x & 63;
@@ -119,10 +128,10 @@ __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
     const int fe = fbase + 256 + lane;                           // my extra column
     const bool acte = EXTRA && lane < a.slab_floats - 256 && fe < a.d;
     // inactive lanes re-read a valid address of the row instead of branching around the load
-    const uint32_t off4 = (uint32_t)(act4 ? f4 : fbase) * 4u;
-    const uint32_t offe = (uint32_t)(acte ? fe : fbase) * 4u;
+    const uint32_t off4 = (uint32_t)(act4 ? f4 : fbase) * kEsz;
+    const uint32_t offe = (uint32_t)(acte ? fe : fbase) * kEsz;
     const char* Bb = reinterpret_cast<const char*>(a.B);
-    const int64_t ldb_bytes = a.ldb * 4;
+    const int64_t ldb_bytes = a.ldb * kEsz;
 
     typedef float accv_t __attribute__((ext_vector_type(16)));
     accv_t ax = {}, ay = {}, az = {}, aw = {}, ae = {};
@@ -196,14 +205,14 @@ __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
                     allowed = (float)(__builtin_amdgcn_s_memrealtime() - t0) * a.cols_per_tick + a.slack_cols;
                 }
             }
-            VT bb[U];
-            float be[U];
+            RT bb[U];
+            RT1 be[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const uint32_t cr = (uint32_t)__builtin_amdgcn_readlane((int)mycr, jj + u);
                 const char* src = Bb + (int64_t)(cr & kColMask) * ldb_bytes;
-                bb[u] = *reinterpret_cast<const VT*>(src + off4);
-                be[u] = EXTRA ? *reinterpret_cast<const float*>(src + offe) : 0.f;
+                bb[u] = hraw<4>(reinterpret_cast<const BT*>(src + off4));
+                if constexpr (EXTRA) be[u] = hraw<1>(reinterpret_cast<const BT*>(src + offe)); else be[u] = hraw_zero<BT, 1>();
             }
             if (a.cols_per_tick > 0.f) tnow = __builtin_amdgcn_s_memrealtime();
             if constexpr (WARP) {
@@ -214,15 +223,18 @@ __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
             for (int u = 0; u < U; u++) {
                 const uint32_t cr = (uint32_t)__builtin_amdgcn_readlane((int)mycr, jj + u);
                 const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myv), jj + u));
-                apply(cr, v, bb[u], be[u]);
+                hpin<BT, 4>(bb[u]);
+                if constexpr (EXTRA) hpin<BT, 4>(be[u]);
+                apply(cr, v, hwiden<4>(bb[u]), hwiden<1>(be[u]));
             }
         }
         for (int j = nb * U; j < n; j++) {
             const uint32_t cr = (uint32_t)__builtin_amdgcn_readlane((int)mycr, j);
             const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myv), j));
             const char* src = Bb + (int64_t)(cr & kColMask) * ldb_bytes;
-            const VT b = *reinterpret_cast<const VT*>(src + off4);
-            const float e1 = EXTRA ? *reinterpret_cast<const float*>(src + offe) : 0.f;
+            const VT b = hload<4>(reinterpret_cast<const BT*>(src + off4));
+            float e1 = 0.f;
+            if constexpr (EXTRA) e1 = hload<1>(reinterpret_cast<const BT*>(src + offe));
             apply(cr, v, b, e1);
         }
     }
@@ -282,9 +294,11 @@ __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
 //  * the clock comparison is integer scalar arithmetic.
 // Requires every tile's entry count to be a multiple of 64 (the plan pads to that).  WIDE: K >= 2^24 or B beyond 4 GiB
 // -- 64-bit row offsets.
-template <int U, bool WIDE, bool WARP = false>
+template <int U, bool WIDE, bool WARP = false, class BT = float>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void cs_spmm16g2k_kernel(CsArgs a) {
     typedef Vec<4>::type VT;
+    typedef typename HRaw<BT, 4>::type RT;
+    constexpr uint32_t kEsz = (uint32_t)sizeof(BT);
     constexpr int kShift = 28;
     constexpr uint32_t kColMask = (1u << kShift) - 1u;
     constexpr int kSteps = kWave / 2;                 // steps per chunk of 64 entries
@@ -299,9 +313,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const int fbase = a.slab * 128;
     const int f4 = fbase + li * 4;
     const bool act = f4 < a.d;
-    const uint32_t off4 = (uint32_t)(act ? f4 : fbase) * 4u;
+    const uint32_t off4 = (uint32_t)(act ? f4 : fbase) * kEsz;
     const char* Bb = reinterpret_cast<const char*>(a.B);
-    const uint32_t ldb32 = (uint32_t)(a.ldb * 4);
+    const uint32_t ldb32 = (uint32_t)(a.ldb * kEsz);
     const int sel0 = hi ? 4 : 0;                      // ds_bpermute byte address of entry (2 j + bin) is sel0 + 8 j
 
     // row r of a bin: (x, y) = axy[2 r], axy[2 r + 1] and (z, w) = azw[2 r], azw[2 r + 1] -- adjacent, even-aligned register
@@ -374,13 +388,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             }
         }
     };
-    auto gather = [&](uint32_t crs, int j) -> VT {
+    auto gather = [&](uint32_t crs, int j) -> RT {
         const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute(sel0 + 8 * j, (int)crs);   // my bin's column word
         if constexpr (WIDE) {
-            return *reinterpret_cast<const VT*>(Bb + (uint64_t)(c & kColMask) * ldb32 + off4);
+            return hraw<4>(reinterpret_cast<const BT*>(Bb + (uint64_t)(c & kColMask) * ldb32 + off4));
         } else {                                       // u24 multiply: the row id above bit 24 is ignored by the instruction
             const uint32_t off = __umul24(c, ldb32) + off4;
-            return *reinterpret_cast<const VT*>(Bb + off);
+            return hraw<4>(reinterpret_cast<const BT*>(Bb + off));
         }
     };
     // step j of the chunk (compile-time j).  The two values come down by v_readlane into FIXED scalar pairs (the packed
@@ -423,7 +437,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     entries(start, ccr, cv);
     entries(start + kWave, ncr, nv);
     Meta cm = meta(ccr, cv);
-    VT buf[2][U];
+    RT buf[2][U];                                   // raw dwords: a bf16 operand is widened when it is applied
     uint32_t pnext = 0;                             // WARP: position of the next batch's first column
     if constexpr (WARP) { if (cpt16 != 0) pace_at(wpos(ccr, 0)); } else pace(ccr, 0);
 #pragma unroll
@@ -453,7 +467,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             // ... while batch k is applied
             static_for<U>([&](auto uc) {
                 constexpr int u = decltype(uc)::value;
-                fma2(cm, cv, std::integral_constant<int, k * U + u>{}, buf[k & 1][u]);
+                hpin<BT, 4>(buf[k & 1][u]);
+                fma2(cm, cv, std::integral_constant<int, k * U + u>{}, hwiden<4>(buf[k & 1][u]));
             });
         });
         ccr = ncr; cv = nv;
@@ -495,9 +510,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 // passes.  Same structure as cs_spmm16g2k_kernel otherwise (entry l of a chunk: step l / 4, bin l % 4; the accumulator
 // offsets of a step are the four bytes of ONE scalar).  The unpacked round-2 form of this kernel was instruction-bound at
 // 4.4 ms (profiles/HISTORY.md 3.1b).
-template <int U, bool WIDE, bool WARP = false>
+template <int U, bool WIDE, bool WARP = false, class BT = float>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void cs_spmm16g4k_kernel(CsArgs a) {
     typedef Vec<4>::type VT;
+    typedef typename HRaw<BT, 4>::type RT;
+    constexpr uint32_t kEsz = (uint32_t)sizeof(BT);
     constexpr int kShift = 28;
     constexpr uint32_t kColMask = (1u << kShift) - 1u;
     constexpr int kSteps = kWave / 4;                 // steps per chunk of 64 entries
@@ -512,9 +529,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const int fbase = a.slab * 64;
     const int f4 = fbase + li * 4;
     const bool act = f4 < a.d;
-    const uint32_t off4 = (uint32_t)(act ? f4 : fbase) * 4u;
+    const uint32_t off4 = (uint32_t)(act ? f4 : fbase) * kEsz;
     const char* Bb = reinterpret_cast<const char*>(a.B);
-    const uint32_t ldb32 = (uint32_t)(a.ldb * 4);
+    const uint32_t ldb32 = (uint32_t)(a.ldb * kEsz);
     const int sel0 = bin * 4;                         // ds_bpermute byte address of entry (4 j + bin) is sel0 + 16 j
 
     typedef float accv_t __attribute__((ext_vector_type(32)));
@@ -582,13 +599,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             }
         }
     };
-    auto gather = [&](uint32_t crs, int j) -> VT {
+    auto gather = [&](uint32_t crs, int j) -> RT {
         const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute(sel0 + 16 * j, (int)crs);   // my bin's column word
         if constexpr (WIDE) {
-            return *reinterpret_cast<const VT*>(Bb + (uint64_t)(c & kColMask) * ldb32 + off4);
+            return hraw<4>(reinterpret_cast<const BT*>(Bb + (uint64_t)(c & kColMask) * ldb32 + off4));
         } else {
             const uint32_t off = __umul24(c, ldb32) + off4;
-            return *reinterpret_cast<const VT*>(Bb + off);
+            return hraw<4>(reinterpret_cast<const BT*>(Bb + off));
         }
     };
     // step j: 4 v_readlane (the values, into fixed scalar pairs), then per bin: pad test -> quarter mask, the bin's
@@ -642,7 +659,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     entries(start, ccr, cv);
     entries(start + kWave, ncr, nv);
     Meta cm = meta(ccr, cv);
-    VT buf[2][U];
+    RT buf[2][U];                                   // raw dwords: a bf16 operand is widened when it is applied
     uint32_t pnext = 0;                             // WARP: position of the next batch's first column
     if constexpr (WARP) { if (cpt16 != 0) pace_at(wpos(ccr, 0)); } else pace(ccr, 0);
 #pragma unroll
@@ -670,7 +687,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             }
             static_for<U>([&](auto uc) {
                 constexpr int u = decltype(uc)::value;
-                fma4(cm, cv, std::integral_constant<int, k * U + u>{}, buf[k & 1][u]);
+                hpin<BT, 4>(buf[k & 1][u]);
+                fma4(cm, cv, std::integral_constant<int, k * U + u>{}, hwiden<4>(buf[k & 1][u]));
             });
         });
         ccr = ncr; cv = nv;
@@ -779,6 +797,7 @@ namespace {
 // dimension, columns per pass, the fifth plane, gathers in flight -- and the kernel's name.
 struct CsVariant { int nslab, slab_floats, U; bool extra; const char* name; };
 
+// (the geometry does not depend on the operand's type: a bf16 product runs the passes of the fp32 one)
 CsVariant cs_variant(const sgcn_csplan_t* plan, int d) {
     CsVariant v{};
     if (plan->G == 4) {             // four lane groups per wave: 64-column passes, every row resident in one round
@@ -819,21 +838,36 @@ CsVariant cs_variant(const sgcn_csplan_t* plan, int d) {
 }
 }  // namespace
 
-extern "C" int sgcn_spmm_cs_variant(const sgcn_csplan_t* plan, int32_t d, char* buf, int32_t buflen) {
+static int cs_variant_text(const sgcn_csplan_t* plan, int32_t d, char* buf, int32_t buflen, bool b16) {
     SGCN_REQUIRE(plan && buf && buflen > 0 && d > 0, "spmm_cs_variant: bad argument");
     SGCN_REQUIRE(plan->R == 16 && (plan->G == 1 || plan->G == 2 || plan->G == 4 || plan->G == 0), "spmm_cs_variant: 16-row bins; one, two or four lane groups");
     const CsVariant v = cs_variant(plan, d);
     int64_t round = plan->round_tiles > 0 ? plan->round_tiles : (tune_get("cs_round") > 0 ? tune_get("cs_round") : 4096);
-    snprintf(buf, (size_t)buflen, "%s x %d launches (%d passes of %d columns x %lld rounds of %lld tiles)", v.name,
+    snprintf(buf, (size_t)buflen, "%s%s x %d launches (%d passes of %d columns x %lld rounds of %lld tiles)", v.name,
+             b16 ? " [bf16 operand]" : "",
              (int)(v.nslab * ((plan->ntiles + round - 1) / round)), v.nslab, v.slab_floats,
              (long long)((plan->ntiles + round - 1) / round), (long long)round);
     return SGCN_OK;
 }
 
-extern "C" int sgcn_spmm_cs_f32(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
-                                const float* B, int64_t ldb, const int32_t* gidx,
-                                const float* rscale, const float* cscale, float* C, int64_t ldc,
-                                float beta, void* stream) {
+extern "C" int sgcn_spmm_cs_variant(const sgcn_csplan_t* plan, int32_t d, char* buf, int32_t buflen) {
+    return cs_variant_text(plan, d, buf, buflen, false);
+}
+
+/* what sgcn_spmm_cs_b16 dispatches: the fp32 entry's kernel and geometry, instantiated for a bfloat16 operand */
+extern "C" int sgcn_spmm_cs_variant_b16(const sgcn_csplan_t* plan, int32_t d, char* buf, int32_t buflen) {
+    return cs_variant_text(plan, d, buf, buflen, true);
+}
+
+// BT = float: sgcn_spmm_cs_f32.  BT = uint16_t: sgcn_spmm_cs_b16 (K x ldb uint16, ldb in ELEMENTS and a multiple of 8, base
+// 16-byte aligned): the same plan, passes, rounds, clock and kernels, the row offsets in bytes of that table.
+template <class BT>
+static int spmm_cs(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
+                   const BT* B, int64_t ldb, const int32_t* gidx,
+                   const float* rscale, const float* cscale, float* C, int64_t ldc,
+                   float beta, void* stream) {
+    constexpr bool kB16 = !std::is_same<BT, float>::value;
+    constexpr int64_t kEsz = (int64_t)sizeof(BT);
     SGCN_REQUIRE(plan && M >= 0 && K >= 0 && d >= 0, "spmm_cs: bad argument");
     if (M == 0 || d == 0) return SGCN_OK;
     SGCN_REQUIRE(plan->R == 16 && (plan->G == 0 || plan->G == 1 || plan->G == 2 || plan->G == 4),
@@ -842,7 +876,12 @@ extern "C" int sgcn_spmm_cs_f32(const sgcn_csplan_t* plan, int32_t M, int32_t K,
                  "spmm_cs: null operand");
     SGCN_REQUIRE(K < (1 << 28), "spmm_cs: K too large for the packed column word");
     const int VW = 4;               // float4 per lane (16-byte aligned rows)
-    SGCN_REQUIRE(pick_vw(d, {B, C, plan->dev_ws}, {ldb, ldc}) >= VW,
+    if (kB16) {
+        SGCN_REQUIRE(ldb >= d && ldb % 8 == 0, "spmm_cs: a bfloat16 operand needs ldb >= d and ldb %% 8 == 0 (ldb %lld, d %d)",
+                     (long long)ldb, d);
+        SGCN_REQUIRE(aligned16(B), "spmm_cs: a bfloat16 operand needs a 16-byte aligned base");
+    }
+    SGCN_REQUIRE(pick_vw(d, {kB16 ? nullptr : (const void*)B, C, plan->dev_ws}, {ldb, ldc}) >= VW,
                  "spmm_cs: rows must be %d-byte aligned (pitch multiple of %d floats covering d)", VW * 4, VW);
     hipStream_t st = (hipStream_t)stream;
     CsArgs a{};
@@ -855,7 +894,7 @@ extern "C" int sgcn_spmm_cs_f32(const sgcn_csplan_t* plan, int32_t M, int32_t K,
     a.warp = tune_get("cs_nowarp") <= 0 && !gidx ? plan->dev_warp : nullptr;
     a.warp_shift = plan->warp_shift;
     SGCN_REQUIRE(!a.warp || (plan->warp_shift >= 0 && plan->warp_shift < 28), "spmm_cs: bad warp_shift");
-    SGCN_REQUIRE((plan->G != 2 && plan->G != 4) || ldb * 4 < (1ll << 32), "spmm_cs: row pitch of B must fit 32 bits");
+    SGCN_REQUIRE((plan->G != 2 && plan->G != 4) || ldb * kEsz < (1ll << 32), "spmm_cs: row pitch of B must fit 32 bits");
     if (plan->nfix > 0) {
         SGCN_REQUIRE(plan->dev_fix && plan->dev_ws && plan->ws_elems >= plan->nslots * a.ldw,
                      "spmm_cs: workspace missing or too small");
@@ -894,22 +933,22 @@ extern "C" int sgcn_spmm_cs_f32(const sgcn_csplan_t* plan, int32_t M, int32_t K,
 #define SGCN_CS16(UU, EE)                                                                                              \
             do {                                                                                                        \
                 if (a.warp != nullptr && a.cols_per_tick > 0.f)                                                         \
-                    hipLaunchKernelGGL((cs_spmm16_kernel<UU, EE, true>), dim3(blocks), dim3(kBlock), 0, st, a);         \
-                else hipLaunchKernelGGL((cs_spmm16_kernel<UU, EE, false>), dim3(blocks), dim3(kBlock), 0, st, a);       \
+                    hipLaunchKernelGGL((cs_spmm16_kernel<UU, EE, true, BT>), dim3(blocks), dim3(kBlock), 0, st, a);     \
+                else hipLaunchKernelGGL((cs_spmm16_kernel<UU, EE, false, BT>), dim3(blocks), dim3(kBlock), 0, st, a);   \
             } while (0)
             // the clock in work coordinates (plan->dev_warp): only a paced launch looks positions up
             const bool warp = a.warp != nullptr && a.cols_per_tick > 0.f;
 #define SGCN_CSG(KERNEL, WIDE_)                                                                                         \
             do {                                                                                                        \
-                if (warp) hipLaunchKernelGGL((KERNEL<4, WIDE_, true>), dim3(blocks), dim3(kBlock), 0, st, a);          \
-                else hipLaunchKernelGGL((KERNEL<4, WIDE_, false>), dim3(blocks), dim3(kBlock), 0, st, a);              \
+                if (warp) hipLaunchKernelGGL((KERNEL<4, WIDE_, true, BT>), dim3(blocks), dim3(kBlock), 0, st, a);      \
+                else hipLaunchKernelGGL((KERNEL<4, WIDE_, false, BT>), dim3(blocks), dim3(kBlock), 0, st, a);          \
             } while (0)
             if (plan->G == 4) {
-                const bool wide = K >= (1 << 24) || ldb * 4 >= (1 << 24) || (int64_t)K * ldb * 4 >= (1ll << 32) ||
+                const bool wide = K >= (1 << 24) || ldb * kEsz >= (1 << 24) || (int64_t)K * ldb * kEsz >= (1ll << 32) ||
                                   tune_get("cs_g2_wide") > 0;
                 if (wide) SGCN_CSG(cs_spmm16g4k_kernel, true); else SGCN_CSG(cs_spmm16g4k_kernel, false);
             } else if (plan->G == 2) {
-                const bool wide = K >= (1 << 24) || ldb * 4 >= (1 << 24) || (int64_t)K * ldb * 4 >= (1ll << 32) ||
+                const bool wide = K >= (1 << 24) || ldb * kEsz >= (1 << 24) || (int64_t)K * ldb * kEsz >= (1ll << 32) ||
                                   tune_get("cs_g2_wide") > 0;
                 if (wide) SGCN_CSG(cs_spmm16g2k_kernel, true); else SGCN_CSG(cs_spmm16g2k_kernel, false);
             } else {
@@ -929,4 +968,19 @@ extern "C" int sgcn_spmm_cs_f32(const sgcn_csplan_t* plan, int32_t M, int32_t K,
         SGCN_HIP_TRY(hipGetLastError());
     }
     return SGCN_OK;
+}
+
+extern "C" int sgcn_spmm_cs_f32(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
+                                const float* B, int64_t ldb, const int32_t* gidx,
+                                const float* rscale, const float* cscale, float* C, int64_t ldc,
+                                float beta, void* stream) {
+    return spmm_cs<float>(plan, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, stream);
+}
+
+/* mirrors sgcn_spmm_cs_f32 on a bfloat16 operand */
+extern "C" int sgcn_spmm_cs_b16(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
+                                const uint16_t* B, int64_t ldb, const int32_t* gidx,
+                                const float* rscale, const float* cscale, float* C, int64_t ldc,
+                                float beta, void* stream) {
+    return spmm_cs<uint16_t>(plan, M, K, d, B, ldb, gidx, rscale, cscale, C, ldc, beta, stream);
 }

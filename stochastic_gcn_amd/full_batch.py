@@ -8,7 +8,8 @@ two products).
 
   StaticMatrix   one adjacency with a plan built once, a lazily built transpose (ops.transpose_host) and the product
                  method PlainAggregator calls (``out=`` with a column-offset view, ``add=`` / ``add_rows=``);
-                 dispatches to ops.spmm / ops.spmm_cs / ops.spmm_lds
+                 dispatches to ops.spmm / ops.spmm_cs / ops.spmm_lds; with ``bf16`` (--full_batch_dtype bf16) every product
+                 rounds its dense operand into a bfloat16 scratch table and gathers from there (sgcn_spmm_*_b16)
   StaticBatch    what Model.upload / get_data accept in place of a PackedBatch: fields[l] = arange(N), unit scales,
                  the N x C label table, and ``rows`` -- the sorted subset of vertices the loss runs over
                  (ops.softmax_ce / sigmoid_ce ``rows=``)
@@ -20,6 +21,7 @@ from . import ops
 from .flags import FLAGS, _CHOICES
 
 KERNELS = _CHOICES['full_batch_kernel']
+DTYPES = _CHOICES['full_batch_dtype']
 
 
 def check_full_batch(flags=None, world=1):
@@ -27,6 +29,16 @@ def check_full_batch(flags=None, world=1):
     f = FLAGS if flags is None else flags
     if f.full_batch_kernel not in KERNELS:
         raise ValueError("--full_batch_kernel must be one of %s, got %r" % ('/'.join(KERNELS), f.full_batch_kernel))
+    dtype = getattr(f, 'full_batch_dtype', 'fp32')
+    if dtype not in DTYPES:
+        raise ValueError("--full_batch_dtype must be one of %s, got %r" % ('/'.join(DTYPES), dtype))
+    if dtype == 'bf16':
+        if not (f.full_batch or f.test_full_batch):
+            raise ValueError("--full_batch_dtype bf16 needs --full_batch or --test_full_batch: it is the storage type of the "
+                             "dense operand of the full-graph products, and no other mode runs them")
+        if f.full_batch_kernel == 'lds':
+            raise ValueError("--full_batch_dtype bf16 is not supported with --full_batch_kernel lds: the LDS-staged sweep "
+                             "stages fp32 pieces of the operand and has no bfloat16 form")
     if f.full_batch:
         for name, why in (('cv', 'exact propagation has no estimator and no history'),
                           ('cvd', 'exact propagation has no estimator and no history'),
@@ -49,6 +61,11 @@ def check_full_batch(flags=None, world=1):
     return bool(f.full_batch), bool(f.test_full_batch)
 
 
+def full_batch_bf16(flags=None):
+    """--full_batch_dtype as a bool (bfloat16 operand?)."""
+    return getattr(FLAGS if flags is None else flags, 'full_batch_dtype', 'fp32') == 'bf16'
+
+
 def _aligned(t):
     """Rows of a 2-D fp32 view on 16-byte boundaries (what the sweep kernels' float4 accesses need)."""
     return t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % 4 == 0)
@@ -59,10 +76,20 @@ class StaticMatrix(object):
     DeviceCSR), 'cs' (column sweep) or 'lds' (LDS-staged sweep + residual), or 'auto': train.static_kernel_for(nnz, d,
     products) with ``products`` the number of times the plan will run -- and for a large graph with communities
     ops.LdsSweepCSR.for_graph, exactly as train.pp_products chooses.  ``d`` is the operand width the choice (and the
-    column sweep's lane grouping) is made for."""
+    column sweep's lane grouping) is made for.
 
-    def __init__(self, a, device, kernel='auto', products=1, d=128, cache_path=None, _transpose_of=None):
+    ``bf16``: every product rounds ``x`` to nearest even into a bfloat16 scratch table -- one per operand width, allocated
+    once and reused every epoch -- and runs the kernel's bfloat16-operand form: half the operand's bytes per nonzero, the
+    sums and ``out`` fp32, bit for bit the fp32 product of the rounded operand.  The transpose inherits it.  The LDS sweep
+    has no such form: forcing it is refused, 'auto' never picks it."""
+
+    bf16 = False          # (the fp32 operand is the default of every instance)
+
+    def __init__(self, a, device, kernel='auto', products=1, d=128, cache_path=None, _transpose_of=None, bf16=False):
         a = a.tocsr()
+        self.bf16, self._scratch = bool(bf16), {}
+        if self.bf16 and kernel == 'lds':
+            raise ValueError("the LDS-staged sweep has no bfloat16-operand form")
         self.a, self.device, self.shape, self.nnz = a, device, (int(a.shape[0]), int(a.shape[1])), int(a.nnz)
         self.requested, self.products, self.d_hint, self.cache_path = kernel, int(products), int(d), cache_path
         self._transpose = _transpose_of
@@ -83,7 +110,7 @@ class StaticMatrix(object):
             from . import train            # (late: train imports this module)
             if train.static_kernel_for(self.nnz, d, self.products) == 'rows':
                 return 'rows'
-            if self.cache_path is None and self.nnz >= 2000000 and d >= 128:
+            if self.cache_path is None and self.nnz >= 2000000 and d >= 128 and not self.bf16:
                 self._plan = ops.LdsSweepCSR.for_graph(a, self.device)
                 if self._plan is not None:
                     return 'lds'
@@ -98,7 +125,7 @@ class StaticMatrix(object):
             path = self.cache_path[:-4] + ".T.npz" if self.cache_path else None
             self._transpose = StaticMatrix(ops.transpose_host(self.a), self.device, self.requested if self.requested != 'auto'
                                            else ('rows' if self.kernel == 'rows' else 'auto'), self.products, self.d_hint,
-                                           path, _transpose_of=self)
+                                           path, _transpose_of=self, bf16=self.bf16)
         return self._transpose
 
     @property
@@ -115,17 +142,31 @@ class StaticMatrix(object):
             r = self._plan.residual
             if isinstance(r, ops.ColumnSweepCSR) and d not in r.pace:
                 self._plan.autotune(x, d=d)
-        elif d not in self._plan.pace:
-            self._plan.autotune(x, d=d)                # once per plan and width; stored with a cached plan
+        elif d not in self._plan._st(x.dtype == torch.bfloat16)[0]:
+            self._plan.autotune(x, d=d)                # once per plan, width and operand type; stored with a cached plan
             self._plan.store_if_cached()
+
+    def operand(self, x):
+        """What the kernel gathers from: ``x`` itself, or under ``bf16`` this matrix's scratch table of x's width holding
+        x rounded to nearest even (ops.operand_round: sgcn_scatter_rows_h16 with no index)."""
+        if not self.bf16:
+            return x
+        n, d = int(x.shape[0]), int(x.shape[1])
+        if n != self.shape[1]:
+            raise ValueError("the operand has %d rows, the matrix %d columns" % (n, self.shape[1]))
+        tab = self._scratch.get(d)
+        if tab is None:
+            tab = self._scratch[d] = ops.history_alloc(n, d, x.device, bf16=True)
+        return ops.operand_round(x, out=tab)
 
     def kernel_for(self, x, out=None):
         """The kernel one product runs on: the matrix's own, or the row kernel where an operand's rows are not 16-byte
-        aligned (a width that is not a multiple of 4: no copy is made for the sweep's sake)."""
+        aligned (a width that is not a multiple of 4: no copy is made for the sweep's sake).  Under ``bf16`` the kernel
+        reads the scratch table, which is always aligned: only the width and ``out`` decide."""
         if self.kernel == 'rows':
             return 'rows'
         d = int(x.shape[1])
-        if d % 4 or not _aligned(x) or (out is not None and not _aligned(out)):
+        if d % 4 or (not self.bf16 and not _aligned(x)) or (out is not None and not _aligned(out)):
             return 'rows'
         return self.kernel
 
@@ -134,6 +175,7 @@ class StaticMatrix(object):
         sweep kernels have no epilogue addend: the addend is stored into ``out`` and the product runs with beta = 1."""
         M, d = self.shape[0], int(x.shape[1])
         k = self.kernel_for(x, out)
+        x = self.operand(x)
         if k == 'rows':
             return ops.spmm(self.rows_csr, x, out=out, add=add, add_rows=add_rows)
         if out is None:

@@ -72,10 +72,13 @@ def _rows2d(t, name):
 
 
 def _hist2d(t, name):
-    """(ptr, ld, bf16?) of a history table: fp32, or bfloat16 (--history_dtype bf16; ld in elements, the layout
-    include/sgcn.h asks for is checked by the library)."""
+    """(ptr, ld, bf16?) of a table that may be stored as bfloat16 -- a history (--history_dtype bf16) or the dense operand of
+    a static-graph product (--full_batch_dtype bf16): fp32, or bfloat16 with ld in elements (the layout include/sgcn.h
+    asks for is checked by the library)."""
     if t.dtype == torch.float32:
         return _rows2d(t, name) + (False,)
+    if t.dtype != torch.bfloat16:
+        raise TypeError("%s must be torch.float32 or torch.bfloat16, got %s" % (name, t.dtype))
     _dev(t, torch.bfloat16, name)
     if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise ValueError("%s must be 2-D with unit column stride" % name)
@@ -188,9 +191,11 @@ class DeviceCSR(object):
 
 def spmm(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=None, add=None, add_rows=0):
     """out[M x d] = rscale (.) (A (cscale (.) B[gidx])) + beta * out   (sgcn_spmm_csr_f32);
-    with ``add``: out[i] += add[i] for i < add_rows in the same launch (sgcn_spmm_csr_add_f32)."""
+    with ``add``: out[i] += add[i] for i < add_rows in the same launch (sgcn_spmm_csr_add_f32).  A bfloat16 ``B`` (a table
+    of ``history_alloc(..., bf16=True)``'s layout) goes to sgcn_spmm_csr_b16 / _add_b16: half the operand's bytes, the bits
+    of the fp32 product of the widened table; ``out`` stays fp32."""
     M, K = A.shape
-    bptr, ldb = _rows2d(B, "B")
+    bptr, ldb, b16 = _hist2d(B, "B")
     d = int(B.shape[1] if d is None else d)
     if out is None:
         if beta != 0.0:
@@ -205,13 +210,13 @@ def spmm(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=None, 
     plan = A.plan.struct(d) if A.plan is not None else None
     if add is not None:
         aptr, ldadd = _rows2d(add, "add")
-        check(lib.sgcn_spmm_csr_add_f32(
+        check((lib.sgcn_spmm_csr_add_b16 if b16 else lib.sgcn_spmm_csr_add_f32)(
             A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), M, K, d, bptr, ldb,
             _ptr(_dev(gidx, torch.int32, "gidx")), _ptr(_dev(rscale, torch.float32, "rscale")),
             _ptr(_dev(cscale, torch.float32, "cscale")), cptr, ldc, float(beta),
             C.byref(plan) if plan is not None else None, aptr, ldadd, int(add_rows), _stream()))
         return out
-    check(lib.sgcn_spmm_csr_f32(
+    check((lib.sgcn_spmm_csr_b16 if b16 else lib.sgcn_spmm_csr_f32)(
         A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), M, K, d, bptr, ldb,
         _ptr(_dev(gidx, torch.int32, "gidx")), _ptr(_dev(rscale, torch.float32, "rscale")),
         _ptr(_dev(cscale, torch.float32, "cscale")), cptr, ldc, float(beta),
@@ -331,6 +336,17 @@ def history_assign(H, src):
     if src.shape[0] > 1 and (src.stride(1) != 1):
         src = src.contiguous()
     return scatter_rows(H, None, src)
+
+
+def operand_round(x, out=None):
+    """``x`` (fp32 rows) rounded to nearest even into a bfloat16 operand table for ``spmm`` / ``spmm_cs``
+    (sgcn_scatter_rows_h16 with no index: the one rounding kernel).  ``out``: a table of ``history_alloc(n, d, device,
+    bf16=True)`` to reuse."""
+    if out is None:
+        out = history_alloc(int(x.shape[0]), int(x.shape[1]), x.device, bf16=True)
+    if tuple(out.shape) != tuple(x.shape):
+        raise ValueError("operand_round: out has shape %s, x %s" % (tuple(out.shape), tuple(x.shape)))
+    return history_assign(out, x)
 
 
 def csr_slice(A, rows_host, rows_dev=None, with_coo_rows=False):
@@ -561,6 +577,20 @@ class ColumnSweepCSR(object):
     WARP_BUCKETS = 16384      # the warp table's size bound (64 KiB: scalar cache / L2 resident)
     WARP_AUTO_DEV = 0.01      # 'auto': a table is kept when some column's share of the work in front of it is off its
                               # share of the ids by more than this (1 % of the sweep ~ a third of an L2 window)
+
+    # The sweep clock of a plan is tuned per width AND operand type: a bfloat16 operand moves half the bytes per step and holds
+    # the lock-step on a different clock.  ``pace`` / ``tuned_ms`` / ``_guard`` are the fp32 operand's; the bfloat16 operand's
+    # live beside them (``pace_b16`` ...) and never mix with them -- in struct(), the autotuner, the lost-lock guard and the
+    # plan cache.
+    def _st(self, bf16=False):
+        """(pace, tuned_ms, guard) of the operand type."""
+        if not bf16:
+            return self.pace, self.tuned_ms, self._guard
+        return self.__dict__.setdefault('_b16', ({}, {}, {}))
+
+    pace_b16 = property(lambda self: self._st(True)[0])
+    tuned_ms_b16 = property(lambda self: self._st(True)[1])
+    _guard_b16 = property(lambda self: self._st(True)[2])
 
     @classmethod
     def make_warp(cls, cols, K, mode='auto'):
@@ -941,7 +971,11 @@ class ColumnSweepCSR(object):
                     tuned_ms=np.array([[d, self.tuned_ms[d]] for d in sorted(self.pace) if d in self.tuned_ms],
                                       np.float64).reshape(-1, 2),
                     warp=t(self.warp) if getattr(self, 'warp', None) is not None else np.zeros(0, np.int32),
-                    warp_shift=int(getattr(self, 'warp_shift', 0)))
+                    warp_shift=int(getattr(self, 'warp_shift', 0)),
+                    # the bfloat16 operand's clocks, under keys of their own: a build without them reads the rest unchanged
+                    pace_b16=np.array([[d, p] for d, p in sorted(self.pace_b16.items())], np.int64).reshape(-1, 2),
+                    tuned_ms_b16=np.array([[d, self.tuned_ms_b16[d]] for d in sorted(self.pace_b16) if d in self.tuned_ms_b16],
+                                          np.float64).reshape(-1, 2))
         import os
         import tempfile
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
@@ -994,6 +1028,10 @@ class ColumnSweepCSR(object):
         tuned = {int(d): float(ms) for d, ms in z["tuned_ms"]} if "tuned_ms" in z.files else {}
         self.pace = {int(d): int(p) for d, p in z["pace"] if int(d) in tuned or int(p) <= 0}
         self.tuned_ms, self._guard, self._tuning = {d: ms for d, ms in tuned.items() if d in self.pace}, {}, False
+        # (a file of a build without the bfloat16 operand has neither key: empty bf16 state)
+        tuned16 = {int(d): float(ms) for d, ms in z["tuned_ms_b16"]} if "tuned_ms_b16" in z.files else {}
+        pace16 = {int(d): int(p) for d, p in z["pace_b16"] if int(d) in tuned16 or int(p) <= 0} if "pace_b16" in z.files else {}
+        self._b16 = (pace16, {d: ms for d, ms in tuned16.items() if d in pace16}, {})
         to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)          # noqa: E731
         self.tile_ptr, self.colrow, self.val = to(tile_ptr), to(z["colrow"]), to(z["val"])
         self.tile_rows, self.tile_slots = to(z["tile_rows"]), to(z["tile_slots"])
@@ -1029,7 +1067,8 @@ class ColumnSweepCSR(object):
             except OSError:           # read-only dataset directory: the cache is an optimisation only
                 pass
 
-    def struct(self, d):
+    def struct(self, d, bf16=False):
+        """The C struct for a product of width d; ``bf16``: with the clock tuned for a bfloat16 operand."""
         ldw = (d + 3) // 4 * 4
         need = self.nslots * ldw
         if need and (self.ws is None or self.ws.numel() < need):
@@ -1045,21 +1084,22 @@ class ColumnSweepCSR(object):
                            self.val.data_ptr(), self.tile_rows.data_ptr(), self.tile_slots.data_ptr(),
                            _ptr(self.fix), self.nfix, self.nslots, _ptr(self.ws),
                            0 if self.ws is None else self.ws.numel(), rnd, self._hint.ctypes.data,
-                           -1 if self.grouped else int(self.pace.get(d, 0)), int(getattr(self, 'G', 1)),
+                           -1 if self.grouped else int(self._st(bf16)[0].get(d, 0)), int(getattr(self, 'G', 1)),
                            1 if (self.grouped or getattr(self, 'ranged', 0)) else 0, _ptr(getattr(self, 'warp', None)),
                            int(getattr(self, 'warp_shift', 0)))
 
-    def variant(self, d):
-        """The kernel variant / launch geometry sgcn_spmm_cs_f32 uses for this plan and width."""
+    def variant(self, d, bf16=False):
+        """The kernel variant / launch geometry sgcn_spmm_cs_f32 (``bf16``: sgcn_spmm_cs_b16) uses for this plan and width."""
         buf = C.create_string_buffer(256)
-        plan = self.struct(d)
-        check(lib.sgcn_spmm_cs_variant(C.byref(plan), int(d), buf, 256))
+        plan = self.struct(d, bf16)
+        check((lib.sgcn_spmm_cs_variant_b16 if bf16 else lib.sgcn_spmm_cs_variant)(C.byref(plan), int(d), buf, 256))
         return buf.value.decode()
 
     def autotune(self, B, d=None, candidates=None, reps=2, refine=True):
         """Pick the sweep clock for this plan and row width by timing a few candidates (the
         sustainable pace depends on the graph, d and the chip's clocks; too fast loses the
-        lock-step and with it the L2 hits, too slow leaves the memory system idle)."""
+        lock-step and with it the L2 hits, too slow leaves the memory system idle).  The clock is tuned for the TYPE of
+        the operand it is handed: a bfloat16 ``B`` tunes ``pace_b16`` and leaves the fp32 clock alone."""
         d = int(B.shape[1] if d is None else d)
         self._tuning = True
         try:
@@ -1072,12 +1112,13 @@ class ColumnSweepCSR(object):
             candidates = (-1, 230, 250, 270, 290, 310, 340, 380) if getattr(self, 'ranged', 0) else \
                 (-1, 200, 220, 240, 260, 280, 320, 380) if getattr(self, 'G', 1) == 1 else \
                 (-1, 130, 160, 190, 210, 230, 250, 280, 320)
+        pace_of, tuned_of, guard_of = self._st(B.dtype == torch.bfloat16)
         if self.grouped:                 # grouped plans run unpaced (see the class docstring)
-            self.pace[d] = -1
+            pace_of[d] = -1
             return (None, -1)
         out = torch.empty((self.shape[0], (d + 3) // 4 * 4), dtype=torch.float32, device=B.device)[:, :d]
         def timed(p, reps=reps):
-            self.pace[d] = p
+            pace_of[d] = p
             spmm_cs(self, B, out=out, d=d)                       # warm
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -1123,9 +1164,9 @@ class ColumnSweepCSR(object):
                     best = (t, best[1])
                     break
                 best = (t, int(best[1] * 1.04 + 0.5))
-        self.pace[d] = best[1]
-        self.tuned_ms[d] = float(best[0])
-        self._guard.pop(d, None)
+        pace_of[d] = best[1]
+        tuned_of[d] = float(best[0])
+        guard_of.pop(d, None)
         return best
 
     # ---- lost-lock guard ----------------------------------------------------------------------------
@@ -1135,12 +1176,14 @@ class ColumnSweepCSR(object):
     # samples in a row above GUARD_FACTOR x the tuned time re-run the autotune on that call's operand.
     GUARD_EVERY = 8
     GUARD_FACTOR = 1.3
+    guard_on = True       # False (per plan): no samples and no re-tunes, e.g. inside a measurement's timed windows
 
-    def _guard_before(self, d):
+    def _guard_before(self, d, bf16=False):
         """Called by spmm_cs ahead of the launches: returns the event pair to record around them, or None."""
-        if self.grouped or self.pace.get(d, 0) <= 0 or d not in self.tuned_ms:
+        pace_of, tuned_of, guard_of = self._st(bf16)
+        if self.grouped or pace_of.get(d, 0) <= 0 or d not in tuned_of:
             return None
-        g = self._guard.setdefault(d, {"calls": 0, "pending": None, "strikes": 0, "retunes": 0, "last_ms": None})
+        g = guard_of.setdefault(d, {"calls": 0, "pending": None, "strikes": 0, "retunes": 0, "last_ms": None})
         g["calls"] += 1
         if g["pending"] is not None or g["calls"] % self.GUARD_EVERY:
             return None
@@ -1149,26 +1192,28 @@ class ColumnSweepCSR(object):
 
     def _guard_after(self, d, B):
         """Called by spmm_cs behind the launches: reads a finished sample, re-tunes after two slow ones in a row."""
-        g = self._guard.get(d)
+        _, tuned_of, guard_of = self._st(B.dtype == torch.bfloat16)
+        g = guard_of.get(d)
         if g is None or g["pending"] is None or not g["pending"][1].query():
             return
         e0, e1 = g["pending"]
         g["pending"] = None
         g["last_ms"] = e0.elapsed_time(e1)
-        if g["last_ms"] > self.GUARD_FACTOR * self.tuned_ms[d]:
+        if g["last_ms"] > self.GUARD_FACTOR * tuned_of[d]:
             g["strikes"] += 1
         else:
             g["strikes"] = 0
         if g["strikes"] >= 2:
             n = g["retunes"] + 1
             self.autotune(B, d=d)                      # (resets the guard's state for d)
-            self._guard[d] = {"calls": 0, "pending": None, "strikes": 0, "retunes": n, "last_ms": None}
+            guard_of[d] = {"calls": 0, "pending": None, "strikes": 0, "retunes": n, "last_ms": None}
 
 
 def spmm_cs(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=None):
-    """Column-sweep variant of ``spmm`` for a ColumnSweepCSR (sgcn_spmm_cs_f32)."""
+    """Column-sweep variant of ``spmm`` for a ColumnSweepCSR (sgcn_spmm_cs_f32; sgcn_spmm_cs_b16 on a bfloat16 ``B``, with
+    the plan's clock for that operand type)."""
     M, K = A.shape
-    bptr, ldb = _rows2d(B, "B")
+    bptr, ldb, b16 = _hist2d(B, "B")
     d = int(B.shape[1] if d is None else d)
     if out is None:
         if beta != 0.0:
@@ -1176,25 +1221,26 @@ def spmm_cs(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=Non
         pitch = (d + 3) // 4 * 4
         out = torch.empty((M, pitch), dtype=torch.float32, device=B.device)[:, :d]
     cptr, ldc = _rows2d(out, "out")
-    plan = A.struct(d)
+    plan = A.struct(d, b16)
     if A.pos2col is not None:        # the plan's columns are sweep positions: B row = pos2col[position]
         if cscale is not None:
             raise ValueError("a grouped column-sweep plan does not take cscale (scale B instead)")
         gidx = A.pos2col if gidx is None else _dev(gidx, torch.int32, "gidx")[A.pos2col.long()]
     gp, rp, cp = _ptr(_dev(gidx, torch.int32, "gidx")), _ptr(_dev(rscale, torch.float32, "rscale")), \
         _ptr(_dev(cscale, torch.float32, "cscale"))
-    ev = A._guard_before(d) if not A._tuning else None
+    watch = A.guard_on and not A._tuning
+    ev = A._guard_before(d, b16) if watch else None
     if ev is not None:
         ev[0].record()
     try:
-        check(lib.sgcn_spmm_cs_f32(C.byref(plan), M, K, d, bptr, ldb, gp, rp, cp, cptr, ldc, float(beta), _stream()))
+        check((lib.sgcn_spmm_cs_b16 if b16 else lib.sgcn_spmm_cs_f32)(C.byref(plan), M, K, d, bptr, ldb, gp, rp, cp, cptr, ldc, float(beta), _stream()))
         if ev is not None:
             ev[1].record()
     except BaseException:
         if ev is not None:          # a sample whose second event was never recorded must not stay pending
-            A._guard[d]["pending"] = None
+            A._st(b16)[2][d]["pending"] = None
         raise
-    if not A._tuning and A._guard:
+    if watch and A._st(b16)[2]:
         A._guard_after(d, B)
     return out
 

@@ -363,7 +363,11 @@ class ShardedSpMM(object):
       * ``forward(B)`` / ``backward(dC)``          -- operand replicated / resident: no collective;
       * ``forward_allgather(B_local)`` / ``backward_allgather(dC_local)`` -- the operand is a
         layer activation sharded like C: the ranks all-gather their row blocks first
-        (xGMI-bound for large operands; bench.py reports both variants)."""
+        (xGMI-bound for large operands; bench.py reports both variants).
+    With ``bf16=True`` the all-gather variants move bfloat16: each rank rounds its own row block to nearest even, the ranks
+    all-gather the uint16 blocks -- half the payload -- and the local product reads the gathered table through the
+    bfloat16-operand kernels (sgcn_spmm_cs_b16 / sgcn_spmm_csr_b16); ``forward`` / ``backward`` take such a table as the
+    resident operand.  Results stay fp32 and equal the fp32 product of the rounded operand bit for bit."""
 
     ROW_WEIGHT = 7       # a row of a block costs the column sweep what ~7 of its nonzeros do (its line of C, its share of
                          # the rounds of resident tiles): blocks of S-RMAT 10 M with EQUAL nonzeros took 4.1 ms per fwd + bwd
@@ -433,19 +437,39 @@ class ShardedSpMM(object):
         return self._mm(A, X, out=out)
 
     def forward(self, B, out=None):
-        """C[lo:hi] = A[lo:hi, :] . B        (B: all rows, resident on this GPU)."""
+        """C[lo:hi] = A[lo:hi, :] . B        (B: all rows, resident on this GPU; fp32 or a bfloat16 operand table)."""
         return self._local(self.A, B, out)
 
     def backward(self, dC, out=None):
-        """dB[lo:hi] = A^T[lo:hi, :] . dC    (dC: all rows, resident on this GPU)."""
+        """dB[lo:hi] = A^T[lo:hi, :] . dC    (dC: all rows, resident on this GPU; fp32 or a bfloat16 operand table)."""
         return self._local(self.AT, dC, out)
 
-    def allgather_rows(self, X_local):
+    @staticmethod
+    def round_rows(X, out):
+        """out[:, :d] (bfloat16, a view of a pitched table) = X rounded to nearest even.  On the device: the one rounding
+        kernel (ops.operand_round).  On the host (the collective's dry run without a GPU, kernel=None): the same integer
+        arithmetic on the bits -- (u + 0x7FFF + ((u >> 16) & 1)) >> 16, a NaN kept a NaN -- spelled with tensor ops."""
+        if X.shape[0] == 0:
+            return out
+        if X.is_cuda:
+            from . import ops
+            return ops.operand_round(X, out=out)
+        u = X.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF
+        nan = ((u & 0x7F800000) == 0x7F800000) & ((u & 0x007FFFFF) != 0)
+        r = torch.where(nan, (u >> 16) | 0x40, r)
+        out.copy_((r - ((r >> 15) << 16)).to(torch.int16).view(torch.bfloat16))     # (the 16 bits as a signed word)
+        return out
+
+    def allgather_rows(self, X_local, bf16=False):
         """All rows from the ranks' blocks (ragged blocks travel padded to the largest one).
         The result keeps 16-byte aligned rows (pitch = d rounded up to 4 floats), which the
-        column-sweep kernel requires of its dense operand."""
+        column-sweep kernel requires of its dense operand.  ``bf16``: each rank rounds its block, the uint16 blocks
+        travel (pitch = d rounded up to 8 elements, the bfloat16 operand's layout) and the result is a bfloat16 table."""
         par = self.par
         d = int(X_local.shape[1])
+        if bf16:
+            return self._allgather_rows_b16(X_local, d)
         pitch = (d + 3) // 4 * 4
         if not par.active:
             if X_local.stride(0) % 4 == 0 and X_local.stride(1) == 1:
@@ -465,8 +489,28 @@ class ShardedSpMM(object):
             full[int(self.bounds[r]):int(self.bounds[r + 1])] = recv[r, :self.row_counts[r]]
         return full[:, :d]
 
-    def forward_allgather(self, B_local, out=None):
-        return self.forward(self.allgather_rows(B_local), out=out)
+    def _allgather_rows_b16(self, X_local, d):
+        par, dev = self.par, X_local.device
+        pitch = (d + 7) // 8 * 8
+        n = int(X_local.shape[0])
+        if not par.active:
+            full = torch.zeros((n, pitch), dtype=torch.bfloat16, device=dev)
+            return self.round_rows(X_local, full[:, :d])
+        cap = max(self.row_counts)
+        send = torch.zeros((cap, pitch), dtype=torch.bfloat16, device=dev)
+        self.round_rows(X_local, send[:n, :d])
+        recv = torch.empty((par.world, cap, pitch), dtype=torch.bfloat16, device=dev)
+        # (the payload travels as 32-bit words -- a row is a multiple of 16 bytes -- which every backend moves)
+        dist.all_gather_into_tensor(recv.view(par.world * cap, pitch).view(torch.int32), send.view(torch.int32))
+        if all(c == cap for c in self.row_counts):
+            return recv.view(par.world * cap, pitch)[:, :d]
+        full = torch.empty((self.shape[0], pitch), dtype=torch.bfloat16, device=dev)
+        for r in range(par.world):
+            full[int(self.bounds[r]):int(self.bounds[r + 1])] = recv[r, :self.row_counts[r]]
+        return full[:, :d]
 
-    def backward_allgather(self, dC_local, out=None):
-        return self.backward(self.allgather_rows(dC_local), out=out)
+    def forward_allgather(self, B_local, out=None, bf16=False):
+        return self.forward(self.allgather_rows(B_local, bf16=bf16), out=out)
+
+    def backward_allgather(self, dC_local, out=None, bf16=False):
+        return self.backward(self.allgather_rows(dC_local, bf16=bf16), out=out)

@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_history_dtype
-from .full_batch import StaticBatch, StaticMatrix, check_full_batch
+from .full_batch import StaticBatch, StaticMatrix, check_full_batch, full_batch_bf16
 from .models import make_template
 from .parallel import DataParallel
 from .plaingcn import PlainGCN
@@ -79,6 +79,9 @@ def plan_cache_paths(dataset):
 # d = 602, 16 host cores): the row-gather kernel needs the CSR in HBM and a row-pointer pass (5 ms) and takes 7.66 ms per
 # product; the column sweep needs its host plan + upload (0.185 s: 8 ns per nonzero), a clock autotune worth ~62 products,
 # and takes 0.40 of the row kernel's time per product.
+# (The constants were fitted with fp32 operands and serve --full_batch_dtype bf16 unchanged: the sweep's product
+# with a bfloat16 operand takes 0.835 of the fp32 one at d = 602 (profiles/spmm_b16_products.jsonl); the row kernel's bf16 time
+# is not measured, so a bf16 set would move one side of the ratio only.)
 CS_PLAN_S_PER_NNZ = 8.0e-9
 CS_AUTOTUNE_PRODUCTS = 62
 CS_TIME_RATIO = 0.40
@@ -400,7 +403,9 @@ class Trainer(object):
         static_kernel_for on the number of times the plan will run), the label table, the loss rows."""
         widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(model.L)]
         mat = StaticMatrix(adj, self.device, FLAGS.full_batch_kernel, full_batch_products(which),
-                           max(widths or [FLAGS.hidden1]), cache_path)
+                           max(widths or [FLAGS.hidden1]), cache_path,
+                           # (passed only when set: the fp32 call keeps the argument list tests/test_full_batch.py records)
+                           **(dict(bf16=True) if full_batch_bf16() else {}))
         labels = self.__dict__.get('_labels_dev')          # ONE N x C table on the device for both static batches
         if labels is None:
             labels = self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
