@@ -307,7 +307,8 @@ int sgcn_lds_profile_buffer(void* dev_buf);
  *   of the output layer as the pre-layer of the loss kernel's head, bit 5 the grouped weight-gradient launch's reductions in
  *   the optimizer's launch (when ADAM directly follows DW_FLUSH), bit 6 (with bit 3) the LayerNorm backward pass of a layer
  *   without an input gradient behind the row pass of the layer above it; 0: one launch per piece, the same bits
- *   gemm_min_steps: K-steps a split-K slice keeps at least (default 3) */
+ *   gemm_min_steps: K-steps a split-K slice keeps at least (default 3)
+ *   gemm_mb16_slice_k: least K per split-K slice of sgcn_gemm_mb16_f32 (0: the default, 2048) */
 int sgcn_tune(const char* key, int64_t value);
 int64_t sgcn_tune_get(const char* key);   /* current value, -1 for an unknown key */
 
@@ -550,6 +551,24 @@ int sgcn_gemm_f32(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_
                   const float* dev_A, int64_t lda, const float* dev_B, int64_t ldb, float* dev_C,
                   int64_t ldc, int32_t accumulate, float* dev_ws, const sgcn_dropout_t* drop_a,
                   const sgcn_dropout_t* drop_c, void* stream);
+/* The same product with the MULTIPLY in bfloat16 and the storage in fp32 ("mb16"; --dense_dtype bf16, the dense layers of
+ * a full-graph pass): argument list and status conventions of sgcn_gemm_f32, M, N or K equal to 0 behave as there.
+ * A, B and C stay fp32 in memory; every operand element is rounded to bfloat16, to nearest even, in registers on its way
+ * to the v_mfma_f32_32x32x16_bf16 fragments, and nothing bfloat16 is ever written to memory.  Contract:
+ *   C_ij = sum_k bf(a_ik) * bf(b_kj)      bf = round to nearest even to 8 significant bits,
+ * every product is exact in fp32 (8 x 8 significant bits), and the products are summed in fp32 in a fixed order that
+ * depends on the form, M, N, K and the knob gemm_mb16_slice_k only: two calls give the same bits.  drop_a multiplies the
+ * stored A element by its factor (0 or 1.0f / keep) in fp32 BEFORE the rounding; drop_c multiplies the fp32 result;
+ * accumulate adds the old C once, last.  Any 4-byte aligned base and any pitch >= width work (16-byte aligned rows load
+ * as float4).  Subnormal fp32 inputs and subnormal products may be flushed to zero.
+ * (trans_a, trans_b) = (1, 1) is not provided: SGCN_ERR_INVALID.
+ * dev_ws (nullable): sgcn_gemm_mb16_ws_floats(...) floats enable deterministic split-K (partial tiles added in slice
+ * order by a second launch, no atomics); ignored with drop_c. */
+int64_t sgcn_gemm_mb16_ws_floats(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K);
+int sgcn_gemm_mb16_f32(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K,
+                       const float* dev_A, int64_t lda, const float* dev_B, int64_t ldb, float* dev_C, int64_t ldc,
+                       int32_t accumulate, float* dev_ws, const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c,
+                       void* stream);
 /* One launch per dense layer: Y = act(LN(X . W) * scale + offset)   (N <= 128 when LN / ReLU is
  * requested; offset/scale NULL -> no LayerNorm).   gcn/layers.py:120-138, :396-411
  * dev_X2 (nullable): rows >= split of the operand come from X2 (row - split): the CVD layer runs its

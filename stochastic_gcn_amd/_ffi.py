@@ -180,6 +180,10 @@ SIGNATURES = {
     "sgcn_gemm_ws_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "sgcn_gemm_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
                                 C.c_int64, P, C.c_int64, C.c_int32, P, P, P, P]),
+    # bfloat16 multiply, fp32 storage (--dense_dtype bf16): sgcn_gemm_f32's argument list
+    "sgcn_gemm_mb16_ws_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sgcn_gemm_mb16_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
+                                     C.c_int64, P, C.c_int64, C.c_int32, P, P, P, P]),
     "sgcn_dense_fwd_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, C.c_int32,
                                      P, C.c_int64, P, P, C.c_float, C.c_int32, P, C.c_int64, P, P, P, P, P, P, P]),
     "sgcn_dense_bwd_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, P, P, P,

@@ -45,6 +45,7 @@ int g_tune_cs_g2_wide = 0;
 int g_tune_cs_nowarp = 0;            // experiments: ignore a plan's warp table (the sweep clock linear in the column id)
 int g_tune_cs_last_pct = 80;          // (round 4: 80 % holds the lock-step on the 90-column pass of d = 602: 3.16 vs 3.22 ms at 90, 3.43 at 70)
 int g_tune_gemm_min_steps = 0;
+int g_tune_gemm_mb16_slice_k = 0;   // sgcn_gemm_mb16.hip: least K per split-K slice (0: its default)
 int g_tune_lds_wave_bias = 100;    // LDS plan: entries of a tile's waves 0-3 per 100 of its waves 4-7 (100: even; made moot by the s_setprio around the update chain)
 int g_tune_lds_mix = 1;            // LDS plan: columns a tile uses once or twice dealt into the chunks among the reused ones (all-staged plans)
 int g_tune_lds_dbg = 0;             // experiments on the LDS sweep: bit 0 no ring fills after the first, bit 1 no arithmetic
@@ -69,6 +70,7 @@ int tune_get(const char* key) {
     if (!strcmp(key, "cs_nowarp")) return g_tune_cs_nowarp;
     if (!strcmp(key, "cs_last_pct")) return g_tune_cs_last_pct;
     if (!strcmp(key, "gemm_min_steps")) return g_tune_gemm_min_steps;
+    if (!strcmp(key, "gemm_mb16_slice_k")) return g_tune_gemm_mb16_slice_k;
     if (!strcmp(key, "lds_wave_bias")) return g_tune_lds_wave_bias;
     if (!strcmp(key, "lds_mix")) return g_tune_lds_mix;
     if (!strcmp(key, "lds_dbg")) return g_tune_lds_dbg;
@@ -319,6 +321,10 @@ extern "C" int sgcn_tune(const char* key, int64_t value) {
     if (!strcmp(key, "cs_g2_wide")) { g_tune_cs_g2_wide = value != 0; return SGCN_OK; }
     if (!strcmp(key, "cs_nowarp")) { g_tune_cs_nowarp = value != 0; return SGCN_OK; }
     if (!strcmp(key, "gemm_min_steps")) { g_tune_gemm_min_steps = (int)value; return SGCN_OK; }
+    if (!strcmp(key, "gemm_mb16_slice_k")) {
+        SGCN_REQUIRE(value >= 0 && value <= 0x7fffffff, "gemm_mb16_slice_k >= 0");
+        g_tune_gemm_mb16_slice_k = (int)value; return SGCN_OK;
+    }
     if (!strcmp(key, "lds_wave_bias")) { SGCN_REQUIRE(value >= 50 && value <= 300, "lds_wave_bias in 50..300 (per cent)"); g_tune_lds_wave_bias = (int)value; return SGCN_OK; }
     if (!strcmp(key, "lds_mix")) { g_tune_lds_mix = value != 0; return SGCN_OK; }
     if (!strcmp(key, "lds_dbg")) { g_tune_lds_dbg = (int)value; return SGCN_OK; }

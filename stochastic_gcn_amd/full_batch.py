@@ -22,6 +22,7 @@ from .flags import FLAGS, _CHOICES
 
 KERNELS = _CHOICES['full_batch_kernel']
 DTYPES = _CHOICES['full_batch_dtype']
+DENSE_DTYPES = _CHOICES['dense_dtype']
 
 
 def check_full_batch(flags=None, world=1):
@@ -39,6 +40,12 @@ def check_full_batch(flags=None, world=1):
         if f.full_batch_kernel == 'lds':
             raise ValueError("--full_batch_dtype bf16 is not supported with --full_batch_kernel lds: the LDS-staged sweep "
                              "stages fp32 pieces of the operand and has no bfloat16 form")
+    dense = getattr(f, 'dense_dtype', 'fp32')
+    if dense not in DENSE_DTYPES:
+        raise ValueError("--dense_dtype must be one of %s, got %r" % ('/'.join(DENSE_DTYPES), dense))
+    if dense == 'bf16' and not (f.full_batch or f.test_full_batch):
+        raise ValueError("--dense_dtype bf16 needs --full_batch or --test_full_batch: it is the multiply type of the dense "
+                         "layers of a pass over the whole graph, and no other mode runs that route")
     if f.full_batch:
         for name, why in (('cv', 'exact propagation has no estimator and no history'),
                           ('cvd', 'exact propagation has no estimator and no history'),
@@ -64,6 +71,11 @@ def check_full_batch(flags=None, world=1):
 def full_batch_bf16(flags=None):
     """--full_batch_dtype as a bool (bfloat16 operand?)."""
     return getattr(FLAGS if flags is None else flags, 'full_batch_dtype', 'fp32') == 'bf16'
+
+
+def dense_bf16(flags=None):
+    """--dense_dtype as a bool (bfloat16 multiplies in the dense layers of a static pass?)."""
+    return getattr(FLAGS if flags is None else flags, 'dense_dtype', 'fp32') == 'bf16'
 
 
 def _aligned(t):

@@ -90,6 +90,7 @@ class Layer(object):
         self.need_dx = True  # models.py clears it on the first parametrised layer (no consumer)
         self.index = 0       # position in the model's layer list (part of the dropout key)
         self.key_fn = None   # () -> 32-bit dropout key of this layer at the current step
+        self.mul_bf16 = False  # models.py sets it for a pass over a static batch under --dense_dtype bf16 (Dense reads it)
 
     def drop_site(self, keep):
         """The dropout site of this layer at the current step, or None when nothing is dropped."""
@@ -162,6 +163,7 @@ class Dense(Layer):
         super(Dense, self).__init__(**kw)
         self.input_dim, self.output_dim = input_dim, output_dim
         self.sparse_inputs, self.act, self.norm = sparse_inputs, act, norm
+        self._bf16 = False          # the route the last forward took (backward follows it)
 
     def param_shapes(self):
         s = [('weights', (self.input_dim, self.output_dim), 'glorot')]
@@ -179,11 +181,20 @@ class Dense(Layer):
             x, self._drop = x.x, x.drop
         if isinstance(x, ops.GatheredRows) and not (self.output_dim <= 128 or not (self.norm or self.act)):
             x = x.materialize()            # only the fused launch reads rows through an index
+        self._bf16 = bool(self.mul_bf16) and not self.sparse_inputs
+        if self._bf16 and isinstance(x, ops.GatheredRows):
+            x = x.materialize()
         self._x = x
         off = self.vars.get('offset') if self.norm else None
         sc = self.vars.get('scale') if self.norm else None
         self._ctx = None
-        if self.sparse_inputs:
+        if self._bf16:
+            # a full-graph pass under --dense_dtype bf16: the product on the bf16 matrix cores (operands rounded in
+            # registers, fp32 sums and tables), LayerNorm / ReLU as their own row pass
+            y = ops.gemm_bf16(x, W, drop_a=self._drop)
+            if self.norm or self.act:
+                y, self._ctx = ops.ln_act_fwd(y, off, sc, self.act)
+        elif self.sparse_inputs:
             y = ops.spmm(x.csr, W)
             if self.norm or self.act:      # fused LayerNorm + ReLU (one kernel)
                 y, self._ctx = ops.ln_act_fwd(y, off, sc, self.act)
@@ -203,6 +214,12 @@ class Dense(Layer):
             xt = self._x.transpose_of(self._x.csr.val)
             ops.spmm(xt, g, out=self.grads['weights'], beta=1.0)
             return None
+        if self._bf16:       # the forward's route: LN/ReLU backward, then the two products on the bf16 matrix cores
+            if self.norm or self.act:
+                g = ops.ln_act_bwd(g, self._out, self._ctx, self.vars.get('scale') if self.norm else None,
+                                   self.act, self.grads.get('offset'), self.grads.get('scale'))
+            ops.gemm_bf16(self._x, g, out=self.grads['weights'], trans_a=True, accumulate=True, drop_a=self._drop)
+            return ops.gemm_bf16(g, self.vars['weights'], trans_b=True, drop_c=self._drop) if self.need_dx else None
         # LN/ReLU backward -> dW += dropout(x)^T g -> dx = (g W^T) * mask, one call
         return ops.dense_bwd(g, self._out, self._ctx, self.vars.get('scale') if self.norm else None, self.act,
                              self._x, self.vars['weights'], self.grads['weights'], self.grads.get('offset'),

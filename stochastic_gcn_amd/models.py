@@ -30,7 +30,7 @@ from . import ops
 from ._ffi import check, lib as _lib
 from .flags import FLAGS
 from .layers import (AugmentedDropoutDense, Dense, DetDropoutFC, Dropout, SparseInput)
-from .full_batch import StaticBatch
+from .full_batch import StaticBatch, StaticCur, dense_bf16
 from .scheduler import PackedBatch, build_plan
 
 
@@ -617,6 +617,11 @@ class GCN(Model):
 
     def forward(self, cur):
         self.cur = cur
+        # --dense_dtype bf16: the dense layers of a pass over a static batch multiply in bfloat16 (layers.Dense); any other
+        # batch of the same model -- a sampled step beside an exact evaluation -- keeps the fp32 kernels
+        bf16 = dense_bf16() and isinstance(cur, StaticCur)
+        for layer in self.layers:
+            layer.mul_bf16 = bf16
         self.activations = [cur.inputs]
         for layer in self.layers:
             self.activations.append(layer(self.activations[-1]))

@@ -1637,6 +1637,30 @@ def gemm(A, B, out=None, trans_a=False, trans_b=False, accumulate=False, drop_a=
     return out
 
 
+def gemm_bf16(A, B, out=None, trans_a=False, trans_b=False, accumulate=False, drop_a=None, drop_c=None):
+    """out = op(A) @ op(B) (+ out) with the multiply in bfloat16 (sgcn_gemm_mb16_f32): operands and result are fp32
+    tensors, every operand element is rounded to bfloat16 (nearest even) inside the kernel, products and sums are fp32.
+    The signature of ``gemm``; both operands transposed is not provided."""
+    ap, lda = _rows2d(A, "A")
+    bp, ldb = _rows2d(B, "B")
+    M, K = (A.shape[1], A.shape[0]) if trans_a else (A.shape[0], A.shape[1])
+    K2, N = (B.shape[1], B.shape[0]) if trans_b else (B.shape[0], B.shape[1])
+    if K != K2:
+        raise ValueError("gemm_bf16: inner dimensions differ (%d vs %d)" % (K, K2))
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an existing `out`")
+        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    cp, ldc = _rows2d(out, "out")
+    need = int(lib.sgcn_gemm_mb16_ws_floats(int(trans_a), int(trans_b), int(M), int(N), int(K)))
+    ws = _gemm_ws(need, A.device) if need else None
+    da = C.byref(drop_a.struct(A.shape[1])) if drop_a is not None else None
+    dc = C.byref(drop_c.struct(N)) if drop_c is not None else None
+    check(lib.sgcn_gemm_mb16_f32(int(trans_a), int(trans_b), int(M), int(N), int(K), ap, lda, bp, ldb, cp, ldc,
+                                 int(accumulate), _ptr(ws), da, dc, _stream()))
+    return out
+
+
 class GatheredRows(object):
     """``src[idx]`` that has not been gathered (tf.gather / history.dense_slice of the minibatch's
     input rows, gcn/vrgcn.py:43-45): the first dense layer's GEMMs read the rows through the index
