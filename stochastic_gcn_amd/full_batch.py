@@ -154,7 +154,7 @@ class StaticMatrix(object):
             r = self._plan.residual
             if isinstance(r, ops.ColumnSweepCSR) and d not in r.pace:
                 self._plan.autotune(x, d=d)
-        elif d not in self._plan._st(x.dtype == torch.bfloat16)[0]:
+        elif d not in self._plan.clock(x.dtype == torch.bfloat16).pace:
             self._plan.autotune(x, d=d)                # once per plan, width and operand type; stored with a cached plan
             self._plan.store_if_cached()
 

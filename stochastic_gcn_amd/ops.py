@@ -119,6 +119,21 @@ def as_tensor(x):
     return x.tensor() if isinstance(x, DevArray) else x
 
 
+def _fixup_ws(ws, nslots, d, device):
+    """The fix-up workspace of a plan with ``nslots`` partial-sum slots, grown to hold rows of width d (16-byte pitch)."""
+    need = nslots * ((d + 3) // 4 * 4)
+    if need and (ws is None or ws.numel() < need):
+        ws = torch.empty(need, dtype=torch.float32, device=device)
+    return ws
+
+
+def _pitched_out(M, d, device, beta=0.0):
+    """A fresh (M, d) fp32 result whose rows sit on a 16-byte pitch (what the sweep kernels store fastest)."""
+    if beta != 0.0:
+        raise ValueError("beta != 0 needs an existing `out`")
+    return torch.empty((M, (d + 3) // 4 * 4), dtype=torch.float32, device=device)[:, :d]
+
+
 class DevicePlan(object):
     """Device copy of a host work plan + its partial-sum workspace."""
 
@@ -130,10 +145,7 @@ class DevicePlan(object):
         self.device = device
 
     def struct(self, d):
-        ldw = (d + 3) // 4 * 4
-        need = self.nslots * ldw
-        if need and (self.ws is None or self.ws.numel() < need):
-            self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        self.ws = _fixup_ws(self.ws, self.nslots, d, self.device)
         return _ffi.Plan(self.seg.data_ptr(), self.nseg, _ptr(self.fix), self.nfix, self.nslots,
                          _ptr(self.ws), 0 if self.ws is None else self.ws.numel())
 
@@ -561,6 +573,51 @@ def reorder_labels(a, max_iters=0, seed=1, min_size=64):
     return comm, int(nc.value)
 
 
+def _cs_round(round_tiles=0):
+    """Tiles per launch round of a column-sweep plan: the caller's, else the library's tunable, else 4096."""
+    return int(round_tiles or (_ffi.lib.sgcn_tune_get(b"cs_round") or 4096))
+
+
+def _smallest_t(fits, lo, hi):
+    """The smallest split threshold in [lo, hi] whose pieces ``fits`` accepts (monotone in t; ``hi`` when none does)."""
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if fits(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+class SweepClock(object):
+    """The sweep clock of a ColumnSweepCSR for ONE operand type, per width d."""
+    # The sweep clock of a plan is tuned per width AND operand type: a bfloat16 operand moves half the bytes per step and holds
+    # the lock-step on a different clock.  A plan keeps one record per type (``plan.clock(bf16)``): ``pace`` / ``tuned_ms`` /
+    # ``_guard`` of the plan are the fp32 operand's, ``pace_b16`` ... the bfloat16 operand's, and the two never mix -- in
+    # struct(), the autotuner, the lost-lock guard and the plan cache.
+    __slots__ = ("pace", "tuned_ms", "guard")
+
+    def __init__(self, pace=None, tuned_ms=None):
+        self.pace = pace or {}              # d -> ns per step of the heaviest tile (autotuned), -1 = unpaced
+        self.tuned_ms = tuned_ms or {}      # d -> the product's time at that pace (what the lost-lock guard compares against)
+        self.guard = {}                     # d -> the guard's state (ColumnSweepCSR._guard_before)
+
+    def to_npz(self):
+        """The (pace, tuned_ms) arrays of the plan cache."""
+        return (np.array([[d, p] for d, p in sorted(self.pace.items())], np.int64).reshape(-1, 2),
+                np.array([[d, self.tuned_ms[d]] for d in sorted(self.pace) if d in self.tuned_ms], np.float64).reshape(-1, 2))
+
+    @classmethod
+    def from_npz(cls, z, pace_key, tuned_key):
+        """A cached pace is only as good as the box and clock it was tuned on: it comes back WITH the time it gave there, so
+        the run-time guard (_guard_before / _guard_after) is armed from the first product on; paces stored without that
+        time (files of older builds) are dropped and tuned again, unless unpaced.  A file without the keys (a build
+        without this operand type) gives an empty clock."""
+        tuned = {int(d): float(ms) for d, ms in z[tuned_key]} if tuned_key in z.files else {}
+        pace = {int(d): int(p) for d, p in z[pace_key] if int(d) in tuned or int(p) <= 0} if pace_key in z.files else {}
+        return cls(pace, {d: ms for d, ms in tuned.items() if d in pace})
+
+
 class ColumnSweepCSR(object):
     """A static CSR re-laid for the column sweep (include/sgcn.h sgcn_csplan_t): built once on the
     host (full-graph / PP products), then multiplied many times.
@@ -578,19 +635,17 @@ class ColumnSweepCSR(object):
     WARP_AUTO_DEV = 0.01      # 'auto': a table is kept when some column's share of the work in front of it is off its
                               # share of the ids by more than this (1 % of the sweep ~ a third of an L2 window)
 
-    # The sweep clock of a plan is tuned per width AND operand type: a bfloat16 operand moves half the bytes per step and holds
-    # the lock-step on a different clock.  ``pace`` / ``tuned_ms`` / ``_guard`` are the fp32 operand's; the bfloat16 operand's
-    # live beside them (``pace_b16`` ...) and never mix with them -- in struct(), the autotuner, the lost-lock guard and the
-    # plan cache.
-    def _st(self, bf16=False):
-        """(pace, tuned_ms, guard) of the operand type."""
-        if not bf16:
-            return self.pace, self.tuned_ms, self._guard
-        return self.__dict__.setdefault('_b16', ({}, {}, {}))
+    def clock(self, bf16=False):
+        """The SweepClock of the operand type (fp32, or bfloat16)."""
+        return self._clocks[bool(bf16)]
 
-    pace_b16 = property(lambda self: self._st(True)[0])
-    tuned_ms_b16 = property(lambda self: self._st(True)[1])
-    _guard_b16 = property(lambda self: self._st(True)[2])
+    CLOCK_KEYS = (("pace", "tuned_ms"), ("pace_b16", "tuned_ms_b16"))       # the clocks' keys in the plan cache, by type
+    pace = property(lambda self: self._clocks[0].pace)
+    tuned_ms = property(lambda self: self._clocks[0].tuned_ms)
+    _guard = property(lambda self: self._clocks[0].guard)
+    pace_b16 = property(lambda self: self._clocks[1].pace)
+    tuned_ms_b16 = property(lambda self: self._clocks[1].tuned_ms)
+    _guard_b16 = property(lambda self: self._clocks[1].guard)
 
     @classmethod
     def make_warp(cls, cols, K, mode='auto'):
@@ -621,28 +676,71 @@ class ColumnSweepCSR(object):
         bound on a full graph (3.75 ms on S-Reddit; its gathers alone 3.21: DESIGN.md 3.2), but the better sweep for a SPARSE
         matrix such as the LDS sweep's residual, which is what uses it."""
         a = a.tocsr()
-        self.G = int(G)
-        self.ranged = 0
+        G, labelled = int(G), col_labels is not None or row_labels is not None
         if R != 16:
             raise ValueError("the column-sweep kernels keep 16-row bins (R = 16)")
-        if self.G not in (1, 2, 4):
+        if G not in (1, 2, 4):
             raise ValueError("G must be 1, 2 or 4 lane groups per wavefront")
         if col_ranges and int(col_ranges) > 1:
-            if self.G != 1 or col_labels is not None or row_labels is not None:
+            if G != 1 or labelled:
                 raise ValueError("col_ranges needs an unlabelled plan with one lane group per wavefront")
-            self._init_ranged(a, device, int(col_ranges), T, round_tiles)
-            return
-        if self.G != 1:
-            if col_labels is not None or row_labels is not None or R != 16:
+            p = self._plan_ranged(a, int(col_ranges), T, round_tiles)
+        elif G != 1:
+            if labelled:
                 raise ValueError("G = 2 plans are ungrouped and use 16-row bins")
-            self._init_g2(a, device, T, round_tiles, align, warp)
-            return
+            p = self._plan_groups(a, G, T, round_tiles, align, warp)
+        else:
+            p = self._plan_one(a, T, round_tiles, col_labels, row_labels, warp)
+        self._finish(p, device, round_tiles)
+
+    # What a builder (_plan_one / _plan_groups / _plan_ranged) or the cache file (_load) hands to _finish: the host arrays
+    # ``tile_ptr, colrow, val, tile_rows, tile_slots, fix``, ``nslots``, ``shape``, ``nnz`` and the entries below, which
+    # default to what a plan without them has.  ``host_plan_s``: what the builder spent in the plan builder proper.
+    _RECORD = dict(R=16, G=1, T=None, align=None, pad_fraction=0.0, ranged=0, range_cuts=None, grouped=False, pos2col=None,
+                   warp=None, warp_shift=0, host_plan_s=None)
+
+    @staticmethod
+    def _record(built, **entries):
+        """A plan record from ``_build``'s result; ``entries`` fill (or replace) the rest."""
+        tile_ptr, colrow, val, tile_rows, tile_slots, fix, _, _, nslots = built
+        p = dict(ColumnSweepCSR._RECORD, tile_ptr=tile_ptr, colrow=colrow, val=val, tile_rows=tile_rows, tile_slots=tile_slots,
+                 fix=fix, nslots=nslots)
+        p.update(entries)
+        return p
+
+    def _finish(self, p, device, round_tiles, clocks=None):
+        """Make this object the plan of record ``p`` on ``device``: the one place that assigns a plan's attributes and
+        uploads its arrays, so a plan is the same object whether it was built (by any builder) or loaded."""
+        t_up = time.perf_counter()
+        to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(device)          # noqa: E731
+        self.shape, self.nnz, self.R, self.round_tiles = p["shape"], p["nnz"], p["R"], round_tiles
+        self.G, self.T, self.align, self.pad_fraction = p["G"], p["T"], p["align"], p["pad_fraction"]
+        self.ranged, self.range_cuts, self.grouped = p["ranged"], p["range_cuts"], p["grouped"]
+        self.ntiles, self.nfix, self.nslots = int(p["tile_ptr"].shape[0] - 1), int(p["fix"].shape[0]), int(p["nslots"])
+        self._tile_nnz = (np.diff(p["tile_ptr"]) // self.G).astype(np.int64)       # steps per tile (what the pace counts)
+        self._hint, self._hint_round = None, None
+        self._clocks = clocks or (SweepClock(), SweepClock())                     # (fp32 operand, bfloat16 operand)
+        self._tuning, self._cache = False, None                                    # (_cache: where ``cached`` wants it stored)
+        self.tile_ptr, self.colrow, self.val = to(p["tile_ptr"]), to(p["colrow"]), to(p["val"])
+        self.tile_rows, self.tile_slots = to(p["tile_rows"]), to(p["tile_slots"])
+        self.fix = to(p["fix"]) if self.nfix else None
+        self.ws, self.device = None, device
+        self.pos2col = to(p["pos2col"])
+        # the clock's coordinates (make_warp; a ranged plan's own table)
+        self.warp, self.warp_shift = to(None if p["warp"] is None else p["warp"].view(np.int32)), p["warp_shift"]
+        # what the plan cost to set up (the product it serves may run once: gcn/utils.py:321-322); None on a loaded plan
+        self.setup_s = None if p["host_plan_s"] is None else {
+            "host_plan_s": p["host_plan_s"], "upload_s": time.perf_counter() - t_up, "host_threads": int(lib.sgcn_host_threads())}
+
+    @staticmethod
+    def _plan_one(a, T, round_tiles, col_labels, row_labels, warp):
+        """One lane group per wavefront (sgcn_csplan_*), plain or labelled (see the class docstring)."""
         rowptr = np.ascontiguousarray(a.indptr, dtype=np.int32)
         col = np.ascontiguousarray(a.indices, dtype=np.int32)
         val = np.ascontiguousarray(a.data, dtype=np.float32)
         M = rowptr.shape[0] - 1
-        self.grouped = col_labels is not None or row_labels is not None
-        self.pos2col = None
+        grouped = col_labels is not None or row_labels is not None
+        pos2col = None
         if col_labels is not None:
             col_labels = np.ascontiguousarray(col_labels, dtype=np.int32)
             if col_labels.shape[0] != a.shape[1]:
@@ -651,40 +749,20 @@ class ColumnSweepCSR(object):
             col2pos = np.empty_like(pos2col)
             col2pos[pos2col] = np.arange(pos2col.shape[0], dtype=np.int32)
             col = np.ascontiguousarray(col2pos[col])                              # the plan lives in positions
-            self.pos2col = torch.from_numpy(pos2col).to(device)
         rg = None
         if row_labels is not None:
             rg = np.ascontiguousarray(row_labels, dtype=np.int32)
             if rg.shape[0] != M:
                 raise ValueError("row_labels must have one label per row")
-        rgp = rg.ctypes.data if rg is not None else None
-        if not T and not self.grouped:
-            T = self.auto_t(rowptr, 1, int(round_tiles or (_ffi.lib.sgcn_tune_get(b"cs_round") or 4096)))
-        self.T = int(T)
+        if not T and not grouped:
+            T = ColumnSweepCSR.auto_t(rowptr, 1, _cs_round(round_tiles))
         t_build = time.perf_counter()
-        tile_ptr, colrow, valout, tile_rows, tile_slots, fix, nt, nfix, nslots = self._build(
-            rowptr, col, val, M, 1, R, T, 0, 0, rgp, None, 0)
+        built = ColumnSweepCSR._build(rowptr, col, val, M, 1, 16, T, 0, 0, rg.ctypes.data if rg is not None else None, None, 0)
         t_build = time.perf_counter() - t_build
-        self.shape = (int(a.shape[0]), int(a.shape[1]))
-        self.R, self.ntiles, self.nfix, self.nslots = R, nt, nfix, nslots
-        self.round_tiles = round_tiles
-        self._tile_nnz = np.diff(tile_ptr).astype(np.int64)
-        self._hint, self._hint_round = None, None
-        self.pace = {}          # d -> ns per nonzero of the heaviest tile (autotuned), -1 = unpaced
-        self.tuned_ms, self._guard, self._tuning = {}, {}, False
-        t_up = time.perf_counter()
-        to = lambda x: torch.from_numpy(x).to(device)          # noqa: E731
-        self.tile_ptr, self.colrow, self.val = to(tile_ptr), to(colrow), to(valout)
-        self.tile_rows, self.tile_slots = to(tile_rows), to(tile_slots)
-        self.fix = to(fix) if nfix else None
-        self.ws, self.device = None, device
-        self.nnz = int(col.shape[0])
         # the clock's coordinates (grouped plans run unpaced: no table)
-        wtab, self.warp_shift = (None, 0) if self.grouped else self.make_warp(col, self.shape[1], warp)
-        self.warp = None if wtab is None else torch.from_numpy(wtab.view(np.int32)).to(device)
-        # what the plan cost to set up (the product it serves may run once: gcn/utils.py:321-322)
-        self.setup_s = {"host_plan_s": t_build, "upload_s": time.perf_counter() - t_up,
-                        "host_threads": int(lib.sgcn_host_threads())}
+        wtab, shift = (None, 0) if grouped else ColumnSweepCSR.make_warp(col, a.shape[1], warp)
+        return ColumnSweepCSR._record(built, shape=(int(a.shape[0]), int(a.shape[1])), nnz=int(col.shape[0]), T=int(T),
+                                      grouped=grouped, pos2col=pos2col, warp=wtab, warp_shift=shift, host_plan_s=t_build)
 
     @staticmethod
     def auto_align(K, nnz, M, G, rnd, d_piece_bytes=None):
@@ -721,14 +799,7 @@ class ColumnSweepCSR(object):
         cap = -(-v0 // cap_round) * cap_round
         if v0 >= 0.75 * cap:
             return 0
-        lo, hi = 24, t0
-        while lo < hi:
-            mid = (lo + hi) // 2
-            if vrows(mid) <= 0.7 * cap:
-                hi = mid
-            else:
-                lo = mid + 1
-        return lo
+        return _smallest_t(lambda t: vrows(t) <= 0.7 * cap, 24, t0)
 
     # ---- a small row block with its rows split BY COLUMN RANGE (round 6) --------------------------------------------------
     RANGE_FILL = 0.95     # virtual rows of a ranged plan: split until they fill this share of one round of resident tiles
@@ -749,7 +820,8 @@ class ColumnSweepCSR(object):
         f2 = 0.5 * (1.0 - np.exp(-nnz / 8.0 / (K / 2.0)))
         return 2 if f2 <= 0.75 * f1 else 0
 
-    def _init_ranged(self, a, device, NR, T, round_tiles):
+    @staticmethod
+    def _plan_ranged(a, NR, T, round_tiles):
         """Rows split by column range instead of by stride: piece j of a row = its nonzeros in columns [cut_j, cut_j+1)
         (ranges of equal nonzeros, cut on warp-bucket boundaries), the pieces of range j form the tiles of XCDs
         [8 j / NR, 8 (j + 1) / NR) (tiles in range order + the launch's tile range cut into eight contiguous pieces:
@@ -758,7 +830,6 @@ class ColumnSweepCSR(object):
         deterministic, and nothing in the kernels changes.  Built from the shipped plan builder: the NR column-restricted
         copies of the block stacked as NR x M rows with the range as the row label, then rows and workspace slots renamed."""
         import scipy.sparse as sp
-        a = a.tocsr()
         if not a.has_sorted_indices:         # (a private copy: the caller's matrix is not reordered behind its back)
             a = a.copy()
             a.sort_indices()
@@ -766,9 +837,8 @@ class ColumnSweepCSR(object):
         rowptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
         col = np.ascontiguousarray(a.indices, dtype=np.int32)
         val = np.ascontiguousarray(a.data, dtype=np.float32)
-        rnd = int(round_tiles or (_ffi.lib.sgcn_tune_get(b"cs_round") or 4096))
         shift = 0
-        while (K >> shift) > self.WARP_BUCKETS:
+        while (K >> shift) > ColumnSweepCSR.WARP_BUCKETS:
             shift += 1
         bucket = 1 << shift
         cum = np.concatenate([[0], np.cumsum(np.bincount(col, minlength=K).astype(np.int64))])
@@ -787,23 +857,13 @@ class ColumnSweepCSR(object):
         labels = np.ascontiguousarray(np.repeat(np.arange(NR, dtype=np.int32), M))
         sdeg = np.diff(srp.astype(np.int64))
         if not T:      # split further (by stride, inside a range) until the pieces fill RANGE_FILL of one round
-            cap = int(self.RANGE_FILL * rnd * 16)
+            cap = int(ColumnSweepCSR.RANGE_FILL * _cs_round(round_tiles) * 16)
             pieces = lambda t: int(np.maximum(sdeg > 0, -(-sdeg // t)).sum())      # noqa: E731
-            lo, hi = 24, int(max(64, sdeg.max() if sdeg.size else 64))
-            if pieces(hi) > cap:
-                T = hi
-            else:
-                while lo < hi:
-                    mid = (lo + hi) // 2
-                    if pieces(mid) <= cap:
-                        hi = mid
-                    else:
-                        lo = mid + 1
-                T = lo
-        self.T, self.ranged, self.range_cuts = int(T), NR, [int(x) for x in cuts]
+            hi = int(max(64, sdeg.max() if sdeg.size else 64))
+            T = hi if pieces(hi) > cap else _smallest_t(lambda t: pieces(t) <= cap, 24, hi)
         t_build = time.perf_counter()
-        tile_ptr, colrow, valout, tile_rows, tile_slots, fix, nt, nfix, _ = self._build(
-            srp, scol, sval, NR * M, 1, 16, self.T, 0, 0, labels.ctypes.data, None, 0)
+        built = ColumnSweepCSR._build(srp, scol, sval, NR * M, 1, 16, int(T), 0, 0, labels.ctypes.data, None, 0)
+        _, _, _, tile_rows, tile_slots, fix, _, nfix, _ = built
         # ---- rename: stacked row j * M + r -> row r; its workspace slots -> consecutive slots of row r, range by range
         npieces = (sdeg > 0).astype(np.int64)                      # an empty piece takes no slot (and writes nothing)
         old_first = np.full(NR * M, -1, dtype=np.int64)
@@ -830,72 +890,37 @@ class ColumnSweepCSR(object):
         rs = np.nonzero(split)[0]
         new_fix = np.stack([rs, base[rs], total[rs]], axis=1).astype(np.int32) if rs.size else np.zeros((0, 3), np.int32)
         t_build = time.perf_counter() - t_build
-        self.grouped, self.pos2col = False, None
-        self.shape = (M, K)
-        self.R, self.ntiles, self.nfix, self.nslots = 16, nt, int(new_fix.shape[0]), int(total[split].sum())
-        self.round_tiles = round_tiles
-        self._tile_nnz = np.diff(tile_ptr).astype(np.int64)
-        self._hint, self._hint_round = None, None
-        self.pace, self.tuned_ms, self._guard, self._tuning = {}, {}, {}, False
-        t_up = time.perf_counter()
-        to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)          # noqa: E731
-        self.tile_ptr, self.colrow, self.val = to(tile_ptr), to(colrow), to(valout)
-        self.tile_rows, self.tile_slots = to(new_rows), to(new_slots)
-        self.fix = to(new_fix) if self.nfix else None
-        self.ws, self.device = None, device
-        self.nnz = int(col.shape[0])
         # the clock's coordinates: a column's position INSIDE its range, scaled to [0, K) -- every range starts at 0
         nb = -(-K // bucket)
         first = np.arange(nb, dtype=np.int64) * bucket
         rj = np.searchsorted(cuts, first, side="right") - 1
         lo_, hi_ = cuts[rj], cuts[rj + 1]
         table = ((first - lo_) * K // np.maximum(hi_ - lo_, 1)).astype(np.uint32)
-        self.warp, self.warp_shift = to(table.view(np.int32)), shift
-        self.setup_s = {"host_plan_s": t_build, "upload_s": time.perf_counter() - t_up,
-                        "host_threads": int(lib.sgcn_host_threads())}
+        return ColumnSweepCSR._record(built, shape=(M, K), nnz=int(col.shape[0]), T=int(T), ranged=NR,
+                                      range_cuts=[int(x) for x in cuts], tile_rows=new_rows, tile_slots=new_slots, fix=new_fix,
+                                      nslots=int(total[split].sum()), warp=table, warp_shift=shift, host_plan_s=t_build)
 
-    def _init_g2(self, a, device, T, round_tiles, align, warp='auto'):
+    @staticmethod
+    def _plan_groups(a, G, T, round_tiles, align, warp):
         """G = 2 / 4 lane groups per wavefront (sgcn_csplang_*)"""
-        G = self.G
         rowptr = np.ascontiguousarray(a.indptr, dtype=np.int32)
         col = np.ascontiguousarray(a.indices, dtype=np.int32)
         val = np.ascontiguousarray(a.data, dtype=np.float32)
-        M = rowptr.shape[0] - 1
-        rnd = int(round_tiles or (_ffi.lib.sgcn_tune_get(b"cs_round") or 4096))
+        M, K = rowptr.shape[0] - 1, int(a.shape[1])
+        rnd = _cs_round(round_tiles)
         if not T:
-            T = self.auto_t(rowptr, G, rnd)
-        self.T = int(T)
-        self.shape = (int(a.shape[0]), int(a.shape[1]))
+            T = ColumnSweepCSR.auto_t(rowptr, G, rnd)
         # the clock's coordinates first: the bins of a wave are aligned in them
-        wtab, self.warp_shift = self.make_warp(col, self.shape[1], warp)
-        self.warp = None if wtab is None else torch.from_numpy(wtab.view(np.int32)).to(device)
-        wp = wtab.ctypes.data if wtab is not None else None
+        wtab, shift = ColumnSweepCSR.make_warp(col, K, warp)
         if align is None or align == 'auto':
-            align = self.auto_align(self.shape[1], col.shape[0], M, G, rnd)
-        self.align = align = int(align)
+            align = ColumnSweepCSR.auto_align(K, col.shape[0], M, G, rnd)
         t_build = time.perf_counter()
-        tile_ptr, colrow, valout, tile_rows, tile_slots, fix, nt, nfix, nslots = self._build(
-            rowptr, col, val, M, G, 16, T, rnd, align, None, wp, self.warp_shift)
+        built = ColumnSweepCSR._build(rowptr, col, val, M, G, 16, T, rnd, int(align), None,
+                                      wtab.ctypes.data if wtab is not None else None, shift)
         t_build = time.perf_counter() - t_build
-        ne = int(colrow.shape[0])
-        self.pad_fraction = 1.0 - col.shape[0] / max(ne, 1)
-        self.grouped, self.pos2col = False, None
-        self.shape = (int(a.shape[0]), int(a.shape[1]))
-        self.R, self.ntiles, self.nfix, self.nslots = 16, nt, nfix, nslots
-        self.round_tiles = round_tiles
-        self._tile_nnz = (np.diff(tile_ptr) // G).astype(np.int64)       # steps per tile (what the pace counts)
-        self._hint, self._hint_round = None, None
-        self.pace = {}
-        self.tuned_ms, self._guard, self._tuning = {}, {}, False
-        t_up = time.perf_counter()
-        to = lambda x: torch.from_numpy(x).to(device)          # noqa: E731
-        self.tile_ptr, self.colrow, self.val = to(tile_ptr), to(colrow), to(valout)
-        self.tile_rows, self.tile_slots = to(tile_rows), to(tile_slots)
-        self.fix = to(fix) if nfix else None
-        self.ws, self.device = None, device
-        self.nnz = int(col.shape[0])
-        self.setup_s = {"host_plan_s": t_build, "upload_s": time.perf_counter() - t_up,
-                        "host_threads": int(lib.sgcn_host_threads())}
+        return ColumnSweepCSR._record(built, shape=(int(a.shape[0]), K), nnz=int(col.shape[0]), G=G, T=int(T), align=int(align),
+                                      pad_fraction=1.0 - col.shape[0] / max(int(built[1].shape[0]), 1), warp=wtab,
+                                      warp_shift=shift, host_plan_s=t_build)
 
     @staticmethod
     def _build(rowptr, col, val, M, G, R, T, rnd, align, rgp, wp, warp_shift, threads=0):
@@ -957,25 +982,18 @@ class ColumnSweepCSR(object):
         return 2 if -(-dp // 128) * 0.73 * r2 <= -(-dp // 320) * r1 else 1
 
     def save(self, path, key):
-        if self.grouped or getattr(self, 'ranged', 0):
+        if self.grouped or self.ranged:
             raise ValueError("grouped / column-range plans are not cached (they are cheap to rebuild)")
         t = lambda x: x.cpu().numpy()          # noqa: E731
-        blob = dict(key=np.array(key), G=int(getattr(self, 'G', 1)), pad_fraction=float(getattr(self, 'pad_fraction', 0.0)),
+        blob = dict(key=np.array(key), G=self.G, pad_fraction=float(self.pad_fraction),
                     R=self.R, shape=np.array(self.shape, np.int64), nslots=self.nslots,
                     round_tiles=self.round_tiles, tile_ptr=t(self.tile_ptr), colrow=t(self.colrow), val=t(self.val),
                     tile_rows=t(self.tile_rows), tile_slots=t(self.tile_slots),
                     fix=t(self.fix) if self.fix is not None else np.zeros((0, 3), np.int32),
-                    pace=np.array([[d, p] for d, p in sorted(self.pace.items())], np.int64).reshape(-1, 2),
-                    # the product's time at that pace: what the lost-lock guard compares against (a pace without it
-                    # -- a file of an older build -- is not restored: the guard could not watch it)
-                    tuned_ms=np.array([[d, self.tuned_ms[d]] for d in sorted(self.pace) if d in self.tuned_ms],
-                                      np.float64).reshape(-1, 2),
-                    warp=t(self.warp) if getattr(self, 'warp', None) is not None else np.zeros(0, np.int32),
-                    warp_shift=int(getattr(self, 'warp_shift', 0)),
-                    # the bfloat16 operand's clocks, under keys of their own: a build without them reads the rest unchanged
-                    pace_b16=np.array([[d, p] for d, p in sorted(self.pace_b16.items())], np.int64).reshape(-1, 2),
-                    tuned_ms_b16=np.array([[d, self.tuned_ms_b16[d]] for d in sorted(self.pace_b16) if d in self.tuned_ms_b16],
-                                          np.float64).reshape(-1, 2))
+                    warp=t(self.warp) if self.warp is not None else np.zeros(0, np.int32), warp_shift=self.warp_shift)
+        # each operand type's clocks under keys of their own: a build without the bfloat16 operand reads the rest unchanged
+        for clock, (pace_key, tuned_key) in zip(self._clocks, self.CLOCK_KEYS):
+            blob[pace_key], blob[tuned_key] = clock.to_npz()
         import os
         import tempfile
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
@@ -1013,34 +1031,13 @@ class ColumnSweepCSR(object):
         G = int(z["G"]) if "G" in z.files else 1
         if g is not None and G != g:
             return None
+        warp = z["warp"] if "warp" in z.files and z["warp"].shape[0] else None
+        p = dict(cls._RECORD, G=G, R=int(z["R"]), shape=tuple(int(x) for x in z["shape"]), nnz=int(z["colrow"].shape[0]),
+                 pad_fraction=float(z["pad_fraction"]) if "pad_fraction" in z.files else 0.0, nslots=int(z["nslots"]),
+                 warp=warp, warp_shift=int(z["warp_shift"]) if warp is not None else 0,
+                 **{k: z[k] for k in ("tile_ptr", "colrow", "val", "tile_rows", "tile_slots", "fix")})
         self = cls.__new__(cls)
-        self.grouped, self.pos2col, self.G, self.ranged = False, None, G, 0
-        self.pad_fraction = float(z["pad_fraction"]) if "pad_fraction" in z.files else 0.0
-        self.shape = tuple(int(x) for x in z["shape"])
-        self.R, self.nslots, self.round_tiles = int(z["R"]), int(z["nslots"]), int(z["round_tiles"])
-        tile_ptr = z["tile_ptr"]
-        self.ntiles, self.nfix = int(tile_ptr.shape[0] - 1), int(z["fix"].shape[0])
-        self._tile_nnz = (np.diff(tile_ptr) // G).astype(np.int64)         # steps per tile (what the pace counts)
-        self._hint, self._hint_round = None, None
-        # a cached pace is only as good as the box and clock it was tuned on: it comes back WITH the time it gave there,
-        # so the run-time guard (_guard_before / _guard_after) is armed from the first product on; paces stored without
-        # that time (files of older builds) are dropped and tuned again
-        tuned = {int(d): float(ms) for d, ms in z["tuned_ms"]} if "tuned_ms" in z.files else {}
-        self.pace = {int(d): int(p) for d, p in z["pace"] if int(d) in tuned or int(p) <= 0}
-        self.tuned_ms, self._guard, self._tuning = {d: ms for d, ms in tuned.items() if d in self.pace}, {}, False
-        # (a file of a build without the bfloat16 operand has neither key: empty bf16 state)
-        tuned16 = {int(d): float(ms) for d, ms in z["tuned_ms_b16"]} if "tuned_ms_b16" in z.files else {}
-        pace16 = {int(d): int(p) for d, p in z["pace_b16"] if int(d) in tuned16 or int(p) <= 0} if "pace_b16" in z.files else {}
-        self._b16 = (pace16, {d: ms for d, ms in tuned16.items() if d in pace16}, {})
-        to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)          # noqa: E731
-        self.tile_ptr, self.colrow, self.val = to(tile_ptr), to(z["colrow"]), to(z["val"])
-        self.tile_rows, self.tile_slots = to(z["tile_rows"]), to(z["tile_slots"])
-        self.fix = to(z["fix"]) if self.nfix else None
-        self.ws, self.device = None, device
-        self.nnz = int(z["colrow"].shape[0])
-        self.warp, self.warp_shift = None, 0
-        if "warp" in z.files and z["warp"].shape[0]:
-            self.warp, self.warp_shift = to(z["warp"]), int(z["warp_shift"])
+        self._finish(p, device, int(z["round_tiles"]), tuple(SweepClock.from_npz(z, *keys) for keys in cls.CLOCK_KEYS))
         return self
 
     @classmethod
@@ -1050,7 +1047,7 @@ class ColumnSweepCSR(object):
         if path is None:
             return cls(a, device, G=G), False
         # the identity of the matrix AND of the build parameters the plan depends on (tiles per launch round)
-        key = "%s:r%d:Tauto:aauto:w1" % (cls.matrix_key(a), int(_ffi.lib.sgcn_tune_get(b"cs_round") or 4096))   # cached() builds with the default T / align
+        key = "%s:r%d:Tauto:aauto:w1" % (cls.matrix_key(a), _cs_round())   # cached() builds with the default T / align
         hit = cls.load(path, device, key, g=G)
         if hit is not None:
             return hit, True
@@ -1060,20 +1057,16 @@ class ColumnSweepCSR(object):
 
     def store_if_cached(self):
         """Write the plan (with the paces autotuned so far) to the path ``cached`` was given."""
-        c = getattr(self, "_cache", None)
-        if c is not None:
+        if self._cache is not None:
             try:
-                self.save(*c)
+                self.save(*self._cache)
             except OSError:           # read-only dataset directory: the cache is an optimisation only
                 pass
 
     def struct(self, d, bf16=False):
         """The C struct for a product of width d; ``bf16``: with the clock tuned for a bfloat16 operand."""
-        ldw = (d + 3) // 4 * 4
-        need = self.nslots * ldw
-        if need and (self.ws is None or self.ws.numel() < need):
-            self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
-        rnd = self.round_tiles or (_ffi.lib.sgcn_tune_get(b"cs_round") or 4096)
+        self.ws = _fixup_ws(self.ws, self.nslots, d, self.device)
+        rnd = _cs_round(self.round_tiles)
         if self._hint_round != rnd:         # heaviest tile of every launch, for pacing
             nl = -(-self.ntiles // rnd)
             pad = np.zeros(nl * rnd, dtype=np.int64)
@@ -1084,9 +1077,8 @@ class ColumnSweepCSR(object):
                            self.val.data_ptr(), self.tile_rows.data_ptr(), self.tile_slots.data_ptr(),
                            _ptr(self.fix), self.nfix, self.nslots, _ptr(self.ws),
                            0 if self.ws is None else self.ws.numel(), rnd, self._hint.ctypes.data,
-                           -1 if self.grouped else int(self._st(bf16)[0].get(d, 0)), int(getattr(self, 'G', 1)),
-                           1 if (self.grouped or getattr(self, 'ranged', 0)) else 0, _ptr(getattr(self, 'warp', None)),
-                           int(getattr(self, 'warp_shift', 0)))
+                           -1 if self.grouped else int(self.clock(bf16).pace.get(d, 0)), self.G,
+                           1 if (self.grouped or self.ranged) else 0, _ptr(self.warp), self.warp_shift)
 
     def variant(self, d, bf16=False):
         """The kernel variant / launch geometry sgcn_spmm_cs_f32 (``bf16``: sgcn_spmm_cs_b16) uses for this plan and width."""
@@ -1109,14 +1101,15 @@ class ColumnSweepCSR(object):
 
     def _autotune(self, B, d, candidates, reps, refine):
         if candidates is None:           # ns per step of the heaviest tile (a G = 2 step is one load for two nonzeros)
-            candidates = (-1, 230, 250, 270, 290, 310, 340, 380) if getattr(self, 'ranged', 0) else \
-                (-1, 200, 220, 240, 260, 280, 320, 380) if getattr(self, 'G', 1) == 1 else \
+            candidates = (-1, 230, 250, 270, 290, 310, 340, 380) if self.ranged else \
+                (-1, 200, 220, 240, 260, 280, 320, 380) if self.G == 1 else \
                 (-1, 130, 160, 190, 210, 230, 250, 280, 320)
-        pace_of, tuned_of, guard_of = self._st(B.dtype == torch.bfloat16)
+        clock = self.clock(B.dtype == torch.bfloat16)
+        pace_of, tuned_of, guard_of = clock.pace, clock.tuned_ms, clock.guard
         if self.grouped:                 # grouped plans run unpaced (see the class docstring)
             pace_of[d] = -1
             return (None, -1)
-        out = torch.empty((self.shape[0], (d + 3) // 4 * 4), dtype=torch.float32, device=B.device)[:, :d]
+        out = _pitched_out(self.shape[0], d, B.device)
         def timed(p, reps=reps):
             pace_of[d] = p
             spmm_cs(self, B, out=out, d=d)                       # warm
@@ -1180,10 +1173,10 @@ class ColumnSweepCSR(object):
 
     def _guard_before(self, d, bf16=False):
         """Called by spmm_cs ahead of the launches: returns the event pair to record around them, or None."""
-        pace_of, tuned_of, guard_of = self._st(bf16)
-        if self.grouped or pace_of.get(d, 0) <= 0 or d not in tuned_of:
+        clock = self.clock(bf16)
+        if self.grouped or clock.pace.get(d, 0) <= 0 or d not in clock.tuned_ms:
             return None
-        g = guard_of.setdefault(d, {"calls": 0, "pending": None, "strikes": 0, "retunes": 0, "last_ms": None})
+        g = clock.guard.setdefault(d, {"calls": 0, "pending": None, "strikes": 0, "retunes": 0, "last_ms": None})
         g["calls"] += 1
         if g["pending"] is not None or g["calls"] % self.GUARD_EVERY:
             return None
@@ -1192,7 +1185,8 @@ class ColumnSweepCSR(object):
 
     def _guard_after(self, d, B):
         """Called by spmm_cs behind the launches: reads a finished sample, re-tunes after two slow ones in a row."""
-        _, tuned_of, guard_of = self._st(B.dtype == torch.bfloat16)
+        clock = self.clock(B.dtype == torch.bfloat16)
+        tuned_of, guard_of = clock.tuned_ms, clock.guard
         g = guard_of.get(d)
         if g is None or g["pending"] is None or not g["pending"][1].query():
             return
@@ -1216,10 +1210,7 @@ def spmm_cs(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=Non
     bptr, ldb, b16 = _hist2d(B, "B")
     d = int(B.shape[1] if d is None else d)
     if out is None:
-        if beta != 0.0:
-            raise ValueError("beta != 0 needs an existing `out`")
-        pitch = (d + 3) // 4 * 4
-        out = torch.empty((M, pitch), dtype=torch.float32, device=B.device)[:, :d]
+        out = _pitched_out(M, d, B.device, beta)
     cptr, ldc = _rows2d(out, "out")
     plan = A.struct(d, b16)
     if A.pos2col is not None:        # the plan's columns are sweep positions: B row = pos2col[position]
@@ -1238,9 +1229,9 @@ def spmm_cs(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=Non
             ev[1].record()
     except BaseException:
         if ev is not None:          # a sample whose second event was never recorded must not stay pending
-            A._st(b16)[2][d]["pending"] = None
+            A.clock(b16).guard[d]["pending"] = None
         raise
-    if watch and A._st(b16)[2]:
+    if watch and A.clock(b16).guard:
         A._guard_after(d, B)
     return out
 
@@ -1419,10 +1410,7 @@ class LdsSweepCSR(object):
                 DeviceCSR.from_scipy(h.residual, device)
 
     def struct(self, d):
-        ldw = (d + 3) // 4 * 4
-        need = self.nslots * ldw
-        if need and (self.ws is None or self.ws.numel() < need):
-            self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        self.ws = _fixup_ws(self.ws, self.nslots, d, self.device)
         return _ffi.LdsPlan(self.VW, self.NW, self.RW, self.S, self.U, self.nparts, self.unit, (C.c_int32 * 9)(*self.xcd_tile_ptr),
                             self.ntiles, self.nchunks, self.nent,
                             self.tile_chunk_ptr.data_ptr(), self.chunk_cols.data_ptr(), self.chunk_hdr.data_ptr(),
@@ -1491,10 +1479,7 @@ def spmm_lds(A, B, out=None, rscale=None, beta=0.0, d=None, local_only=False):
     bptr, ldb = _rows2d(B, "B")
     d = int(B.shape[1] if d is None else d)
     if out is None:
-        if beta != 0.0:
-            raise ValueError("beta != 0 needs an existing `out`")
-        pitch = (d + 3) // 4 * 4
-        out = torch.empty((M, pitch), dtype=torch.float32, device=B.device)[:, :d]
+        out = _pitched_out(M, d, B.device, beta)
     cptr, ldc = _rows2d(out, "out")
     if A.col_fold is not None:               # one value per column: B's rows take it (one pass over B), the plan is a unit plan
         pitch = (d + 31) // 32 * 32               # rows on 128-byte lines: a piece of a row never straddles one more line than it must

@@ -2,6 +2,7 @@
 exactly one tile slot with its row and value, grouped plans keep tiles inside their row group,
 and label propagation finds planted communities (and nothing in a graph without structure)."""
 import ctypes as C
+import inspect
 
 import numpy as np
 import pytest
@@ -512,3 +513,86 @@ def test_choose_ranges_takes_the_small_fabric_bound_block_only():
     assert CS.choose_ranges(58300, 5800000, 232965, 1) == 0        # a quarter: 2 x 58 k pieces do not fit one round
     assert CS.choose_ranges(29211, 2896039, 232965, 2) == 0        # two lane groups: not a one-group plan
     assert CS.choose_ranges(2000, 20000, 232965, 1) == 0           # so sparse that an XCD touches few columns either way
+
+
+# ---- one construction path: every plan is the same object however it was obtained --------------------------------------
+def _small(M=300, K=300, density=0.05, seed=3):
+    a = sp.random(M, K, density=density, format='csr', dtype=np.float32, random_state=np.random.RandomState(seed))
+    a.sort_indices()
+    return a
+
+
+def _nonpointer_fields(st):
+    """The fields of a CsPlan that are not addresses (those are reduced to null / set)."""
+    return {n: (getattr(st, n) is not None) if t is C.c_void_p else getattr(st, n) for n, t in st._fields_}
+
+
+@pytest.fixture(scope="module")
+def six_plans(tmp_path_factory):
+    """One plan of each kind (round_tiles=64: 1,024 rows per round, so 300 rows already split, pad and take fix-up slots)
+    and a sixth loaded from the cache."""
+    import torch
+    from stochastic_gcn_amd.ops import ColumnSweepCSR as CS
+    cpu, a, lab = torch.device("cpu"), _small(), (np.arange(300) // 40).astype(np.int32)
+    plans = {"g1": CS(a, cpu, round_tiles=64), "labelled": CS(a, cpu, T=48, col_labels=lab, row_labels=lab, round_tiles=64),
+             "g2": CS(a, cpu, G=2, round_tiles=64), "g4": CS(a, cpu, G=4, align=300, round_tiles=64),
+             "ranged": CS(_small(200, 8192, 0.01, 5), cpu, col_ranges=2, round_tiles=64)}
+    path = str(tmp_path_factory.mktemp("plans") / "g2.npz")
+    plans["g2"].save(path, "k")
+    plans["loaded"] = CS.load(path, cpu, "k", g=2)
+    assert plans["loaded"] is not None
+    return plans
+
+
+def test_every_kind_of_plan_has_the_same_attributes(six_plans):
+    names = {k: set(vars(p)) for k, p in six_plans.items()}
+    assert all(v == names["g1"] for v in names.values()), {k: sorted(v ^ names["g1"]) for k, v in names.items()}
+    for kind, p in six_plans.items():
+        assert p.struct(64).G == p.G and p.struct(64, bf16=True).ntiles == p.ntiles, kind
+    # the defaults of a path that has no value of its own
+    g1, g2, rg, ld = (six_plans[k] for k in ("g1", "g2", "ranged", "loaded"))
+    assert (g1.align, g1.pad_fraction, g1.range_cuts, g1.ranged) == (None, 0.0, None, 0)
+    assert (g2.range_cuts, g2.ranged) == (None, 0) and g2.align is not None and g2.T is not None and g2.setup_s is not None
+    assert (rg.align, rg.pad_fraction, rg.ranged) == (None, 0.0, 2) and len(rg.range_cuts) == 3
+    assert (ld.T, ld.align, ld.setup_s, ld.range_cuts, ld.ranged) == (None, None, None, None, 0)
+    assert ld.pad_fraction == g2.pad_fraction
+
+
+def test_a_plan_hands_out_its_live_clock_dicts_one_per_operand_type(six_plans):
+    from stochastic_gcn_amd.ops import ColumnSweepCSR as CS
+    for kind, p in six_plans.items():
+        for name in ("pace", "tuned_ms", "_guard", "pace_b16", "tuned_ms_b16", "_guard_b16"):
+            assert getattr(p, name) is getattr(p, name) and getattr(p, name) == {}, (kind, name)
+        assert p.pace is p.clock(False).pace and p.pace_b16 is p.clock(True).pace and p.pace is not p.pace_b16
+        assert p._guard is p.clock(False).guard and p.tuned_ms_b16 is p.clock(True).tuned_ms
+        p.pace_b16[64] = 140
+        try:
+            assert p.pace == {} and p.clock(True).pace == {64: 140}
+            assert p.struct(64, bf16=True).pace_ns_per_nnz == (-1 if p.grouped else 140)
+            assert p.struct(64).pace_ns_per_nnz == (-1 if p.grouped else 0)
+        finally:
+            del p.pace_b16[64]                       # (the plans are shared by the tests of this module)
+    assert "getattr(self," not in inspect.getsource(CS)
+
+
+@pytest.mark.parametrize("G", [1, 2, 4])
+def test_a_saved_plan_loads_as_the_plan_that_was_built(tmp_path, G):
+    import torch
+    from stochastic_gcn_amd.ops import ColumnSweepCSR as CS
+    cpu = torch.device("cpu")
+    A = CS(_small(), cpu, G=G, round_tiles=64)
+    assert A.nfix > 0 and A.ntiles > 1
+    A.pace[64], A.tuned_ms[64], A.pace_b16[64], A.tuned_ms_b16[64] = 250, 1.5, 140, 0.9
+    path = str(tmp_path / "plan.npz")
+    A.save(path, "k")
+    B = CS.load(path, cpu, "k", g=G)
+    assert B is not None and CS.load(path, cpu, "k", g=3) is None and CS.load(path, cpu, "other", g=G) is None
+    for k in ("tile_ptr", "colrow", "val", "tile_rows", "tile_slots", "fix", "warp"):
+        x, y = getattr(A, k), getattr(B, k)
+        assert (x is None and y is None) or (x.dtype == y.dtype and torch.equal(x, y)), k
+    assert np.array_equal(A._tile_nnz, B._tile_nnz)
+    for bf16 in (False, True):
+        assert _nonpointer_fields(A.struct(64, bf16)) == _nonpointer_fields(B.struct(64, bf16))
+        assert A.struct(64, bf16).pace_ns_per_nnz == (140 if bf16 else 250)
+        assert np.array_equal(A._hint, B._hint)
+    assert A.variant(64) == B.variant(64)
