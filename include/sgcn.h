@@ -52,7 +52,8 @@ const char* sgcn_last_error(void);
  *       (additive, still v16: sgcn_moments_*; the bfloat16 history -- sgcn_vr_aggregate_h16 / _pre_h16 / _post_h16,
  *       sgcn_scatter_rows_h16, sgcn_gather_rows_h16, sgcn_hist_apply_h16, step ops 48 .. 53; the losses over a row
  *       subset of N-row tables -- sgcn_softmax_ce_rows_f32 / sgcn_sigmoid_ce_rows_f32; a bfloat16 dense operand for the
- *       static-graph products -- sgcn_spmm_csr_b16 / _csr_add_b16 / sgcn_spmm_cs_b16 / sgcn_spmm_cs_variant_b16) */
+ *       static-graph products -- sgcn_spmm_csr_b16 / _csr_add_b16 / sgcn_spmm_cs_b16 / sgcn_spmm_cs_variant_b16; the staleness
+ *       of a history -- sgcn_hist_error_f32 / _h16 / _ws_doubles) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -650,6 +651,22 @@ int sgcn_moments_add_f32(const float* dev_x, int64_t n, int64_t count, double* d
  * The np.mean(...) scalars the study prints                             gcn/stats.py, gcn/train.py:256-276 */
 int sgcn_moments_summary_f64(const double* dev_mean_a, const double* dev_m2_a, int64_t count_a, const double* dev_mean_b,
                              int64_t n, double* dev_out3, void* stream);
+
+/* ---- staleness of a control-variate history (--history_error) -------------------------------------------------------
+ * x: the exact activations (n x d fp32, row pitch ldx >= d: a column-offset view is fine, columns >= d are never read),
+ * h: the stored history (fp32, pitch ldh >= d; _h16: the bfloat16 history's storage contract above -- uint16, ldh in
+ * elements, ldh % 8 == 0, 16-byte aligned base -- widened exactly).
+ *   out4[0] = sum (x - h)^2   out4[1] = sum x^2   out4[2] = max |x - h|   out4[3] = number of rows with any x != h
+ * as fp64, every difference and square taken in fp64 ((double)x - (double)h is exact).  The grid is fixed (1,024
+ * workgroups on any device): one wave per row, lanes striding the columns with fp64 partials, a fixed tree per workgroup
+ * into ws (sgcn_hist_error_ws_doubles() doubles, caller-owned), then ONE workgroup adds the partials in index order.  No
+ * atomics: bitwise the same on every call.  n == 0 (or d == 0): out4 = 0 without a launch.
+ * The relative staleness of a layer is sqrt(out4[0] / out4[1]). */
+int64_t sgcn_hist_error_ws_doubles(void);
+int sgcn_hist_error_f32(const float* dev_x, int64_t ldx, const float* dev_h, int64_t ldh, int64_t n, int32_t d,
+                        double* dev_out4, double* dev_ws, void* stream);
+int sgcn_hist_error_h16(const float* dev_x, int64_t ldx, const uint16_t* dev_h, int64_t ldh, int64_t n, int32_t d,
+                        double* dev_out4, double* dev_ws, void* stream);
 
 /* ---- deterministic dropout (--det_dropout; gcn/layers.py:141-202, 236-248, 320-349, 425-428): the element-wise and
  * row-wise pieces of the moment-propagation variant, forward and backward (autodiff of the reference's formulas).  The

@@ -223,6 +223,10 @@ SIGNATURES = {
     "sgcn_adam_f32": (C.c_int, [P, P, P, P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, P]),
     "sgcn_moments_add_f32": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P]),
     "sgcn_moments_summary_f64": (C.c_int, [P, P, C.c_int64, P, C.c_int64, P, P]),
+    # staleness of a history (--history_error): (x, ldx, h, ldh, n, d, out4, ws, stream)
+    "sgcn_hist_error_ws_doubles": (C.c_int64, []),
+    "sgcn_hist_error_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int32, P, P, P]),
+    "sgcn_hist_error_h16": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int32, P, P, P]),
     "sgcn_sched_create": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.POINTER(C.c_void_p)]),
     "sgcn_sched_destroy": (None, [C.c_void_p]),

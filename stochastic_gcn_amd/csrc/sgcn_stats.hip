@@ -92,6 +92,98 @@ __global__ __launch_bounds__(kBlock) void moments_summary_kernel(const double* _
     if (threadIdx.x < 3) out3[threadIdx.x] = red[threadIdx.x][0] / (double)n;     // n == 0: NaN, as np.mean of nothing
 }
 
+// ---- staleness of a control-variate history (--history_error): x = the exact activations, h = the stored table ----------
+// out4 = { sum (x - h)^2, sum x^2, max |x - h|, rows with any x != h }, every difference and square in fp64 ((double)x -
+// (double)h is exact).  A FIXED grid (kHistErrBlocks workgroups whatever the device): wave w of the grid takes rows w, w +
+// kHistErrWaves, ..., four of them per trip (their loads are requested before any is added), its lanes stride the columns and
+// keep fp64 partials; a workgroup folds its 256 lanes by a fixed tree into ws[4 b ..], and hist_error_final_kernel -- one
+// workgroup -- adds the kHistErrBlocks partials in index order.  No atomics: the same bits on every call.
+constexpr int kHistErrBlocks = 1024;
+constexpr int kHistErrWaves = kHistErrBlocks * (kBlock / kWave);
+constexpr int kHistErrRows = 4;
+
+__device__ __forceinline__ float hist_elem(const float* p) { return *p; }
+__device__ __forceinline__ float hist_elem(const uint16_t* p) { return __uint_as_float((uint32_t)*p << 16); }
+
+template <class HT>
+__global__ __launch_bounds__(kBlock) void hist_error_kernel(const float* __restrict__ x, int64_t ldx, const HT* __restrict__ h,
+                                                            int64_t ldh, int64_t n, int32_t d, double* __restrict__ ws) {
+    __shared__ double red[4][kBlock];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    double s_err = 0.0, s_ref = 0.0, s_max = 0.0, s_rows = 0.0;
+    for (int64_t r0 = wave; r0 < n; r0 += (int64_t)kHistErrRows * kHistErrWaves) {      // (wave-uniform)
+        int off[kHistErrRows] = {};
+        for (int c = lane; c < d; c += kWave) {
+            float xv[kHistErrRows], hv[kHistErrRows];
+#pragma unroll
+            for (int u = 0; u < kHistErrRows; u++) {
+                const int64_t r = r0 + (int64_t)u * kHistErrWaves;
+                const bool in = r < n;
+                xv[u] = in ? x[r * ldx + c] : 0.f;
+                hv[u] = in ? hist_elem(h + r * ldh + c) : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < kHistErrRows; u++) {
+                const double xd = (double)xv[u], e = xd - (double)hv[u];
+                s_err = __dadd_rn(s_err, __dmul_rn(e, e));          // (no contraction: each square is rounded, then added)
+                s_ref = __dadd_rn(s_ref, __dmul_rn(xd, xd));
+                s_max = fmax(s_max, fabs(e));
+                off[u] |= xv[u] != hv[u];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kHistErrRows; u++)
+            if (__any(off[u]) && lane == 0) s_rows += 1.0;
+    }
+    red[0][threadIdx.x] = s_err;
+    red[1][threadIdx.x] = s_ref;
+    red[2][threadIdx.x] = s_max;
+    red[3][threadIdx.x] = s_rows;
+    __syncthreads();
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + s];
+            red[1][threadIdx.x] += red[1][threadIdx.x + s];
+            red[2][threadIdx.x] = fmax(red[2][threadIdx.x], red[2][threadIdx.x + s]);
+            red[3][threadIdx.x] += red[3][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) ws[4 * (int64_t)blockIdx.x + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(kBlock) void hist_error_final_kernel(const double* __restrict__ ws, double* __restrict__ out4) {
+    __shared__ double part[4 * kHistErrBlocks];
+    for (int i = threadIdx.x; i < 4 * kHistErrBlocks; i += kBlock) part[i] = ws[i];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int q = threadIdx.x;
+        double a = 0.0;
+        for (int b = 0; b < kHistErrBlocks; b++) a = q == 2 ? fmax(a, part[4 * b + q]) : a + part[4 * b + q];
+        out4[q] = a;
+    }
+}
+
+template <class HT>
+int hist_error_launch(const char* who, const float* x, int64_t ldx, const HT* h, int64_t ldh, int64_t n, int32_t d, double* out4,
+                      double* ws, hipStream_t st) {
+    SGCN_REQUIRE(n >= 0 && d >= 0, "%s: negative size", who);
+    SGCN_REQUIRE(out4 && aligned8(out4), "%s: out4 must be an 8-byte aligned device address", who);
+    if (n == 0 || d == 0) {
+        SGCN_HIP_TRY(hipMemsetAsync(out4, 0, 4 * sizeof(double), st));
+        return SGCN_OK;
+    }
+    SGCN_REQUIRE(x && h && ws, "%s: null operand", who);
+    SGCN_REQUIRE(aligned8(ws) && (reinterpret_cast<uintptr_t>(x) & 3u) == 0, "%s: operand not aligned to its element size", who);
+    SGCN_REQUIRE(ldx >= d && ldh >= d, "%s: leading dimension too small", who);
+    hipLaunchKernelGGL(hist_error_kernel<HT>, dim3(kHistErrBlocks), dim3(kBlock), 0, st, x, ldx, h, ldh, n, d, ws);
+    SGCN_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(hist_error_final_kernel, dim3(1), dim3(kBlock), 0, st, ws, out4);
+    SGCN_HIP_TRY(hipGetLastError());
+    return SGCN_OK;
+}
+
 }  // namespace
 }  // namespace sgcn
 
@@ -132,4 +224,20 @@ extern "C" int sgcn_moments_summary_f64(const double* mean_a, const double* m2_a
                        (double)count_a, mean_b, n, out3);
     SGCN_HIP_TRY(hipGetLastError());
     return SGCN_OK;
+}
+
+extern "C" int64_t sgcn_hist_error_ws_doubles(void) { return 4 * (int64_t)kHistErrBlocks; }
+
+extern "C" int sgcn_hist_error_f32(const float* x, int64_t ldx, const float* h, int64_t ldh, int64_t n, int32_t d, double* out4,
+                                   double* ws, void* stream) {
+    SGCN_REQUIRE(!h || (reinterpret_cast<uintptr_t>(h) & 3u) == 0, "hist_error_f32: history not aligned to its element size");
+    return hist_error_launch<float>("hist_error_f32", x, ldx, h, ldh, n, d, out4, ws, (hipStream_t)stream);
+}
+
+extern "C" int sgcn_hist_error_h16(const float* x, int64_t ldx, const uint16_t* h, int64_t ldh, int64_t n, int32_t d, double* out4,
+                                   double* ws, void* stream) {
+    // (the bfloat16 history's storage contract, include/sgcn.h: pitch in elements, a multiple of 8, a 16-byte aligned base)
+    SGCN_REQUIRE(!h || (ldh % 8 == 0 && aligned16(h)),
+                 "hist_error_h16: a bfloat16 history needs ldh %% 8 == 0 and a 16-byte aligned base (ldh %lld)", (long long)ldh);
+    return hist_error_launch<uint16_t>("hist_error_h16", x, ldx, h, ldh, n, d, out4, ws, (hipStream_t)stream);
 }

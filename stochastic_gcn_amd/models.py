@@ -615,15 +615,19 @@ class GCN(Model):
         m = sp.csr_matrix((np.asarray(w, np.float32), np.asarray(a.col), np.asarray(a.rowptr)), shape=tuple(a.shape))
         return ops.DeviceCSR.from_scipy(m, self.device, with_plan=True, with_transpose=True)
 
-    def forward(self, cur):
+    dense_fp32 = False      # True: this model's static passes keep the fp32 dense kernels under --dense_dtype bf16 (exact_history.py)
+
+    def forward(self, cur, stop=None):
+        """``stop``: run layers[:stop] only (the exact history pass needs nothing behind the last aggregator's input)."""
         self.cur = cur
         # --dense_dtype bf16: the dense layers of a pass over a static batch multiply in bfloat16 (layers.Dense); any other
-        # batch of the same model -- a sampled step beside an exact evaluation -- keeps the fp32 kernels
-        bf16 = dense_bf16() and isinstance(cur, StaticCur)
+        # batch of the same model -- a sampled step beside an exact evaluation -- keeps the fp32 kernels, and so does a
+        # model that opts out (``dense_fp32``: the history passes are fp32 whatever the full-graph modes run in)
+        bf16 = dense_bf16() and isinstance(cur, StaticCur) and not self.dense_fp32
         for layer in self.layers:
             layer.mul_bf16 = bf16
         self.activations = [cur.inputs]
-        for layer in self.layers:
+        for layer in self.layers[:stop]:
             self.activations.append(layer(self.activations[-1]))
         self.outputs = self.activations[-1]
         return self.outputs

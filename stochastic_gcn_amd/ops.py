@@ -14,6 +14,7 @@ Reference seams replaced:
   spmm_cs         the same product as spmm for a STATIC graph (column sweep, ColumnSweepCSR)
   moments_add / moments_summary   Stat.add + np.mean / np.std of the kept draws   gcn/stats.py,
                   gcn/train.py:241-276 (running fp64 statistics on the device, stats.DeviceStat)
+  history_error   how far a stored history is from the exact activations (no reference counterpart; exact_history.py)
 """
 import ctypes as C
 import time
@@ -534,6 +535,40 @@ def moments_summary(mean_a, m2_a, count_a, mean_b=None, out=None):
         out = torch.empty(3, dtype=torch.float64, device=mean_a.device)
     check(lib.sgcn_moments_summary_f64(mean_a.data_ptr(), m2_a.data_ptr(), int(count_a), _ptr(mean_b), n,
                                        _dev(out, torch.float64, "out").data_ptr(), _stream()))
+    return out
+
+
+# ---- staleness of a control-variate history (sgcn_stats.hip; --history_error) -----------------------------------------------
+_HIST_ERR_WS = {}
+
+
+def history_error(x, H, out=None):
+    """Device fp64[4] = {sum (x - H)^2, sum x^2, max |x - H|, rows with any x != H} of the exact activations ``x`` (fp32 rows,
+    a pitched view is fine) against the stored history ``H`` (fp32 or bfloat16, widened exactly): every difference and square
+    in fp64, a fixed grid and summation order -- the same bits on every call (sgcn_hist_error_f32 / _h16).  Nothing is
+    synchronised; the relative staleness is sqrt(out[0] / out[1]) once the vector is on the host."""
+    if x.dim() != 2 or tuple(x.shape) != tuple(H.shape):
+        raise ValueError("history_error: x has shape %s, the history %s" % (tuple(x.shape), tuple(H.shape)))
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if n == 0:          # (the strides of an empty tensor say nothing: the library zeroes out4 without reading a pitch)
+        _dev(x, torch.float32, "x")
+        if H.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("H must be torch.float32 or torch.bfloat16, got %s" % H.dtype)
+        h16 = H.dtype == torch.bfloat16
+        xp, ldx, hp, ldh = None, d, None, (d + 7) // 8 * 8
+    else:
+        xp, ldx = _rows2d(x, "x")
+        hp, ldh, h16 = _hist2d(H, "H")
+    if not H.is_cuda:
+        raise RuntimeError("H must live in HBM (got a %s tensor): the SpMM/history path has no CPU fallback" % (H.device,))
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=x.device)
+    # one workspace per device: the two launches of a call run back to back on the caller's stream
+    ws = _HIST_ERR_WS.get(x.device)
+    if ws is None:
+        ws = _HIST_ERR_WS[x.device] = torch.empty(int(lib.sgcn_hist_error_ws_doubles()), dtype=torch.float64, device=x.device)
+    check((lib.sgcn_hist_error_h16 if h16 else lib.sgcn_hist_error_f32)(
+        xp, ldx, hp, ldh, n, d, _dev(out, torch.float64, "out").data_ptr(), ws.data_ptr(), _stream()))
     return out
 
 

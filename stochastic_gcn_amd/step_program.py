@@ -821,6 +821,7 @@ class StepProgram(object):
             raise Unsupported("model output is not a plain activation")
         nL = self.rows[self.L]
         c = logits.cols
+        self.logits = logits                  # (arena activation: tensor_of(self.logits, rows) after a run)
         lab_b = self._pb.o_labels
         train = m.is_training
         stats, self.stats_off = self._alloc_vec(4 + (2 if train else 3) * nL.cap)     # (evaluation: + the rows' classes)

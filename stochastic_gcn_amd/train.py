@@ -25,7 +25,7 @@ import scipy.sparse as sp
 import torch
 
 from . import ops
-from .flags import FLAGS, check_history_dtype
+from .flags import FLAGS, check_exact_history, check_history_dtype
 from .full_batch import StaticBatch, StaticMatrix, check_full_batch, full_batch_bf16
 from .models import make_template
 from .parallel import DataParallel
@@ -278,6 +278,9 @@ class Trainer(object):
         torch.manual_seed(FLAGS.seed)
         # (--full_batch / --test_full_batch with an estimator, a sampler option or several ranks: refused before a device is touched)
         self.full_batch, self.test_full_batch = check_full_batch(world=int(os.environ.get("WORLD_SIZE", "1")))
+        # (--history_init exact / --history_refresh / --history_error without a history, with two of them, on several ranks: too)
+        self.history_init_exact, self.history_refresh, self.history_error = \
+            check_exact_history(world=int(os.environ.get("WORLD_SIZE", "1")))
         if not torch.cuda.is_available():
             raise RuntimeError("training needs an MI355X (no CPU fallback for the SpMM/history path)")
         check_history_dtype()             # (--history_dtype bf16 with --det_dropout: refused before anything is built)
@@ -392,6 +395,16 @@ class Trainer(object):
                                                   int(FLAGS.seed) + 1000 * k, cv=FLAGS.test_cv,
                                                   importance=FLAGS.test_importance))
             self.eval_slots = [StagingSlot(pin=True) for _ in range(ring if nthr > 1 else 4)]
+        # the exact history passes (exact_history.py): one twin + matrix per model whose history they fill or measure
+        self.exact_train = self.exact_test = None
+        if FLAGS.cv and (self.history_init_exact or self.history_refresh or self.history_error):
+            t = time()
+            self.exact_train = self._exact_history(self.train_model, train_adj, 'train', caches[0])
+            self.static_setup_s += time() - t
+        if FLAGS.test_cv and self.history_init_exact:
+            t = time()
+            self.exact_test = self._exact_history(self.test_model, full_adj, 'test', caches[1])
+            self.static_setup_s += time() - t
         self.cost_val = []
         self.avg_loss = Averager(1)
         self.avg_acc = Averager(1)
@@ -406,10 +419,50 @@ class Trainer(object):
                            max(widths or [FLAGS.hidden1]), cache_path,
                            # (passed only when set: the fp32 call keeps the argument list tests/test_full_batch.py records)
                            **(dict(bf16=True) if full_batch_bf16() else {}))
+        self.__dict__.setdefault('_static_matrices', []).append((adj, mat))      # (an exact history pass over the same adjacency shares it)
         labels = self.__dict__.get('_labels_dev')          # ONE N x C table on the device for both static batches
         if labels is None:
             labels = self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
         return StaticBatch(mat, labels, np.sort(np.asarray(rows)), model.L, self.device)
+
+    # ---- the exact history passes (exact_history.py) ------------------------------------------------
+    def _exact_history(self, model, adj, which, cache_path):
+        """The exact pass of one history-owning model over its own adjacency: the matrix another pass or --test_full_batch
+        already built for that adjacency where its operand is fp32, else one of its own (the plan-cache path of the
+        adjacency; 'auto' on the number of passes the flags imply)."""
+        from .exact_history import ExactHistory, history_passes, make_matrix
+        shared = self.__dict__.setdefault('_static_matrices', [])
+        mat = next((m for a, m in shared if a is adj and not getattr(m, 'bf16', False)), None)
+        if mat is None:
+            mat = make_matrix(adj, self.device, model, history_passes(which), cache_path)
+            shared.append((adj, mat))
+        return ExactHistory(model, mat)
+
+    def history_pass(self, epoch):
+        """What happens to the histories before training epoch ``epoch`` (0-based), ahead of train_epoch() so that the epoch
+        lines and their time= token are untouched: --history_init exact fills both models' histories before epoch 0,
+        --history_refresh K overwrites the training model's before epochs K, 2K, ..., --history_error measures it before
+        every epoch -- ONE exact forward per model and epoch at most, the error taken from the forward that is then
+        assigned.  Prints one line per layer and returns the record kept in last_epoch['history'] (None: nothing to do)."""
+        from .exact_history import refresh_due
+        if epoch == 0 and self.exact_test is not None:
+            r = self.exact_test.run(assign=True)
+            self.log('[sgcn] history: test model filled by one exact pass | pass {:.5f} s'.format(r['pass_s']))
+        ex = self.exact_train
+        if ex is None:
+            return None
+        assign = (epoch == 0 and self.history_init_exact) or refresh_due(epoch, self.history_refresh)
+        if not (assign or self.history_error):
+            return None
+        r = ex.run(measure=self.history_error, assign=assign)
+        r['epoch'] = epoch + 1
+        for l in range(self.train_model.L):
+            e = r['layers'][l] if r['layers'] is not None else None
+            self.log('[sgcn] history: epoch {:04d} layer {}'.format(epoch + 1, l)
+                     + (' rel_err={:.6e} max_err={:.6e} rows_off={}'.format(e['rel_err'], e['max_err'], e['rows_off'])
+                        if e is not None else '')
+                     + (' | refreshed' if assign else '') + ' | pass {:.5f} s'.format(r['pass_s']))
+        return r
 
     def _weights_version(self):
         """Changes whenever the shared weights do: Adam steps (either model class steps through adam_t) and in-place torch
@@ -665,7 +718,10 @@ class Trainer(object):
             return
         log('Start training...')
         for epoch in range(100000000):
+            hist = self.history_pass(epoch)
             t, tsch = self.train_epoch()
+            if hist is not None:
+                self.last_epoch['history'] = hist
             cost, acc, micro, macro, duration = self.evaluate(self.val_d)
             self.cost_val.append(cost)
             cost_val = self.cost_val
