@@ -20,12 +20,11 @@ The passes are fp32 whatever --dense_dtype / --full_batch_dtype say: those belon
 import math
 from time import time
 
-import numpy as np
 import torch
 
 from . import ops
 from .flags import FLAGS
-from .full_batch import StaticBatch, StaticMatrix
+from .full_batch import StaticBatch, model_matrix
 from .layers import PlainAggregator, dense_of
 from .models import Model
 from .plaingcn import PlainGCN
@@ -83,40 +82,21 @@ class ExactTwin(PlainGCN):
         assert len(self.agg_index) == owner.L
 
 
-class _ForwardBatch(StaticBatch):
-    """A static batch for forward passes only: no label table and no loss rows on the device."""
-
-    def __init__(self, matrix, L, device):
-        N = int(matrix.shape[0])
-        if matrix.shape[0] != matrix.shape[1]:
-            raise ValueError("a static batch needs a square (vertex x vertex) matrix")
-        self.N, self.L, self.matrix, self.device = N, int(L), matrix, device
-        self.dropout = 0.0
-        self.host_rows = self.rows = self.labels = None
-        self.host_field = np.arange(N, dtype=np.int32)
-        field = torch.from_numpy(self.host_field).to(device)
-        ones = torch.ones(N, dtype=torch.float32, device=device)
-        self.fields, self.scales, self.adj = [field] * (self.L + 1), [ones] * self.L, [matrix] * self.L
-        nnz = int(getattr(matrix, 'nnz', 0))
-        self.sizes = dict(adj=[nnz] * self.L, fadj=[0] * self.L, fields=[N] * (self.L + 1))
-
-
 def make_matrix(adj, device, owner, passes, cache_path=None, kernel=None):
     """The StaticMatrix of an exact history pass over ``adj``: fp32 operand always; the kernel from --full_batch_kernel;
     'auto' weighs the plan against passes x (L - 1) products -- a pass stops at the LAST aggregator's input, so it multiplies
     the matrix L - 1 times (not at all for the two-layer pre-processed recipes)."""
-    widths = [owner.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(max(owner.L - 1, 1))]
-    return StaticMatrix(adj, device, FLAGS.full_batch_kernel if kernel is None else kernel,
-                        int(passes) * max(owner.L - 1, 0), max(widths), cache_path, bf16=False)
+    return model_matrix(adj, device, owner, int(passes) * max(owner.L - 1, 0), cache_path, kernel, bf16=False,
+                        layers=owner.L - 1)
 
 
 class ExactHistory(object):
     def __init__(self, owner, matrix):
-        if getattr(matrix, 'bf16', False):
+        if matrix.bf16:
             raise ValueError("the exact history pass needs an fp32-operand matrix")
         self.owner, self.matrix = owner, matrix
         self.twin = ExactTwin(owner)
-        self.batch = _ForwardBatch(matrix, owner.L, owner.device)
+        self.batch = StaticBatch(matrix, None, None, owner.L, owner.device)       # (forward only: no labels, no loss rows)
         self.passes = 0
 
     def forward(self, full=False):

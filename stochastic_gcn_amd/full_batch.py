@@ -6,13 +6,16 @@ multiplies the SAME N x N matrix, forward by ``A`` and backward by ``A^T``, once
 column sweep, the LDS sweep and their planner / autotuner / plan cache were built for (bench.py times exactly these
 two products).
 
-  StaticMatrix   one adjacency with a plan built once, a lazily built transpose (ops.transpose_host) and the product
-                 method PlainAggregator calls (``out=`` with a column-offset view, ``add=`` / ``add_rows=``);
-                 dispatches to ops.spmm / ops.spmm_cs / ops.spmm_lds; with ``bf16`` (--full_batch_dtype bf16) every product
-                 rounds its dense operand into a bfloat16 scratch table and gathers from there (sgcn_spmm_*_b16)
+  StaticMatrix   one adjacency with a plan built once and a lazily built transpose (ops.transpose_host): it alone chooses the
+                 kernel, tunes and stores the plan and dispatches to ops.spmm / ops.spmm_cs / ops.spmm_lds.  ``multiply`` is
+                 the plain product (train.pp_products); ``product`` is the method PlainAggregator calls (``out=`` with a
+                 column-offset view, ``add=`` / ``add_rows=``): it decides on alignment and, with ``bf16`` (--full_batch_dtype
+                 bf16), rounds the dense operand into a bfloat16 scratch table the kernel gathers from (sgcn_spmm_*_b16)
+  model_matrix   the StaticMatrix of one model's aggregation layers (the operand width its plan is made for)
+  static_kernel_for   the cost model 'auto' decides by; train.py builds on this module, never the other way round
   StaticBatch    what Model.upload / get_data accept in place of a PackedBatch: fields[l] = arange(N), unit scales,
                  the N x C label table, and ``rows`` -- the sorted subset of vertices the loss runs over
-                 (ops.softmax_ce / sigmoid_ce ``rows=``)
+                 (ops.softmax_ce / sigmoid_ce ``rows=``); without labels: a batch for forward passes only (exact_history.py)
 """
 import numpy as np
 import torch
@@ -78,6 +81,38 @@ def dense_bf16(flags=None):
     return getattr(FLAGS if flags is None else flags, 'dense_dtype', 'fp32') == 'bf16'
 
 
+# What the static-graph kernels cost end to end on the MI355X (profiles/r60_bench_setup.json, S-Reddit: 23.2 M nonzeros,
+# d = 602, 16 host cores): the row-gather kernel needs the CSR in HBM and a row-pointer pass (5 ms) and takes 7.66 ms per
+# product; the column sweep needs its host plan + upload (0.185 s: 8 ns per nonzero), a clock autotune worth ~62 products,
+# and takes 0.40 of the row kernel's time per product.
+# (The constants were fitted with fp32 operands and serve --full_batch_dtype bf16 unchanged: the sweep's product
+# with a bfloat16 operand takes 0.835 of the fp32 one at d = 602 (profiles/spmm_b16_products.jsonl); the row kernel's bf16 time
+# is not measured, so a bf16 set would move one side of the ratio only.)
+CS_PLAN_S_PER_NNZ = 8.0e-9
+CS_AUTOTUNE_PRODUCTS = 62
+CS_TIME_RATIO = 0.40
+ROWS_S_PER_NNZ_FLOAT = 7.66e-3 / (23173306 * 602.0)
+
+
+def static_kernel_for(nnz, d, products):
+    """'rows' or 'cs': the kernel with the lower expected END-TO-END time for `products` products of one static matrix
+    with a d-wide dense operand -- setup included.  The reference computes each PP product once (gcn/utils.py:321-322, the
+    result cached in the dataset's .npz), and for one product no plan pays: the column sweep breaks even at ~83 products of
+    S-Reddit (a full-batch model's layers over a few epochs), which is what bench.py reports as
+    setup.products_to_break_even_vs_rows_kernel."""
+    t_rows = ROWS_S_PER_NNZ_FLOAT * nnz * d
+    rows = products * t_rows
+    cs = CS_PLAN_S_PER_NNZ * nnz + (CS_AUTOTUNE_PRODUCTS + products) * CS_TIME_RATIO * t_rows
+    return 'cs' if cs < rows else 'rows'
+
+
+def full_batch_products(which):
+    """How many times the plan of a full-graph matrix will run (what static_kernel_for weighs its setup against).  SGDTrain
+    leaves on `epoch > FLAGS.epochs` (gcn/train.py:234), i.e. after epochs + 2 epochs: 'train' -- one step in each of them;
+    'full' -- one evaluation in each of them and the test."""
+    return int(FLAGS.epochs) + 2 if which == 'train' else int(FLAGS.epochs) + 3
+
+
 def _aligned(t):
     """Rows of a 2-D fp32 view on 16-byte boundaries (what the sweep kernels' float4 accesses need)."""
     return t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % 4 == 0)
@@ -85,10 +120,10 @@ def _aligned(t):
 
 class StaticMatrix(object):
     """A static sparse matrix on the device, multiplied many times: ``kernel`` is 'rows' (the row-gather kernel on a
-    DeviceCSR), 'cs' (column sweep) or 'lds' (LDS-staged sweep + residual), or 'auto': train.static_kernel_for(nnz, d,
-    products) with ``products`` the number of times the plan will run -- and for a large graph with communities
-    ops.LdsSweepCSR.for_graph, exactly as train.pp_products chooses.  ``d`` is the operand width the choice (and the
-    column sweep's lane grouping) is made for.
+    DeviceCSR), 'cs' (column sweep) or 'lds' (LDS-staged sweep + residual), or 'auto': static_kernel_for(nnz, d, products)
+    with ``products`` the number of times the plan will run -- and for a large graph with communities and no plan cache
+    ops.LdsSweepCSR.for_graph.  ``d`` is the operand width the choice (and the column sweep's lane grouping) is made for.
+    Every static-graph product of the package is planned, tuned and run here.
 
     ``bf16``: every product rounds ``x`` to nearest even into a bfloat16 scratch table -- one per operand width, allocated
     once and reused every epoch -- and runs the kernel's bfloat16-operand form: half the operand's bytes per nonzero, the
@@ -119,9 +154,10 @@ class StaticMatrix(object):
             self._plan = ops.LdsSweepCSR(a, self.device, host=ops.LdsSweepCSR.auto_host(a, labels))
             return 'lds'
         if kernel == 'auto':
-            from . import train            # (late: train imports this module)
-            if train.static_kernel_for(self.nnz, d, self.products) == 'rows':
+            if static_kernel_for(self.nnz, d, self.products) == 'rows':
                 return 'rows'
+            # a large graph WITH communities (>= 90 % of its nonzeros inside tiles that share their columns): the LDS-staged
+            # sweep + the column sweep on the rest; anything else: the column sweep alone
             if self.cache_path is None and self.nnz >= 2000000 and d >= 128 and not self.bf16:
                 self._plan = ops.LdsSweepCSR.for_graph(a, self.device)
                 if self._plan is not None:
@@ -182,27 +218,55 @@ class StaticMatrix(object):
             return 'rows'
         return self.kernel
 
+    def multiply(self, x, out=None, beta=0.0, kernel=None):
+        """out = A x + beta out on ``kernel`` -- the matrix's own, or 'rows' -- with ``x`` as it is handed over: no alignment
+        decision and no rounding (``product`` makes both; train.pp_products hands over a width that is no multiple of 4 on
+        a padded pitch, which the sweeps take).  A sweep tunes its clock on the first product of a width and operand type."""
+        k, d = self.kernel if kernel is None else kernel, int(x.shape[1])
+        if k not in ('rows', self.kernel):
+            raise ValueError("this matrix runs on %r or on the row kernel, not on %r" % (self.kernel, k))
+        if k == 'rows':
+            return ops.spmm(self.rows_csr, x, out=out, beta=beta)
+        self._autotune(x, d)
+        return (ops.spmm_lds if k == 'lds' else ops.spmm_cs)(self._plan, x, out=out, beta=beta, d=d)
+
     def product(self, x, out=None, add=None, add_rows=0):
-        """out = A x (+ add on the first ``add_rows`` rows), the keyword set of ops.spmm that PlainAggregator uses.  The
-        sweep kernels have no epilogue addend: the addend is stored into ``out`` and the product runs with beta = 1."""
+        """out = A x (+ add on the first ``add_rows`` rows), the keyword set of ops.spmm that PlainAggregator uses.  The row
+        kernel adds in its epilogue; the sweep kernels have none: the addend is stored into ``out`` and the product runs
+        with beta = 1."""
         M, d = self.shape[0], int(x.shape[1])
         k = self.kernel_for(x, out)
         x = self.operand(x)
+        if add is None:
+            return self.multiply(x, out=out, kernel=k)
         if k == 'rows':
             return ops.spmm(self.rows_csr, x, out=out, add=add, add_rows=add_rows)
         if out is None:
             out = torch.empty((M, d), dtype=torch.float32, device=x.device)
-        self._autotune(x, d)
-        beta = 0.0
-        if add is not None:
-            r = int(add_rows)
-            out[:r].copy_(add[:r])
-            if r < M:
-                out[r:].zero_()
-            beta = 1.0
-        if k == 'lds':
-            return ops.spmm_lds(self._plan, x, out=out, beta=beta, d=d)
-        return ops.spmm_cs(self._plan, x, out=out, beta=beta, d=d)
+        r = int(add_rows)
+        out[:r].copy_(add[:r])
+        if r < M:
+            out[r:].zero_()
+        return self.multiply(x, out=out, beta=1.0, kernel=k)
+
+    def describe(self, d):
+        """What train.pp_products records of a product of width d: where the plan came from, the sweep clock (the column
+        sweep only), the kernel variant, the product count the kernel was chosen for."""
+        cs = self.kernel == 'cs'
+        kernel = "sgcn::spmm_seg_kernel" if self.kernel == 'rows' else \
+            self._plan.variant(d, self.bf16) if cs else self._plan.variant(d)
+        return dict(plan_from_cache=self.plan_from_cache, pace=self._plan.clock(self.bf16).pace.get(d) if cs else None,
+                    kernel=kernel, products=self.products)
+
+
+def model_matrix(adj, device, model, products, cache_path=None, kernel=None, bf16=False, layers=None):
+    """The StaticMatrix of ``adj`` for the aggregation layers of ``model``: the kernel of --full_batch_kernel unless one is
+    given, the plan made for the widest operand -- agg0_dim at layer 0, --hidden1 behind it -- of the first ``layers``
+    aggregation layers (default: all; an exact history pass counts one less).  ``products`` is the caller's to know."""
+    n = model.L if layers is None else max(int(layers), 1)
+    widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(n)]
+    return StaticMatrix(adj, device, FLAGS.full_batch_kernel if kernel is None else kernel, products,
+                        max(widths or [FLAGS.hidden1]), cache_path, bf16=bf16)
 
 
 class StaticCur(object):
@@ -213,22 +277,27 @@ class StaticCur(object):
 class StaticBatch(object):
     """The whole graph as one batch: ``fields[l] = arange(N)`` and ``scales[l] = 1`` for every l, ``labels`` the N x C
     table, ``adj[l]`` ONE shared StaticMatrix, and ``rows`` the vertices the loss runs over -- ascending and unique
-    (checked here, on the host: the loss kernel trusts it)."""
+    (checked here, on the host: the loss kernel trusts it).  Without ``labels`` and ``rows`` (both None): a batch for
+    forward passes only, with no label table and no loss rows on the device."""
 
     def __init__(self, matrix, labels, rows, L, device=None):
         N = int(matrix.shape[0])
         if matrix.shape[0] != matrix.shape[1]:
             raise ValueError("a static batch needs a square (vertex x vertex) matrix")
-        if int(labels.shape[0]) != N:
+        if labels is None and rows is not None:
+            raise ValueError("loss rows need the label table they index")
+        if labels is not None and int(labels.shape[0]) != N:
             raise ValueError("labels has %d rows, the graph %d vertices" % (int(labels.shape[0]), N))
         device = device if device is not None else getattr(matrix, 'device', None)
         self.N, self.L, self.matrix, self.device = N, int(L), matrix, device
         self.dropout = 0.0
-        self.host_rows = ops.check_loss_rows(rows, N)
         self.host_field = np.arange(N, dtype=np.int32)
         to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)      # noqa: E731
-        self.labels = labels if isinstance(labels, torch.Tensor) else to(np.asarray(labels, dtype=np.float32))
-        self.rows = to(self.host_rows)
+        self.host_rows = self.rows = self.labels = None
+        if labels is not None:
+            self.host_rows = ops.check_loss_rows(rows, N)
+            self.labels = labels if isinstance(labels, torch.Tensor) else to(np.asarray(labels, dtype=np.float32))
+            self.rows = to(self.host_rows)
         field, ones = to(self.host_field), torch.ones(N, dtype=torch.float32, device=device)
         self.fields = [field] * (self.L + 1)
         self.scales = [ones] * self.L
@@ -238,6 +307,8 @@ class StaticBatch(object):
 
     def with_rows(self, rows):
         """The same batch with the loss over another subset (validation / test ids share the matrix, labels, fields)."""
+        if self.labels is None:
+            raise ValueError("a forward-only static batch has no loss rows")
         other = StaticBatch.__new__(StaticBatch)
         other.__dict__.update(self.__dict__)
         other.host_rows = ops.check_loss_rows(rows, self.N)

@@ -26,7 +26,8 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype
-from .full_batch import StaticBatch, StaticMatrix, check_full_batch, full_batch_bf16
+from .full_batch import (StaticBatch, StaticMatrix, check_full_batch, full_batch_bf16, full_batch_products, model_matrix,
+                         static_kernel_for)         # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
 from .parallel import DataParallel
 from .plaingcn import PlainGCN
@@ -75,46 +76,14 @@ def plan_cache_paths(dataset):
     return base + ".csplan.train.npz", base + ".csplan.full.npz"
 
 
-# What the static-graph kernels cost end to end on the MI355X (profiles/r60_bench_setup.json, S-Reddit: 23.2 M nonzeros,
-# d = 602, 16 host cores): the row-gather kernel needs the CSR in HBM and a row-pointer pass (5 ms) and takes 7.66 ms per
-# product; the column sweep needs its host plan + upload (0.185 s: 8 ns per nonzero), a clock autotune worth ~62 products,
-# and takes 0.40 of the row kernel's time per product.
-# (The constants were fitted with fp32 operands and serve --full_batch_dtype bf16 unchanged: the sweep's product
-# with a bfloat16 operand takes 0.835 of the fp32 one at d = 602 (profiles/spmm_b16_products.jsonl); the row kernel's bf16 time
-# is not measured, so a bf16 set would move one side of the ratio only.)
-CS_PLAN_S_PER_NNZ = 8.0e-9
-CS_AUTOTUNE_PRODUCTS = 62
-CS_TIME_RATIO = 0.40
-ROWS_S_PER_NNZ_FLOAT = 7.66e-3 / (23173306 * 602.0)
-
-
-def static_kernel_for(nnz, d, products):
-    """'rows' or 'cs': the kernel with the lower expected END-TO-END time for `products` products of one static matrix
-    with a d-wide dense operand -- setup included.  The reference computes each PP product once (gcn/utils.py:321-322, the
-    result cached in the dataset's .npz), and for one product no plan pays: the column sweep breaks even at ~83 products of
-    S-Reddit (a full-batch model's layers over a few epochs), which is what bench.py reports as
-    setup.products_to_break_even_vs_rows_kernel."""
-    t_rows = ROWS_S_PER_NNZ_FLOAT * nnz * d
-    rows = products * t_rows
-    cs = CS_PLAN_S_PER_NNZ * nnz + (CS_AUTOTUNE_PRODUCTS + products) * CS_TIME_RATIO * t_rows
-    return 'cs' if cs < rows else 'rows'
-
-
-def full_batch_products(which):
-    """How many times the plan of a full-graph matrix will run (what static_kernel_for weighs its setup against).  SGDTrain
-    leaves on `epoch > FLAGS.epochs` (gcn/train.py:234), i.e. after epochs + 2 epochs: 'train' -- one step in each of them;
-    'full' -- one evaluation in each of them and the test."""
-    return int(FLAGS.epochs) + 2 if which == 'train' else int(FLAGS.epochs) + 3
-
-
 def pp_products(train_adj, full_adj, features, device, cache=(None, None), stats=None, products=1):
     """train_feats = train_adj . feats, test_feats = full_adj . feats (gcn/utils.py:169-170,
-    321-322).  Dense features: an SpMM kernel on the GPU (K11), chosen by expected end-to-end time for the number of
-    times the product will run with one plan (``products``; ``static_kernel_for``): once, as in the reference -- the
-    row-gather kernel sgcn_spmm_csr_f32, no plan; many times -- the column sweep (sgcn_spmm_cs_f32, the kernel bench.py
-    times), its host plan cached beside the dataset, or for a graph with communities the LDS-staged sweep
-    (ops.LdsSweepCSR.for_graph).  Sparse features: a sparse x sparse product, done once on the host with SciPy exactly
-    like the reference."""
+    321-322).  Dense features: one product each of a StaticMatrix on the GPU (K11), which chooses the kernel by expected
+    end-to-end time for the number of times the product will run with one plan (``products``; ``static_kernel_for``): once,
+    as in the reference -- the row-gather kernel sgcn_spmm_csr_f32, no plan; many times -- the column sweep (sgcn_spmm_cs_f32,
+    the kernel bench.py times), its host plan cached beside the dataset, or for a graph with communities the LDS-staged
+    sweep (ops.LdsSweepCSR.for_graph).  Sparse features: a sparse x sparse product, done once on the host with SciPy
+    exactly like the reference."""
     if sp.issparse(features):
         return train_adj.dot(features).tocsr(), full_adj.dot(features).tocsr()
     X = features.to(device) if isinstance(features, torch.Tensor) else \
@@ -127,30 +96,13 @@ def pp_products(train_adj, full_adj, features, device, cache=(None, None), stats
     out = []
     for a, path in zip((train_adj, full_adj), cache):
         t0 = time()
-        if static_kernel_for(a.nnz, d, products) == 'rows':
-            R = ops.DeviceCSR.from_scipy(a, device)
-            out.append(ops.spmm(R, X).contiguous())
-            if stats is not None:
-                torch.cuda.synchronize()
-                stats.append(dict(plan_from_cache=False, pace=None, kernel="sgcn::spmm_seg_kernel", products=products,
-                                  end_to_end_s=time() - t0))
-            continue
-        # a large graph WITH communities (>= 90 % of its nonzeros inside tiles that share their columns): the LDS-staged
-        # sweep + the column sweep on the rest; anything else: the column sweep alone
-        L = ops.LdsSweepCSR.for_graph(a, device) if (path is None and a.nnz >= 2000000 and d >= 128) else None
-        if L is not None:
-            L.autotune(X)
-            if stats is not None:
-                stats.append(dict(plan_from_cache=False, pace=None, kernel=L.variant(d), products=products))
-            out.append(ops.spmm_lds(L, X).contiguous())
-            continue
-        A, hit = ops.ColumnSweepCSR.cached(a, device, path, G=ops.ColumnSweepCSR.choose_g(d, a.nnz / max(a.shape[0], 1), a.shape[0]))
-        if d not in A.pace:
-            A.autotune(X)               # once per plan and width; stored with the cached plan
-        A.store_if_cached()
+        m = StaticMatrix(a, device, 'auto', products, d, path)
+        out.append(m.multiply(X).contiguous())          # (multiply, not product: d % 4 != 0 on an aligned pitch still sweeps)
         if stats is not None:
-            stats.append(dict(plan_from_cache=hit, pace=A.pace.get(d), kernel=A.variant(d), products=products))
-        out.append(ops.spmm_cs(A, X).contiguous())
+            stats.append(m.describe(d))
+            if m.kernel == 'rows':
+                torch.cuda.synchronize()
+                stats[-1]['end_to_end_s'] = time() - t0
     return out[0], out[1]
 
 
@@ -360,6 +312,8 @@ class Trainer(object):
         self.train_sch = self.eval_sch = None
         self.train_schs, self.eval_schs, self.slots, self.eval_slots = [], [], [], []
         self.static_setup_s = 0.0
+        self.static_matrices = []         # (adjacency, StaticMatrix): an exact history pass over the same adjacency shares it
+        self._labels_dev = None           # ONE N x C label table on the device for both static batches
         caches = plan_cache_paths(FLAGS.dataset)
         if self.full_batch:
             # exact full-graph training: no sampler, no prefetcher, no staging slots -- one static batch over train_adj
@@ -414,16 +368,11 @@ class Trainer(object):
     def _static_batch(self, adj, which, cache_path, model, rows):
         """The static batch of one adjacency for one model: the matrix with its plan (kernel by --full_batch_kernel; auto:
         static_kernel_for on the number of times the plan will run), the label table, the loss rows."""
-        widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(model.L)]
-        mat = StaticMatrix(adj, self.device, FLAGS.full_batch_kernel, full_batch_products(which),
-                           max(widths or [FLAGS.hidden1]), cache_path,
-                           # (passed only when set: the fp32 call keeps the argument list tests/test_full_batch.py records)
-                           **(dict(bf16=True) if full_batch_bf16() else {}))
-        self.__dict__.setdefault('_static_matrices', []).append((adj, mat))      # (an exact history pass over the same adjacency shares it)
-        labels = self.__dict__.get('_labels_dev')          # ONE N x C table on the device for both static batches
-        if labels is None:
-            labels = self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
-        return StaticBatch(mat, labels, np.sort(np.asarray(rows)), model.L, self.device)
+        mat = model_matrix(adj, self.device, model, full_batch_products(which), cache_path, bf16=full_batch_bf16())
+        self.static_matrices.append((adj, mat))
+        if self._labels_dev is None:
+            self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
+        return StaticBatch(mat, self._labels_dev, np.sort(np.asarray(rows)), model.L, self.device)
 
     # ---- the exact history passes (exact_history.py) ------------------------------------------------
     def _exact_history(self, model, adj, which, cache_path):
@@ -431,11 +380,10 @@ class Trainer(object):
         already built for that adjacency where its operand is fp32, else one of its own (the plan-cache path of the
         adjacency; 'auto' on the number of passes the flags imply)."""
         from .exact_history import ExactHistory, history_passes, make_matrix
-        shared = self.__dict__.setdefault('_static_matrices', [])
-        mat = next((m for a, m in shared if a is adj and not getattr(m, 'bf16', False)), None)
+        mat = next((m for a, m in self.static_matrices if a is adj and not m.bf16), None)
         if mat is None:
             mat = make_matrix(adj, self.device, model, history_passes(which), cache_path)
-            shared.append((adj, mat))
+            self.static_matrices.append((adj, mat))
         return ExactHistory(model, mat)
 
     def history_pass(self, epoch):

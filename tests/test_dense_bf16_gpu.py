@@ -132,10 +132,8 @@ def _dense_layers(model):
 
 
 def _static_batch(case, adj, model, rows, kernel='cs'):
-    from stochastic_gcn_amd.flags import FLAGS
-    from stochastic_gcn_amd.full_batch import StaticBatch, StaticMatrix
-    widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(model.L)]
-    mat = StaticMatrix(adj, DEV, kernel, 3, max(widths or [FLAGS.hidden1]))
+    from stochastic_gcn_amd.full_batch import StaticBatch, model_matrix
+    mat = model_matrix(adj, DEV, model, 3, kernel=kernel)
     return StaticBatch(mat, case['labels'], np.sort(rows), model.L, DEV)
 
 

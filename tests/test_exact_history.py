@@ -199,13 +199,13 @@ def test_pass_count_per_flag_set():
 def test_matrix_gets_the_products_of_the_passes(monkeypatch):
     """make_matrix: fp32 operand, the kernel of --full_batch_kernel, passes x (L - 1) products -- a pass stops at the last
     aggregator's input."""
-    from stochastic_gcn_amd import exact_history
+    from stochastic_gcn_amd import exact_history, full_batch
     made = []
 
     class Rec(object):
         def __init__(self, a, device, kernel, products, d, cache_path, bf16=None):
             made.append((kernel, products, d, cache_path, bf16))
-    monkeypatch.setattr(exact_history, "StaticMatrix", Rec)
+    monkeypatch.setattr(full_batch, "StaticMatrix", Rec)            # (full_batch.model_matrix constructs it)
 
     class M(object):
         def __init__(self, L, agg0):

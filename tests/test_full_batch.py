@@ -116,6 +116,8 @@ def test_trainer_refuses_several_ranks(monkeypatch):
 
 # ---- the static batch -------------------------------------------------------------------------------------------------
 class _FakeMatrix(object):
+    bf16 = False
+
     def __init__(self, n, nnz):
         self.shape, self.nnz, self.device = (n, n), nnz, torch.device("cpu")
 
@@ -169,10 +171,10 @@ def _ring(n):
 def test_auto_asks_static_kernel_for_with_the_product_count(monkeypatch):
     """auto = static_kernel_for(nnz, d, products), products = the number of times that plan will run: the epochs for a
     training matrix (SGDTrain runs epochs + 2 of them), one evaluation per epoch and the test for full_adj."""
-    from stochastic_gcn_amd import train
+    from stochastic_gcn_amd import full_batch, train
     from stochastic_gcn_amd.full_batch import StaticMatrix
     seen = []
-    monkeypatch.setattr(train, "static_kernel_for", lambda nnz, d, products: seen.append((nnz, d, products)) or 'rows')
+    monkeypatch.setattr(full_batch, "static_kernel_for", lambda nnz, d, products: seen.append((nnz, d, products)) or 'rows')
     FLAGS.update(epochs=37)
     assert train.full_batch_products('train') == 39 and train.full_batch_products('full') == 40
     a = _ring(50)
@@ -189,26 +191,34 @@ def test_auto_asks_static_kernel_for_with_the_product_count(monkeypatch):
 
 
 def test_trainer_hands_the_counts_over(monkeypatch):
-    """Trainer._static_batch: the training matrix with the epochs, full_adj with the evaluations."""
+    """Trainer._static_batch: the training matrix with the epochs, full_adj with the evaluations, the operand type of
+    --full_batch_dtype as an ordinary keyword."""
     from stochastic_gcn_amd import full_batch, train
-    made = []
+    made, operand = [], []
 
     class Rec(object):
-        def __init__(self, a, device, kernel, products, d, cache_path):
+        def __init__(self, a, device, kernel, products, d, cache_path, bf16):
             made.append((a.shape, kernel, products, d, cache_path))
-            self.shape, self.nnz, self.device = a.shape, a.nnz, device
-    monkeypatch.setattr(train, "StaticMatrix", Rec)
+            operand.append(bf16)
+            self.shape, self.nnz, self.device, self.bf16 = a.shape, a.nnz, device, bf16
+    monkeypatch.setattr(full_batch, "StaticMatrix", Rec)            # (full_batch.model_matrix constructs it)
     FLAGS.update(epochs=12, hidden1=48, full_batch_kernel='auto')
 
     class M(object):
         L, agg0_dim = 2, 48
     tr = train.Trainer.__new__(train.Trainer)
     tr.device, tr.labels = torch.device("cpu"), np.zeros((50, 3), np.float32)
+    tr.static_matrices, tr._labels_dev = [], None
     sb = tr._static_batch(_ring(50), 'train', None, M(), np.array([7, 3, 5]))
     assert made[-1] == ((50, 50), 'auto', 14, 48, None) and sb.rows.tolist() == [3, 5, 7] and sb.L == 2
+    assert operand[-1] is False
     tr._static_batch(_ring(50), 'full', "x.npz", M(), np.array([1]))
     assert made[-1] == ((50, 50), 'auto', 15, 48, "x.npz")
     assert isinstance(sb, full_batch.StaticBatch)
+    FLAGS.update(full_batch_dtype='bf16', full_batch=True)
+    tr._static_batch(_ring(50), 'train', None, M(), np.array([1]))
+    assert made[-1] == ((50, 50), 'auto', 14, 48, None) and operand[-1] is True
+    assert [m for _, m in tr.static_matrices] and all(isinstance(m, Rec) for _, m in tr.static_matrices)
 
 
 def test_unaligned_width_falls_back_to_the_row_kernel():
@@ -224,6 +234,143 @@ def test_unaligned_width_falls_back_to_the_row_kernel():
     assert m.kernel_for(torch.zeros(8, 20)[:, 2:18]) == 'rows'
     m.kernel = 'rows'
     assert m.kernel_for(torch.zeros(8, 16)) == 'rows'
+
+
+# ---- one path for every static-graph product ---------------------------------------------------------------------------
+class _FakeClock(object):
+    def __init__(self):
+        self.pace = {}
+
+
+class _FakePlan(object):
+    """What StaticMatrix asks of a ColumnSweepCSR, recorded."""
+
+    def __init__(self, log):
+        self.log, self._clock = log, _FakeClock()
+
+    def clock(self, bf16=False):
+        return self._clock
+
+    def autotune(self, x, d=None):
+        self.log.append(('autotune', tuple(x.shape), d))
+        self._clock.pace[d] = 250
+
+    def store_if_cached(self):
+        self.log.append(('store_if_cached',))
+
+    def variant(self, d, bf16=False):
+        return "fake sweep d=%d" % d
+
+
+@pytest.fixture
+def recorded(monkeypatch):
+    """Recorders in place of everything StaticMatrix builds or launches: ``log`` lists the calls in order."""
+    from stochastic_gcn_amd import ops
+    log = []
+
+    def product(name):
+        def run(A, x, out=None, beta=0.0, d=None, **kw):
+            log.append((name, tuple(x.shape), tuple(x.stride()), d, beta))
+            return torch.zeros((A.shape[0], x.shape[1]))
+        return run
+
+    class Csr(object):
+        def __init__(self, a):
+            self.shape = a.shape
+    monkeypatch.setattr(ops.DeviceCSR, "from_scipy", staticmethod(lambda a, device: log.append(('from_scipy',)) or Csr(a)))
+
+    def cached(a, device, path=None, G=1):
+        log.append(('cached', path, G))
+        plan = _FakePlan(log)
+        plan.shape = a.shape
+        return plan, False
+    monkeypatch.setattr(ops.ColumnSweepCSR, "cached", staticmethod(cached))
+    monkeypatch.setattr(ops.LdsSweepCSR, "for_graph", staticmethod(lambda a, device: log.append(('for_graph',))))
+    monkeypatch.setattr(ops, "spmm", product('spmm'))
+    monkeypatch.setattr(ops, "spmm_cs", product('spmm_cs'))
+    monkeypatch.setattr(ops, "spmm_lds", product('spmm_lds'))
+    return log
+
+
+def _pp(log, monkeypatch, verdict, **kw):
+    from stochastic_gcn_amd import full_batch, train
+    asked = []
+    monkeypatch.setattr(full_batch, "static_kernel_for", lambda nnz, d, products: asked.append((nnz, d, products)) or verdict)
+    a, X = _ring(50), torch.arange(300, dtype=torch.float32).reshape(50, 6)
+    tf, ff = train.pp_products(a, a, X, torch.device("cpu"), **kw)
+    assert tuple(tf.shape) == tuple(ff.shape) == (50, 6) and tf.is_contiguous()
+    return asked
+
+
+def test_pp_products_run_once_ask_the_cost_model_and_take_the_rows_kernel(recorded, monkeypatch):
+    asked = _pp(recorded, monkeypatch, 'rows', products=1)
+    assert asked == [(100, 6, 1)] * 2
+    assert [c[0] for c in recorded] == ['from_scipy', 'spmm', 'from_scipy', 'spmm']
+
+
+def test_pp_products_sweep_an_unaligned_width_on_a_padded_pitch(recorded, monkeypatch):
+    """Width 6 is no multiple of 4: pp_products pads the pitch once and the sweep -- not the row kernel that
+    StaticMatrix.product would fall back to -- takes the view."""
+    from stochastic_gcn_amd import ops
+    stats = []
+    _pp(recorded, monkeypatch, 'cs', products=200, cache=("t.npz", "f.npz"), stats=stats)
+    G = ops.ColumnSweepCSR.choose_g(6, 100 / 50, 50)
+    assert [c for c in recorded if c[0] == 'cached'] == [('cached', "t.npz", G), ('cached', "f.npz", G)]
+    products = [c for c in recorded if c[0].startswith('spmm')]
+    assert [c[0] for c in products] == ['spmm_cs', 'spmm_cs']
+    for _, shape, stride, d, beta in products:
+        assert shape == (50, 6) and stride[0] % 4 == 0 and stride[1] == 1 and d == 6 and beta == 0.0
+    for c in recorded:
+        if c[0] == 'autotune':
+            assert c[1] == (50, 6) and c[2] == 6
+    assert not any(c[0] in ('for_graph', 'from_scipy') for c in recorded)          # a cache path: the LDS planner is not asked
+    assert len(stats) == 2
+    for rec in stats:
+        assert set(rec) == {'plan_from_cache', 'pace', 'kernel', 'products'}
+        assert rec == dict(plan_from_cache=False, pace=250, kernel="fake sweep d=6", products=200)
+
+
+def test_multiply_tunes_a_width_once(recorded):
+    from stochastic_gcn_amd.full_batch import StaticMatrix
+    m = StaticMatrix(_ring(50), torch.device("cpu"), 'cs', 5, 8, "p.npz")
+    x = torch.zeros(50, 8)
+    m.multiply(x)
+    first = [c[0] for c in recorded]
+    assert first == ['cached', 'autotune', 'store_if_cached', 'spmm_cs']
+    m.multiply(x)
+    assert [c[0] for c in recorded[len(first):]] == ['spmm_cs']                    # no autotune, no store
+    m.multiply(torch.zeros(50, 12))                                                 # another width: its own tune
+    assert [c[0] for c in recorded[len(first) + 1:]] == ['autotune', 'store_if_cached', 'spmm_cs']
+    with pytest.raises(ValueError, match="not on 'lds'"):
+        m.multiply(x, kernel='lds')
+    assert m.describe(8) == dict(plan_from_cache=False, pace=250, kernel="fake sweep d=8", products=5)
+
+
+def test_forward_only_static_batch():
+    from stochastic_gcn_amd.full_batch import StaticBatch
+    N, L = 11, 2
+    A, dev = _FakeMatrix(N, 40), torch.device("cpu")
+    full = StaticBatch(A, np.zeros((N, 3), np.float32), np.array([1, 4]), L, dev)
+    fwd = StaticBatch(A, None, None, L, dev)
+    assert fwd.labels is None and fwd.rows is None and fwd.host_rows is None
+    assert (fwd.N, fwd.L, fwd.dropout, fwd.sizes) == (full.N, full.L, full.dropout, full.sizes)
+    assert len(fwd.fields) == L + 1 and len(fwd.scales) == L
+    assert all(torch.equal(a, b) and a.dtype == b.dtype for a, b in zip(fwd.fields + fwd.scales, full.fields + full.scales))
+    assert fwd.adj == full.adj == [A] * L and np.array_equal(fwd.host_field, full.host_field)
+    cur = fwd.cur("inputs")
+    assert cur.labels is None and cur.rows is None and cur.adj[0] is A
+    with pytest.raises(ValueError, match="forward-only"):
+        fwd.with_rows(np.array([0]))
+    with pytest.raises(ValueError, match="label table"):
+        StaticBatch(A, None, np.array([0]), L, dev)
+
+
+def test_full_batch_does_not_import_train():
+    import subprocess
+    import sys
+    code = ("import sys; import stochastic_gcn_amd.full_batch; "
+            "sys.exit(1 if 'stochastic_gcn_amd.train' in sys.modules else 0)")
+    assert subprocess.run([sys.executable, "-c", code], cwd=ROOT).returncode == 0
 
 
 # ---- the exports ------------------------------------------------------------------------------------------------------

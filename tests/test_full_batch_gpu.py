@@ -35,10 +35,8 @@ def _np(x):
 
 
 def _static_batch(case, adj, model, rows, kernel, products=3):
-    from stochastic_gcn_amd.flags import FLAGS
-    from stochastic_gcn_amd.full_batch import StaticBatch, StaticMatrix
-    widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(model.L)]
-    mat = StaticMatrix(adj, DEV, kernel, products, max(widths or [FLAGS.hidden1]))
+    from stochastic_gcn_amd.full_batch import StaticBatch, model_matrix
+    mat = model_matrix(adj, DEV, model, products, kernel=kernel)
     assert mat.kernel == kernel
     return StaticBatch(mat, case['labels'], np.sort(rows), model.L, DEV)
 
@@ -130,6 +128,34 @@ def test_unaligned_width_runs_on_the_row_kernel():
     assert sorted(set(calls)) == [('cs', 32), ('rows', 22)], calls
     # the first aggregation has no backward (nothing in front of it has parameters); the second runs forward and backward
     assert calls.count(('rows', 22)) == 1 and calls.count(('cs', 32)) == 2
+
+
+def test_multiply_takes_a_width_off_the_vector_size_on_a_padded_pitch_on_every_kernel():
+    """StaticMatrix.multiply (what train.pp_products calls) makes no alignment decision: 130 columns -- two 128-column
+    passes, no multiple of 4 -- as a view of a 132-float pitch run on the kernel that was asked for.  1,000 vertices in 8
+    planted communities (p_in 0.95, ~20 k nonzeros): no multiple of the LDS sweep's 768-row tile or the sweep's 16-row bins.
+    Against SciPy in float64 with the bound of the pp tests (tests/test_train_gpu.py): max|got - ref| <= 1e-4 max|ref|."""
+    from stochastic_gcn_amd import synthetic
+    from stochastic_gcn_amd.full_batch import StaticMatrix
+    a = synthetic.reddit_sbm(n=1000, m=10000, classes=8, splits=(600, 100, 300), p_in=0.95, seed=3)[2]
+    assert a.shape == (1000, 1000) and 15000 <= a.nnz <= 21000
+    X = np.random.RandomState(0).standard_normal((1000, 130)).astype(np.float32)
+    ref = a.astype(np.float64).dot(X.astype(np.float64))
+    x = torch.zeros((1000, 132), dtype=torch.float32, device=DEV)[:, :130]
+    x.copy_(torch.from_numpy(X))
+    assert x.stride(0) == 132
+    for kernel in ('rows', 'cs', 'lds'):
+        m = StaticMatrix(a, DEV, kernel, 3, 130)
+        assert m.kernel == kernel and m.kernel_for(x) == 'rows'          # (product would fall back; multiply does not)
+        got = m.multiply(x)
+        assert tuple(got.shape) == (1000, 130)
+        err = np.abs(got.cpu().numpy() - ref).max()
+        print("multiply on %s: max err %.3e, bound %.3e" % (kernel, err, 1e-4 * np.abs(ref).max()))
+        assert err <= 1e-4 * np.abs(ref).max(), kernel
+        if kernel == 'cs':
+            assert 130 in m._plan.pace                                    # tuned by the first product ...
+            assert torch.equal(m.multiply(x), got)                        # ... and the second one is the same product
+        assert m.describe(130)['products'] == 3
 
 
 @pytest.mark.parametrize("name", ['cora', 'pubmed', 'reddit3k_pp', 'reddit3k_nopp', 'multilabel'])
