@@ -570,6 +570,20 @@ int sgcn_gemm_mb16_f32(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, i
                        const float* dev_A, int64_t lda, const float* dev_B, int64_t ldb, float* dev_C, int64_t ldc,
                        int32_t accumulate, float* dev_ws, const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c,
                        void* stream);
+/* The same product with A ALREADY bfloat16 in memory ("a16"; --feature_dtype bf16, the resident feature table of a model
+ * whose every pass is a full-graph pass): dev_A holds bfloat16 bits, lda is in ELEMENTS; B, C, the workspace, the split
+ * rule (sgcn_gemm_mb16_ws_floats), the masks and the order of additions are those of sgcn_gemm_mb16_f32.  Forms NN (0, 0)
+ * and TN (1, 0) only -- the two products that read the feature table; NT and (1, 1): SGCN_ERR_INVALID.  Without drop_a the
+ * stored bits reach the matrix cores unconverted; with drop_a an element is widened exactly, multiplied by its factor in
+ * fp32 and rounded to nearest even.  Contract: on a table that holds no subnormal value, the bits of sgcn_gemm_mb16_f32 on
+ * the widened table, for every form, split, accumulate setting and mask.  A subnormal element is passed on as stored (the
+ * fp32 entry's conversion may flush it; the matrix cores may flush either), so on such a table the two entries may differ.
+ * Any 2-byte aligned base and any pitch >= width work; 8-byte aligned rows with lda % 4 == 0 and run lengths (K for NN, M
+ * for TN) that are a multiple of 4 load 8 bytes at once -- the layout of a bfloat16 history table (pitch 8 * ceil(d / 8)). */
+int sgcn_gemm_mb16_a16(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K,
+                       const uint16_t* dev_A, int64_t lda, const float* dev_B, int64_t ldb, float* dev_C, int64_t ldc,
+                       int32_t accumulate, float* dev_ws, const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c,
+                       void* stream);
 /* One launch per dense layer: Y = act(LN(X . W) * scale + offset)   (N <= 128 when LN / ReLU is
  * requested; offset/scale NULL -> no LayerNorm).   gcn/layers.py:120-138, :396-411
  * dev_X2 (nullable): rows >= split of the operand come from X2 (row - split): the CVD layer runs its

@@ -184,6 +184,9 @@ SIGNATURES = {
     "sgcn_gemm_mb16_ws_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "sgcn_gemm_mb16_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
                                      C.c_int64, P, C.c_int64, C.c_int32, P, P, P, P]),
+    # the same with A stored as bfloat16 (--feature_dtype bf16; forms NN and TN): lda in elements
+    "sgcn_gemm_mb16_a16": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
+                                     C.c_int64, P, C.c_int64, C.c_int32, P, P, P, P]),
     "sgcn_dense_fwd_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, C.c_int32,
                                      P, C.c_int64, P, P, C.c_float, C.c_int32, P, C.c_int64, P, P, P, P, P, P, P]),
     "sgcn_dense_bwd_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, P, P, P,

@@ -25,6 +25,16 @@
 // (accumulate) last.  No atomics.  Edges are handled by selection: an out-of-range row, column or k has its address
 // clamped and its value replaced by 0 before the rounding, so padding that holds NaN never reaches a product.
 // Subnormal fp32 inputs may be flushed to zero by the conversion, and subnormal products by the MFMA.
+//
+// sgcn_gemm_mb16_a16 (--feature_dtype bf16): A is a table that is bfloat16 IN MEMORY already (the resident feature table,
+// rounded once at set-up); B and C stay fp32.  Forms NN and TN only -- the two that ever read the feature table.  The A tile
+// loads half the bytes (8 per run of 4 where the fp32 tile loads 16) and, without a mask, its stored bits go to the LDS
+// tile unconverted; with drop_a an element is widened exactly, multiplied by its factor in fp32 and rounded to nearest
+// even -- the operations the fp32 tile performs on the widened value.  Everything else (B tile, MFMA block, split rule,
+// order of additions, epilogue) is the same code, so on a table without subnormal values the result has the bits of
+// sgcn_gemm_mb16_f32 on the widened table.  A subnormal bfloat16 element reaches the MFMA as it is stored here (no
+// conversion touches it unless drop_a is on), where the fp32 entry's conversion may already have flushed it: both may end
+// as zero in the product, but the two entries are not promised to agree on such a table.
 #include "sgcn_dev.h"
 
 namespace sgcn {
@@ -34,6 +44,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMbTM = 128, kMbTN = 128, kMbTK = 32;
 constexpr int kMbPitch = kMbTK + 8;                  // LDS row pitch in elements (80 bytes)
@@ -41,7 +52,7 @@ constexpr int kMbSliceK = 2048;                      // least K per split-K slic
 constexpr int kMbTargetBlocks = 512;                 // split until the grid has about two workgroups per CU
 
 struct Mb16Args {
-    const float* A; int64_t lda;
+    const void* A; int64_t lda;       // fp32, or bfloat16 bits (sgcn_gemm_mb16_a16); lda in elements either way
     const float* B; int64_t ldb;
     float* C; int64_t ldc;
     int32_t M, N, K;
@@ -49,8 +60,8 @@ struct Mb16Args {
     int32_t kchunk;                  // blockIdx.z covers k in [z * kchunk, (z + 1) * kchunk)
     float* ws;                       // split-K: partial tiles go to ws[z][M][N]
     DropArgs drop_a, drop_c;
-    int32_t vec_a, vec_b;            // 16-byte aligned rows, run lengths a multiple of 4: picks the float4 instantiation
-};
+    int32_t vec_a, vec_b;            // 16-byte aligned rows (8-byte: a bfloat16 A), run lengths a multiple of 4: picks the
+};                                   // instantiation that loads a run of 4 at once
 
 // One operand tile of a K-step: 128 (x: rows of A / columns of B) by 32 (k), 16 elements per thread.
 //   KMAJOR == false  the stored matrix is [X x K], k contiguous: the thread takes 4 consecutive k of rows x = (tid >> 3) + 32 q
@@ -62,10 +73,9 @@ struct Mb16Args {
 // stage() is where they are waited for: it selects 0 for what is out of range (an out-of-range row, column or k never
 // reaches a product, whatever the padding holds), applies the dropout factor in fp32, rounds to bf16 and writes the
 // [x][k] LDS tile.  Both are straight-line code: the load class is a template parameter, the mask one uniform branch.
+// The stored element type T is float, or uint16_t for a table of bfloat16 bits (below).
 template <bool KMAJOR, bool VEC>
-struct MbTile {
-    f32x4 r[4];
-
+struct MbMap {
     // is element e of load q inside the operand?  (VEC: e does not matter)
     __device__ __forceinline__ static bool inside(int q, int e, int x0, int X, int k0, int kend, int tid) {
         if (!KMAJOR) {
@@ -76,6 +86,12 @@ struct MbTile {
             return k < kend && (VEC ? x + 3 : x + e) < X;
         }
     }
+};
+
+template <bool KMAJOR, bool VEC, typename T = float>
+struct MbTile : MbMap<KMAJOR, VEC> {
+    using MbMap<KMAJOR, VEC>::inside;
+    f32x4 r[4];
 
     __device__ __forceinline__ void fetch(const float* P, int64_t ld, int x0, int X, int k0, int kend, int tid) {
 #pragma unroll
@@ -124,7 +140,67 @@ struct MbTile {
     }
 };
 
-template <bool TA, bool TB, bool VA, bool VB>
+// The same tile of a table stored as bfloat16: the same thread map, 2-byte elements.  VEC: the host verified 8-byte aligned
+// rows and run lengths that are a multiple of 4 -- a run of 4 is one 8-byte load (global_load_dwordx2); otherwise 2-byte
+// loads.  fetch() only issues loads, addresses clamped.  stage() selects 0 for what is out of range; without a mask the
+// stored bits go to the LDS tile as they are (no conversion: the element IS the bfloat16 the fp32 tile would have made of
+// its widened value); with a mask the element is widened exactly, multiplied by the factor in fp32 and rounded to nearest
+// even, as the fp32 tile does.
+template <bool KMAJOR, bool VEC>
+struct MbTile<KMAJOR, VEC, uint16_t> : MbMap<KMAJOR, VEC> {
+    using MbMap<KMAJOR, VEC>::inside;
+    u16x4 r[4];
+
+    __device__ __forceinline__ void fetch(const uint16_t* P, int64_t ld, int x0, int X, int k0, int kend, int tid) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int row = KMAJOR ? min(k0 + (tid >> 5) * 4 + q, kend - 1) : min(x0 + (tid >> 3) + 32 * q, X - 1);
+            const int first = KMAJOR ? x0 + (tid & 31) * 4 : k0 + (tid & 7) * 4;
+            const uint16_t* rowp = P + (int64_t)row * ld;
+            if (VEC) {
+                r[q] = *reinterpret_cast<const u16x4*>(rowp + (inside(q, 0, x0, X, k0, kend, tid) ? first : 0));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++) r[q][e] = rowp[inside(q, e, x0, X, k0, kend, tid) ? first + e : 0];
+            }
+        }
+    }
+
+    __device__ __forceinline__ void stage(__bf16 (*S)[kMbPitch], int x0, int X, int k0, int kend, const DropArgs& drop, int tid) {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) r[q][e] = inside(q, e, x0, X, k0, kend, tid) ? r[q][e] : (uint16_t)0;
+        if (drop.on) {                   // widen (exact), factor in fp32, round to nearest even
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                f32x4 w;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int x = KMAJOR ? x0 + (tid & 31) * 4 + e : x0 + (tid >> 3) + 32 * q;
+                    const int k = KMAJOR ? k0 + (tid >> 5) * 4 + q : k0 + (tid & 7) * 4 + e;
+                    w[e] = __uint_as_float((uint32_t)r[q][e] << 16) * (KMAJOR ? drop_factor(drop, k, x) : drop_factor(drop, x, k));
+                }
+                r[q] = __builtin_bit_cast(u16x4, __builtin_convertvector(w, bf16x4));
+            }
+        }
+        if (!KMAJOR) {
+            const int kq = (tid & 7) * 4;
+#pragma unroll
+            for (int q = 0; q < 4; q++) *reinterpret_cast<u16x4*>(&S[(tid >> 3) + 32 * q][kq]) = r[q];
+        } else {
+            const int kb = (tid >> 5) * 4, xq = (tid & 31) * 4;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const u16x4 col = {r[0][e], r[1][e], r[2][e], r[3][e]};
+                *reinterpret_cast<u16x4*>(&S[xq + e][kb]) = col;
+            }
+        }
+    }
+};
+
+// AT: the stored element type of A -- float, or uint16_t for bfloat16 bits (sgcn_gemm_mb16_a16: TB is false there)
+template <bool TA, bool TB, bool VA, bool VB, typename AT = float>
 __global__ __launch_bounds__(kBlock) void gemm_mb16_kernel(Mb16Args g) {
     // (static LDS only, declared 16-byte aligned: the fragment reads are 16-byte ds_read_b128)
     __shared__ __attribute__((aligned(16))) __bf16 As[2][kMbTM][kMbPitch];      // [i][kk]
@@ -135,13 +211,14 @@ __global__ __launch_bounds__(kBlock) void gemm_mb16_kernel(Mb16Args g) {
     const int kend = min(g.K, kbeg + g.kchunk);
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;       // the wavefront's quadrant
     f32x16 acc[2][2] = {};
-    MbTile<TA, VA> ta;              // A stored [K x M] when TA: k-major
+    MbTile<TA, VA, AT> ta;          // A stored [K x M] when TA: k-major
+    const AT* gA = static_cast<const AT*>(g.A);
     MbTile<!TB, VB> tb;             // B stored [K x N] unless TB: k-major
     const DropArgs nodrop{};
 
     const int iters = (kend - kbeg + kMbTK - 1) / kMbTK;
     if (iters > 0) {
-        ta.fetch(g.A, g.lda, m0, g.M, kbeg, kend, tid);
+        ta.fetch(gA, g.lda, m0, g.M, kbeg, kend, tid);
         tb.fetch(g.B, g.ldb, n0, g.N, kbeg, kend, tid);
         ta.stage(As[0], m0, g.M, kbeg, kend, g.drop_a, tid);
         tb.stage(Bs[0], n0, g.N, kbeg, kend, nodrop, tid);
@@ -151,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void gemm_mb16_kernel(Mb16Args g) {
         const int cur = it & 1, knext = kbeg + (it + 1) * kMbTK;
         const bool more = it + 1 < iters;
         if (more) {                  // issued here, waited for in stage() behind the MFMAs
-            ta.fetch(g.A, g.lda, m0, g.M, knext, kend, tid);
+            ta.fetch(gA, g.lda, m0, g.M, knext, kend, tid);
             tb.fetch(g.B, g.ldb, n0, g.N, knext, kend, tid);
         }
         // lane l holds A[i = l & 31][k = 8 (l >> 5) + 0..7] and B[k = 8 (l >> 5) + 0..7][j = l & 31] of a 16-wide k-step
@@ -232,6 +309,61 @@ void mb16_launch(const Mb16Args& g, dim3 grid, hipStream_t st) {
     else hipLaunchKernelGGL((gemm_mb16_kernel<TA, TB, false, false>), grid, dim3(kBlock), 0, st, g);
 }
 
+template <bool TA>
+void mb16_launch_a16(const Mb16Args& g, dim3 grid, hipStream_t st) {
+    if (g.vec_a && g.vec_b) hipLaunchKernelGGL((gemm_mb16_kernel<TA, false, true, true, uint16_t>), grid, dim3(kBlock), 0, st, g);
+    else if (g.vec_a) hipLaunchKernelGGL((gemm_mb16_kernel<TA, false, true, false, uint16_t>), grid, dim3(kBlock), 0, st, g);
+    else if (g.vec_b) hipLaunchKernelGGL((gemm_mb16_kernel<TA, false, false, true, uint16_t>), grid, dim3(kBlock), 0, st, g);
+    else hipLaunchKernelGGL((gemm_mb16_kernel<TA, false, false, false, uint16_t>), grid, dim3(kBlock), 0, st, g);
+}
+
+// The one host path of both entries; a16: A holds bfloat16 bits
+int mb16_run(bool a16, int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K, const void* A, int64_t lda,
+             const float* B, int64_t ldb, float* C, int64_t ldc, int32_t accumulate, float* ws,
+             const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c, void* stream) {
+    SGCN_REQUIRE(!(trans_a && trans_b), "gemm_mb16: the (trans_a, trans_b) = (1, 1) form is not provided");
+    SGCN_REQUIRE(!(a16 && trans_b), "gemm_mb16_a16: the NT form (trans_b) is not provided for a bfloat16 A: the feature "
+                                    "table is only ever read by the forward and the weight-gradient products");
+    SGCN_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_mb16: negative size");
+    if (M == 0 || N == 0) return SGCN_OK;
+    // (K = 0: C = 0 or C unchanged, and the operands are never read -- an empty tensor has no address)
+    SGCN_REQUIRE(C && (K == 0 || (A && B)), "gemm_mb16: null operand");
+    SGCN_REQUIRE(!a16 || K == 0 || (uintptr_t)A % 2 == 0, "gemm_mb16_a16: A must be 2-byte aligned");
+    Mb16Args g{};
+    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.accumulate = accumulate;
+    g.drop_a = drop_args(drop_a);
+    g.drop_c = drop_args(drop_c);
+    SGCN_REQUIRE(!g.drop_a.on || g.drop_a.width == (trans_a ? M : K), "gemm_mb16: drop_a width must be the stored A's row length");
+    SGCN_REQUIRE(!g.drop_c.on || g.drop_c.width == N, "gemm_mb16: drop_c width must be N");
+    if (g.drop_c.on) ws = nullptr;           // the output mask is applied in the GEMM's own epilogue
+    // (a run of 4 elements is one load: 16 bytes of fp32, 8 bytes of bfloat16)
+    auto al = [](const void* p, int64_t ld, int bytes) { return p && ((uintptr_t)p % bytes == 0) && (ld % 4 == 0); };
+    // (a run of 4 must be all in range or all out: the run it lies in is a multiple of 4 long -- MbMap::inside)
+    g.vec_a = al(A, lda, a16 ? 8 : 16) && (trans_a ? M : K) % 4 == 0;
+    g.vec_b = al(B, ldb, 16) && (trans_b ? K : N) % 4 == 0;
+    int S = ws ? mb16_split_factor(M, N, K) : 1;
+    g.kchunk = ((K + S - 1) / S + kMbTK - 1) / kMbTK * kMbTK;
+    S = K > 0 ? (K + g.kchunk - 1) / g.kchunk : 1;
+    if (K == 0) g.kchunk = kMbTK;
+    g.ws = S > 1 ? ws : nullptr;
+    const dim3 grid((unsigned)((M + kMbTM - 1) / kMbTM), (unsigned)((N + kMbTN - 1) / kMbTN), (unsigned)S);
+    hipStream_t st = (hipStream_t)stream;
+    if (a16) {
+        if (trans_a) mb16_launch_a16<true>(g, grid, st);
+        else mb16_launch_a16<false>(g, grid, st);
+    } else if (!trans_a && !trans_b) mb16_launch<false, false>(g, grid, st);
+    else if (trans_a) mb16_launch<true, false>(g, grid, st);
+    else mb16_launch<false, true>(g, grid, st);
+    if (S > 1) {
+        // (a split call has at most kMbTargetBlocks / 2 tiles, so M <= 32,768: within the grid's y range)
+        hipLaunchKernelGGL(mb16_reduce_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)M), dim3(256), 0, st,
+                           g.ws, S, M, N, C, ldc, accumulate);
+    }
+    SGCN_HIP_TRY(hipGetLastError());
+    return SGCN_OK;
+}
+
 }  // namespace
 }  // namespace sgcn
 
@@ -248,38 +380,12 @@ extern "C" int sgcn_gemm_mb16_f32(int32_t trans_a, int32_t trans_b, int32_t M, i
                                   const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
                                   int64_t ldc, int32_t accumulate, float* ws,
                                   const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c, void* stream) {
-    SGCN_REQUIRE(!(trans_a && trans_b), "gemm_mb16: the (trans_a, trans_b) = (1, 1) form is not provided");
-    SGCN_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_mb16: negative size");
-    if (M == 0 || N == 0) return SGCN_OK;
-    // (K = 0: C = 0 or C unchanged, and the operands are never read -- an empty tensor has no address)
-    SGCN_REQUIRE(C && (K == 0 || (A && B)), "gemm_mb16: null operand");
-    Mb16Args g{};
-    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K; g.accumulate = accumulate;
-    g.drop_a = drop_args(drop_a);
-    g.drop_c = drop_args(drop_c);
-    SGCN_REQUIRE(!g.drop_a.on || g.drop_a.width == (trans_a ? M : K), "gemm_mb16: drop_a width must be the stored A's row length");
-    SGCN_REQUIRE(!g.drop_c.on || g.drop_c.width == N, "gemm_mb16: drop_c width must be N");
-    if (g.drop_c.on) ws = nullptr;           // the output mask is applied in the GEMM's own epilogue
-    auto al = [](const void* p, int64_t ld) { return p && ((uintptr_t)p % 16 == 0) && (ld % 4 == 0); };
-    // (a float4 must be all in range or all out: the run it lies in is a multiple of 4 long -- MbTile::inside)
-    g.vec_a = al(A, lda) && (trans_a ? M : K) % 4 == 0;
-    g.vec_b = al(B, ldb) && (trans_b ? K : N) % 4 == 0;
-    int S = ws ? mb16_split_factor(M, N, K) : 1;
-    g.kchunk = ((K + S - 1) / S + kMbTK - 1) / kMbTK * kMbTK;
-    S = K > 0 ? (K + g.kchunk - 1) / g.kchunk : 1;
-    if (K == 0) g.kchunk = kMbTK;
-    g.ws = S > 1 ? ws : nullptr;
-    const dim3 grid((unsigned)((M + kMbTM - 1) / kMbTM), (unsigned)((N + kMbTN - 1) / kMbTN), (unsigned)S);
-    hipStream_t st = (hipStream_t)stream;
-    if (!trans_a && !trans_b) mb16_launch<false, false>(g, grid, st);
-    else if (trans_a) mb16_launch<true, false>(g, grid, st);
-    else mb16_launch<false, true>(g, grid, st);
-    if (S > 1) {
-        // (a split call has at most kMbTargetBlocks / 2 tiles, so M <= 32,768: within the grid's y range)
-        hipLaunchKernelGGL(mb16_reduce_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)M), dim3(256), 0, st,
-                           g.ws, S, M, N, C, ldc, accumulate);
-    }
-    SGCN_HIP_TRY(hipGetLastError());
-    return SGCN_OK;
+    return mb16_run(false, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, accumulate, ws, drop_a, drop_c, stream);
+}
+
+extern "C" int sgcn_gemm_mb16_a16(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K,
+                                  const uint16_t* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                                  int64_t ldc, int32_t accumulate, float* ws,
+                                  const sgcn_dropout_t* drop_a, const sgcn_dropout_t* drop_c, void* stream) {
+    return mb16_run(true, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, accumulate, ws, drop_a, drop_c, stream);
 }

@@ -26,6 +26,7 @@ from .flags import FLAGS, _CHOICES
 KERNELS = _CHOICES['full_batch_kernel']
 DTYPES = _CHOICES['full_batch_dtype']
 DENSE_DTYPES = _CHOICES['dense_dtype']
+FEATURE_DTYPES = _CHOICES['feature_dtype']
 
 
 def check_full_batch(flags=None, world=1):
@@ -68,6 +69,29 @@ def check_full_batch(flags=None, world=1):
                           ('gradvar', 'the study draws from the evaluation sampler')):
             if getattr(f, name):
                 raise ValueError("--test_full_batch is not supported with --%s: %s" % (name, why))
+    return bool(f.full_batch), bool(f.test_full_batch)
+
+
+def check_feature_dtype(flags=None):
+    """(training model's table bfloat16?, test model's table bfloat16?) under --feature_dtype, with the combinations it has
+    no kernel or no meaning for refused.  Needs no device; a sibling of check_full_batch, called beside it.
+
+    The rule is per model: a model's dense feature table is stored as bfloat16 when the flag is bf16 and EVERY pass that
+    model ever runs is a static pass -- the training model under --full_batch, the test model under --test_full_batch.  A
+    model that runs sampled steps (--cv --cvd beside --test_full_batch) keeps its fp32 table: the fp32 GEMM and the fused
+    dense_fwd of those steps have no bfloat16-table loader."""
+    f = FLAGS if flags is None else flags
+    dtype = getattr(f, 'feature_dtype', 'fp32')
+    if dtype not in FEATURE_DTYPES:
+        raise ValueError("--feature_dtype must be one of %s, got %r" % ('/'.join(FEATURE_DTYPES), dtype))
+    if dtype != 'bf16':
+        return False, False
+    if getattr(f, 'dense_dtype', 'fp32') != 'bf16':
+        raise ValueError("--feature_dtype bf16 needs --dense_dtype bf16: only the bf16-multiply GEMM reads a bfloat16 feature "
+                         "table; the fp32 GEMM and the fused dense layer have no loader for one")
+    if not (f.full_batch or f.test_full_batch):
+        raise ValueError("--feature_dtype bf16 needs --full_batch or --test_full_batch: it is the storage type of the feature "
+                         "table of a model whose every pass covers the whole graph, and no other mode has such a model")
     return bool(f.full_batch), bool(f.test_full_batch)
 
 
@@ -134,7 +158,7 @@ class StaticMatrix(object):
 
     def __init__(self, a, device, kernel='auto', products=1, d=128, cache_path=None, _transpose_of=None, bf16=False):
         a = a.tocsr()
-        self.bf16, self._scratch = bool(bf16), {}
+        self.bf16, self._scratch, self._widened = bool(bf16), {}, {}
         if self.bf16 and kernel == 'lds':
             raise ValueError("the LDS-staged sweep has no bfloat16-operand form")
         self.a, self.device, self.shape, self.nnz = a, device, (int(a.shape[0]), int(a.shape[1])), int(a.nnz)
@@ -183,9 +207,10 @@ class StaticMatrix(object):
         return self._rows
 
     def _autotune(self, x, d):
-        if d in self._tuned:
+        key = (d, x.dtype == torch.bfloat16)
+        if key in self._tuned:
             return
-        self._tuned.add(d)
+        self._tuned.add(key)
         if self.kernel == 'lds':
             r = self._plan.residual
             if isinstance(r, ops.ColumnSweepCSR) and d not in r.pace:
@@ -194,14 +219,27 @@ class StaticMatrix(object):
             self._plan.autotune(x, d=d)                # once per plan, width and operand type; stored with a cached plan
             self._plan.store_if_cached()
 
-    def operand(self, x):
-        """What the kernel gathers from: ``x`` itself, or under ``bf16`` this matrix's scratch table of x's width holding
-        x rounded to nearest even (ops.operand_round: sgcn_scatter_rows_h16 with no index)."""
-        if not self.bf16:
+    def operand(self, x, kernel=None):
+        """What ``kernel`` (default: the matrix's own) gathers from: ``x`` itself, or under ``bf16`` this matrix's scratch
+        table of x's width holding x rounded to nearest even (ops.operand_round: sgcn_scatter_rows_h16 with no index).  An
+        ``x`` that is bfloat16 already (the feature table under --feature_dtype bf16) is handed through as it is -- no
+        rounding pass, no scratch table -- whatever ``bf16`` says; only a product on the LDS sweep, which has no bfloat16
+        form, widens it (exactly) into an fp32 scratch table, and says so once."""
+        b16 = x.dtype == torch.bfloat16
+        if not (self.bf16 or b16):
             return x
         n, d = int(x.shape[0]), int(x.shape[1])
         if n != self.shape[1]:
             raise ValueError("the operand has %d rows, the matrix %d columns" % (n, self.shape[1]))
+        if b16:
+            if (self.kernel if kernel is None else kernel) != 'lds':
+                return x
+            tab = self._widened.get(d)
+            if tab is None:
+                print("[sgcn] the LDS-staged sweep has no bfloat16-operand form: a bfloat16 operand of width %d is widened into "
+                      "an fp32 scratch table of its size on every product (--full_batch_kernel cs or rows reads it directly)" % d)
+                tab = self._widened[d] = torch.empty((n, (d + 3) // 4 * 4), dtype=torch.float32, device=x.device)[:, :d]
+            return ops.history_widen(x, out=tab)
         tab = self._scratch.get(d)
         if tab is None:
             tab = self._scratch[d] = ops.history_alloc(n, d, x.device, bf16=True)
@@ -210,11 +248,12 @@ class StaticMatrix(object):
     def kernel_for(self, x, out=None):
         """The kernel one product runs on: the matrix's own, or the row kernel where an operand's rows are not 16-byte
         aligned (a width that is not a multiple of 4: no copy is made for the sweep's sake).  Under ``bf16`` the kernel
-        reads the scratch table, which is always aligned: only the width and ``out`` decide."""
+        reads the scratch table, which is always aligned: only the width and ``out`` decide -- and so for a bfloat16 ``x``."""
         if self.kernel == 'rows':
             return 'rows'
         d = int(x.shape[1])
-        if d % 4 or (not self.bf16 and not _aligned(x)) or (out is not None and not _aligned(out)):
+        b16 = self.bf16 or x.dtype == torch.bfloat16        # (a bfloat16 x: a pitch-8 table, or on 'lds' its aligned scratch)
+        if d % 4 or (not b16 and not _aligned(x)) or (out is not None and not _aligned(out)):
             return 'rows'
         return self.kernel
 
@@ -236,7 +275,7 @@ class StaticMatrix(object):
         with beta = 1."""
         M, d = self.shape[0], int(x.shape[1])
         k = self.kernel_for(x, out)
-        x = self.operand(x)
+        x = self.operand(x, k)
         if add is None:
             return self.multiply(x, out=out, kernel=k)
         if k == 'rows':

@@ -402,7 +402,10 @@ class PlainAggregator(Layer):
         if not concat:
             return A.product(x)
         out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
-        out[:, :d] = x[:n1]
+        if x.dtype == torch.bfloat16:       # the feature table under --feature_dtype bf16: the self half widened in place
+            ops.gather_rows(x[:n1], None, out=out[:, :d])
+        else:
+            out[:, :d] = x[:n1]
         A.product(x, out=out[:, d:])
         return out
 

@@ -215,7 +215,7 @@ class DevFeed(object):
 
 class Model(object):
     def __init__(self, **kwargs):
-        allowed_kwargs = {'name', 'logging', 'multitask', 'is_training', 'device', '_store'}
+        allowed_kwargs = {'name', 'logging', 'multitask', 'is_training', 'device', '_store', 'feature_bf16'}
         for kwarg in kwargs.keys():
             assert kwarg in allowed_kwargs, 'Invalid keyword argument: ' + kwarg
         self.name = kwargs.get('name') or 'model'
@@ -231,6 +231,8 @@ class Model(object):
         self.multitask = kwargs.get('multitask', False)
         self.aggregators = []
         self.is_training = kwargs.get('is_training', True)
+        # --feature_dtype bf16 selected this model (full_batch.check_feature_dtype: every pass it runs is a static pass)
+        self.feature_bf16 = bool(kwargs.get('feature_bf16', False))
         dev = kwargs.get('device')
         if dev is None:
             if not torch.cuda.is_available():
@@ -338,6 +340,10 @@ class GCN(Model):
             f.sort_indices()
             self.features = f
             self.features_dev = ops.DeviceCSR.from_scipy(f, dev, with_plan=False)
+            if self.feature_bf16:
+                print("[sgcn] --feature_dtype bf16 leaves sparse input features in fp32: the feature CSR as it is, and the dense "
+                      "table it is converted to under --nopreprocess")
+                self.feature_bf16 = False
             return
 
         def to_dev(x):
@@ -354,6 +360,11 @@ class GCN(Model):
             self.features_dev = out
         else:
             self.features_dev = to_dev(features)
+        if self.feature_bf16:
+            # rounded ONCE, to nearest even, into a bfloat16 table of the history's layout (pitch 8 * ceil(d / 8)); the fp32
+            # table is dropped here: it exists during set-up only
+            n, d = int(self.features_dev.shape[0]), int(self.features_dev.shape[1])
+            self.features_dev = ops.operand_round(self.features_dev, out=ops.history_alloc(n, d, dev, bf16=True))
         self.features = self.features_dev
 
     def _preprocess(self):
@@ -575,6 +586,9 @@ class GCN(Model):
         cv = bool(self._history)        # (structure only: no join, see ``history``)
         if isinstance(feed_dict, StaticBatch):
             return self._upload_static(feed_dict)
+        if self.feature_bf16:
+            raise ValueError("this model's feature table is bfloat16 (--feature_dtype bf16): it runs static batches only; "
+                             "the kernels of a sampled step have no loader for such a table")
         if isinstance(feed_dict, PackedBatch):
             cur = DevFeed.from_packed(feed_dict, self.device)
         else:

@@ -1660,8 +1660,14 @@ def gemm(A, B, out=None, trans_a=False, trans_b=False, accumulate=False, drop_a=
 def gemm_bf16(A, B, out=None, trans_a=False, trans_b=False, accumulate=False, drop_a=None, drop_c=None):
     """out = op(A) @ op(B) (+ out) with the multiply in bfloat16 (sgcn_gemm_mb16_f32): operands and result are fp32
     tensors, every operand element is rounded to bfloat16 (nearest even) inside the kernel, products and sums are fp32.
-    The signature of ``gemm``; both operands transposed is not provided."""
-    ap, lda = _rows2d(A, "A")
+    The signature of ``gemm``; both operands transposed is not provided.  A bfloat16 ``A`` (a table of
+    ``history_alloc(..., bf16=True)``'s layout: the feature table under --feature_dtype bf16) goes to sgcn_gemm_mb16_a16:
+    half the operand's bytes, the bits of the product of the widened table; there ``trans_b`` is not provided either.
+    ``B`` and ``out`` are always fp32."""
+    for name, t in (("B", B), ("out", out)):
+        if t is not None and t.dtype == torch.bfloat16:
+            raise TypeError("gemm_bf16: %s must be torch.float32 (only A may be a bfloat16 table), got %s" % (name, t.dtype))
+    ap, lda, a16 = _hist2d(A, "A")
     bp, ldb = _rows2d(B, "B")
     M, K = (A.shape[1], A.shape[0]) if trans_a else (A.shape[0], A.shape[1])
     K2, N = (B.shape[1], B.shape[0]) if trans_b else (B.shape[0], B.shape[1])
@@ -1676,8 +1682,9 @@ def gemm_bf16(A, B, out=None, trans_a=False, trans_b=False, accumulate=False, dr
     ws = _gemm_ws(need, A.device) if need else None
     da = C.byref(drop_a.struct(A.shape[1])) if drop_a is not None else None
     dc = C.byref(drop_c.struct(N)) if drop_c is not None else None
-    check(lib.sgcn_gemm_mb16_f32(int(trans_a), int(trans_b), int(M), int(N), int(K), ap, lda, bp, ldb, cp, ldc,
-                                 int(accumulate), _ptr(ws), da, dc, _stream()))
+    check((lib.sgcn_gemm_mb16_a16 if a16 else lib.sgcn_gemm_mb16_f32)(
+        int(trans_a), int(trans_b), int(M), int(N), int(K), ap, lda, bp, ldb, cp, ldc, int(accumulate), _ptr(ws), da, dc,
+        _stream()))
     return out
 
 

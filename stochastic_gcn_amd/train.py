@@ -26,8 +26,8 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype
-from .full_batch import (StaticBatch, StaticMatrix, check_full_batch, full_batch_bf16, full_batch_products, model_matrix,
-                         static_kernel_for)         # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
+from .full_batch import (StaticBatch, StaticMatrix, check_feature_dtype, check_full_batch, full_batch_bf16, full_batch_products,
+                         model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
 from .parallel import DataParallel
 from .plaingcn import PlainGCN
@@ -230,6 +230,8 @@ class Trainer(object):
         torch.manual_seed(FLAGS.seed)
         # (--full_batch / --test_full_batch with an estimator, a sampler option or several ranks: refused before a device is touched)
         self.full_batch, self.test_full_batch = check_full_batch(world=int(os.environ.get("WORLD_SIZE", "1")))
+        # (--feature_dtype bf16 without the bf16 GEMMs or without a full-graph mode: too; which model's table it selects)
+        self.feature_bf16 = check_feature_dtype()
         # (--history_init exact / --history_refresh / --history_error without a history, with two of them, on several ranks: too)
         self.history_init_exact, self.history_refresh, self.history_error = \
             check_exact_history(world=int(os.environ.get("WORLD_SIZE", "1")))
@@ -277,7 +279,8 @@ class Trainer(object):
 
         def model_func(model, nbr_features, adj, preprocess, is_training, cvd, _store=None):
             return model(FLAGS.num_layers, preprocess, placeholders, features, nbr_features, adj, cvd,
-                         multitask=multitask, is_training=is_training, device=device, _store=_store)
+                         multitask=multitask, is_training=is_training, device=device, _store=_store,
+                         feature_bf16=self.feature_bf16[0 if is_training else 1])
         create_model = make_template('model', model_func)
         self.train_model = create_model(train_cls, nbr_features=train_features, adj=train_adj,
                                         preprocess=FLAGS.preprocess, is_training=True, cvd=FLAGS.cvd)
