@@ -652,6 +652,18 @@ int sgcn_l2_penalty_f32(const float* dev_theta, int64_t lo, int64_t hi, float wd
  * caller.                                                       gcn/models.py:50-51 */
 int sgcn_adam_f32(float* dev_theta, const float* dev_grad, float* dev_m, float* dev_v, int64_t n,
                   float lr_t, float beta1, float beta2, float eps, void* stream);
+/* sgcn_adam_f32 that also keeps an exponential moving average of the weights (--polyak_decay; the reference declares the
+ * flag, gcn/train.py:52, and the hooks average_model / backup_model / restore_model, gcn/models.py:104-121, whose
+ * attributes it never defines).  theta, m and v get the bits sgcn_adam_f32 gives them; then, for every element, in the
+ * operand order of gcn/models.py:107-108 and with theta the value just stored,
+ *   avg <- fl(fl(avg * decay) + fl(theta * one_minus))
+ * -- two fp32 multiplies and one fp32 add, each rounded to nearest on its own (never an FMA), so that fp32 arithmetic on
+ * the host reproduces every bit.  The caller passes one_minus = fl(1.0f - decay), computed once in fp32, and starts avg as
+ * a copy of the weights; there is no bias correction.  A model that only evaluates reads avg as its weights, so nothing
+ * is backed up or restored around an evaluation.  SGCN_ERR_INVALID, nothing written: avg NULL; [avg, avg + n)
+ * overlapping theta, grad, m or v; decay outside [0, 1). */
+int sgcn_adam_ema_f32(float* dev_theta, const float* dev_grad, float* dev_m, float* dev_v, float* dev_avg, int64_t n,
+                      float lr_t, float beta1, float beta2, float eps, float decay, float one_minus, void* stream);
 
 /* ---- running statistics of the --gradvar bias / variance study (gcn/train.py:241-276) ------------------------------ */
 /* One Welford update of a running fp64 mean / sum of squared deviations by the fp32 sample x[0..n): `count` samples are
@@ -921,6 +933,11 @@ enum {
     SGCN_OP_SCATTER_ROWS_H16 = 51,    /* sgcn_scatter_rows_h16 */
     SGCN_OP_AUX_SCATTER_ROWS_H16 = 52,/* sgcn_scatter_rows_h16 on the auxiliary stream */
     SGCN_OP_HIST_APPLY_H16 = 53,      /* sgcn_hist_apply_h16 (H, ldh, recv, world, cap, d, owner, aux) */
+    /* the optimizer with the weights' moving average (ABI v16, additive; gcn/models.py:104-121): wherever sgcn_step_run looks
+     * for ADAM it takes this op alike -- the loss statistics, the fp32 history scatters behind it and the grouped
+     * weight-gradient reductions in front of it ride in its launch, and every parameter element gets the average's update
+     * exactly once, from the reduction that produced its gradient or from the walk over the rest */
+    SGCN_OP_ADAM_EMA = 54,            /* sgcn_adam_ema_f32 */
     SGCN_OP_GRAD_STORE = 22     /* no arguments, anywhere in the program: the run is in gradient-STORE mode -- every DENSE_BWD
                                  * writes its dW / doffset / dscale instead of adding to them, so the program zeroes nothing
                                  * (it must write every parameter gradient exactly once per step); and the statistics

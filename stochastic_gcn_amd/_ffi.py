@@ -224,6 +224,7 @@ SIGNATURES = {
                                  P, C.c_int64]),
     "sgcn_copy_h2d_async": (C.c_int, [P, P, C.c_int64, P]),
     "sgcn_adam_f32": (C.c_int, [P, P, P, P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, P]),
+    "sgcn_adam_ema_f32": (C.c_int, [P, P, P, P, P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, P]),
     "sgcn_moments_add_f32": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P]),
     "sgcn_moments_summary_f64": (C.c_int, [P, P, C.c_int64, P, C.c_int64, P, P]),
     # staleness of a history (--history_error): (x, ldx, h, ldh, n, d, out4, ws, stream)

@@ -932,8 +932,23 @@ static bool reduce_gaps(const ReduceMulti& R, const float* grad, int64_t n, Tail
     if (G.n == 0) { G.start[0] = 0; G.len[0] = 0; G.n = 1; }
     return true;
 }
+// what sgcn_adam_ema_f32 refuses of its average: [a, a + n) and [b, b + n) share no float; decay in [0, 1)
+static bool adam_disjoint(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+    return x + len <= y || y + len <= x;
+}
+static int adam_avg_check(const float* theta, const float* grad, const float* m, const float* v, const float* avg, int64_t n, float decay) {
+    SGCN_REQUIRE(avg, "adam_ema: null average (sgcn_adam_f32 is the form without one)");
+    SGCN_REQUIRE(decay >= 0.f && decay < 1.f, "adam_ema: decay must lie in [0, 1), got %g", (double)decay);
+    SGCN_REQUIRE(n <= 0 || (adam_disjoint(avg, theta, n) && adam_disjoint(avg, grad, n) && adam_disjoint(avg, m, n) && adam_disjoint(avg, v, n)),
+                 "adam_ema: the average overlaps theta, grad, m or v");
+    return SGCN_OK;
+}
+// `avg` != nullptr: the launch keeps the weights' moving average as well (AdamArgs, sgcn_dev.h) -- in the reductions, the gap
+// walkers and the stand-alone fall-back alike, each parameter element exactly once
 int adam_with_stats(float* theta, const float* grad, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
-                    float eps, void* stream) {
+                    float eps, float* avg, float decay, float one_minus, void* stream) {
+    if (avg) { const int rc = adam_avg_check(theta, grad, m, v, avg, n, decay); if (rc != SGCN_OK) return rc; }
     PendingStats& p = pending_stats();
     TailScatter sc = pending_scatter();
     pending_scatter().jobs = 0;
@@ -950,7 +965,9 @@ int adam_with_stats(float* theta, const float* grad, float* m, float* v, int64_t
             const int r2 = sgcn_scatter_rows_f32(sc.H[j], sc.ldh[j], sc.idx[j], sc.n[j], sc.d[j], sc.src[j], sc.lds[j], stream);
             if (r2 != SGCN_OK) return r2;
         }
-        return n > 0 ? sgcn_adam_f32(theta, grad, m, v, n, lr_t, beta1, beta2, eps, stream) : SGCN_OK;
+        if (n <= 0) return SGCN_OK;
+        return avg ? sgcn_adam_ema_f32(theta, grad, m, v, avg, n, lr_t, beta1, beta2, eps, decay, one_minus, stream)
+                   : sgcn_adam_f32(theta, grad, m, v, n, lr_t, beta1, beta2, eps, stream);
     }
     const bool st = p.armed != 0;
     p.armed = 0;
@@ -960,7 +977,7 @@ int adam_with_stats(float* theta, const float* grad, float* m, float* v, int64_t
     const unsigned extra = sc.jobs ? (unsigned)sc.first[sc.jobs] : 0u;
     const unsigned rblocks = red ? (unsigned)pr.blocks : 0u;
     hipLaunchKernelGGL(adam_stats_kernel, dim3(rblocks + blocks + 1 + extra), dim3(kBlock), 0, (hipStream_t)stream,
-                       AdamArgs{theta, grad, m, v, n, lr_t, beta1, beta2, eps}, st ? p.rowstat : nullptr, st ? p.n : 0, p.c, p.softmax,
+                       AdamArgs{theta, grad, m, v, n, lr_t, beta1, beta2, eps, avg, decay, one_minus}, st ? p.rowstat : nullptr, st ? p.n : 0, p.c, p.softmax,
                        p.stats, (int32_t)blocks, sc, red ? pr.R : ReduceMulti{}, (int32_t)rblocks, G);
     SGCN_HIP_TRY(hipGetLastError());
     return SGCN_OK;
@@ -1110,7 +1127,21 @@ extern "C" int sgcn_adam_f32(float* theta, const float* grad, float* m, float* v
     SGCN_REQUIRE(theta && grad && m && v, "adam: null operand");
     const unsigned blocks = (unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
-                       AdamArgs{theta, grad, m, v, n, lr_t, beta1, beta2, eps});
+                       AdamArgs{theta, grad, m, v, n, lr_t, beta1, beta2, eps, nullptr, 0.f, 0.f});
+    SGCN_HIP_TRY(hipGetLastError());
+    return SGCN_OK;
+}
+
+extern "C" int sgcn_adam_ema_f32(float* theta, const float* grad, float* m, float* v, float* avg, int64_t n, float lr_t,
+                                 float beta1, float beta2, float eps, float decay, float one_minus, void* stream) {
+    SGCN_REQUIRE(n >= 0, "adam_ema: negative size");
+    const int rc = adam_avg_check(theta, grad, m, v, avg, n, decay);
+    if (rc != SGCN_OK) return rc;
+    if (n == 0) return SGCN_OK;
+    SGCN_REQUIRE(theta && grad && m && v, "adam_ema: null operand");
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 2048);
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       AdamArgs{theta, grad, m, v, n, lr_t, beta1, beta2, eps, avg, decay, one_minus});
     SGCN_HIP_TRY(hipGetLastError());
     return SGCN_OK;
 }

@@ -201,12 +201,30 @@ constexpr int kLnRedCols = 32;
 
 // One element of tf.train.AdamOptimizer's update (the ONE copy of this arithmetic: the stand-alone kernel, the optimizer
 // launch of the step program and the reductions that feed it all go through here, so that they agree bit for bit).
-struct AdamArgs { float* theta; const float* grad; float* m; float* v; int64_t n; float lr_t, b1, b2, eps; };
+// `avg` != nullptr (--polyak_decay; average_model of gcn/models.py:104-108): the exponential moving average of the weights
+// takes the value just stored, avg <- fl(fl(avg * decay) + fl(theta * one_minus)) -- two multiplies and an add, each rounded
+// on its own (no contraction into an FMA), so that fp32 host arithmetic reproduces every bit.  `avg` is the same for every
+// lane of a launch: a scalar branch, and nothing of theta / m / v changes with it.
+struct AdamArgs {
+    float* theta; const float* grad; float* m; float* v; int64_t n; float lr_t, b1, b2, eps;
+    float* avg; float decay, one_minus;
+};
 __device__ __forceinline__ void adam_one(const AdamArgs& A, int64_t i, float g) {
-    const float mi = A.b1 * A.m[i] + (1.f - A.b1) * g;
-    const float vi = A.b2 * A.v[i] + (1.f - A.b2) * g * g;
+    // Every product and sum of this body is rounded on its own: contraction is OFF here.  (HIP's __fmul_rn / __fadd_rn are
+    // functions around a plain * and +, which -ffp-contract=fast fuses all the same, so the operators are written out under
+    // the pragma.)  For the moments these are the bits the update has always had -- the compiler used to pair their
+    // products into packed multiplies -- and they must not hinge on what it pairs.
+#pragma clang fp contract(off)
+    const float p1 = A.b1 * A.m[i], q1 = (1.f - A.b1) * g;
+    const float p2 = A.b2 * A.v[i], q2 = ((1.f - A.b2) * g) * g;
+    const float mi = p1 + q1, vi = p2 + q2;
     A.m[i] = mi; A.v[i] = vi;
-    A.theta[i] -= A.lr_t * mi / (sqrtf(vi) + A.eps);
+    const float th = A.theta[i] - A.lr_t * mi / (sqrtf(vi) + A.eps);
+    A.theta[i] = th;
+    if (A.avg) {
+        const float a = A.avg[i] * A.decay, b = th * A.one_minus;
+        A.avg[i] = a + b;
+    }
 }
 
 // `adam` != nullptr: the gradient element just reduced is consumed by the optimizer on the spot (it lives in A->grad)

@@ -44,7 +44,7 @@ void grad_store_mode(int on);            // sgcn_gemm.hip: parameter gradients a
 void stats_defer(int on);                // sgcn_dense.hip: the loss kernel's statistics reduction rides in the optimizer's launch
 int stats_flush(void* stream);
 int adam_with_stats(float* theta, const float* grad, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
-                    float eps, void* stream);
+                    float eps, float* avg, float decay, float one_minus, void* stream);
 bool scatter_park(float* H, int64_t ldh, const int32_t* idx, int32_t n, int32_t d, const float* src, int64_t lds);
 int ce_impl(bool softmax, const float* logits, int64_t ldz, const float* labels, int64_t ldl, int32_t n, int32_t c,
             float* dlogits, int64_t lddz, float* pred, int64_t ldp, float* stats, float* rowstat, void* stream, bool overlap,
@@ -136,6 +136,7 @@ struct CeOp {
         dz = a.p<float>(); lddz = a.next(); pred = a.p<float>(); ldp = a.next(); stats = a.p<float>(); rowstat = a.p<float>();
     }
 };
+inline bool is_adam(int32_t op) { return op == SGCN_OP_ADAM || op == SGCN_OP_ADAM_EMA; }   // the optimizer, with or without the average
 inline bool is_ce(int32_t op) { return op == SGCN_OP_SOFTMAX_CE || op == SGCN_OP_SIGMOID_CE; }
 
 }  // namespace
@@ -320,7 +321,7 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
         store = store || ops[k].op == SGCN_OP_GRAD_STORE;
         l2 = l2 || ops[k].op == SGCN_OP_L2_PENALTY;
         if (ops[k].op == SGCN_OP_SOFTMAX_CE || ops[k].op == SGCN_OP_SIGMOID_CE) ce_at = k;
-        if (ops[k].op == SGCN_OP_ADAM) adam_at = k;
+        if (is_adam(ops[k].op)) adam_at = k;
     }
     // the loss statistics ride in the optimizer's launch when this very run has one after the loss and nothing (the
     // weight-decay term) adds to the loss slot in between
@@ -359,7 +360,7 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
         sgcn_plan_t pl;
         // weight-gradient work forked onto the auxiliary stream (DENSE_BWD) is joined before anything that
         // reads or writes gradients outside the backward chain
-        if (op.op == SGCN_OP_ADAM || op.op == SGCN_OP_L2_PENALTY || op.op == SGCN_OP_SCATTER_ROWS || op.op == SGCN_OP_SCATTER_ROWS_H16 ||
+        if (is_adam(op.op) || op.op == SGCN_OP_L2_PENALTY || op.op == SGCN_OP_SCATTER_ROWS || op.op == SGCN_OP_SCATTER_ROWS_H16 ||
             op.op == SGCN_OP_MEMSET0 || op.op == SGCN_OP_VR_AGG_POST || op.op == SGCN_OP_VR_AGG_POST_H16 ||
             (op.op == SGCN_OP_DENSE_BWD && memset_on_aux)) {
             rc = sgcn::aux_join(stream);
@@ -476,7 +477,7 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
         }
         case SGCN_OP_DW_FLUSH:
             // the optimizer right behind the weight gradients: their reductions ride in its launch (fuse bit 5)
-            rc = sgcn::dw_group_flush(stream, (fuse & 32) && k + 1 < nops && ops[k + 1].op == SGCN_OP_ADAM);
+            rc = sgcn::dw_group_flush(stream, (fuse & 32) && k + 1 < nops && is_adam(ops[k + 1].op));
             break;
         case SGCN_OP_GRAD_STORE:         // (mode of the whole run: set before the loop)
         case SGCN_OP_MODE:
@@ -694,10 +695,15 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
             head.on = false;
             break;
         }
-        case SGCN_OP_ADAM: {
+        case SGCN_OP_ADAM:
+        case SGCN_OP_ADAM_EMA: {
+            const bool ema = op.op == SGCN_OP_ADAM_EMA;
             float* th = a.p<float>(); const float* g = a.p<const float>(); float* m = a.p<float>(); float* v = a.p<float>();
+            float* avg = ema ? a.p<float>() : nullptr;
             const int64_t n = a.next();
             const float lr = a.f(), b1 = a.f(), b2 = a.f(), eps = a.f();
+            const float decay = ema ? a.f() : 0.f, one_minus = ema ? a.f() : 0.f;
+            if (ema && !avg) { rc = sgcn::fail(SGCN_ERR_INVALID, "step_run: ADAM_EMA without an average"); break; }
             // history scatters that directly follow the optimizer (the reference orders them after it by a control dependency
             // only, gcn/models.py:186-194) touch nothing it touches: they ride in its launch as further workgroups
             int32_t nxt = k + 1;
@@ -712,7 +718,7 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
                 if (!H || !r || !src || !sgcn::scatter_park(H, ldh, r, rn, rd, src, lds)) break;
             }
             skip_until = nxt;
-            rc = sgcn::adam_with_stats(th, g, m, v, n, lr, b1, b2, eps, stream);
+            rc = sgcn::adam_with_stats(th, g, m, v, n, lr, b1, b2, eps, avg, decay, one_minus, stream);
             break;
         }
         case SGCN_OP_ALLREDUCE_AVG: {

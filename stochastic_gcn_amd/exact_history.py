@@ -66,6 +66,7 @@ class ExactTwin(PlainGCN):
             raise ValueError("the exact pass fills ONE history per layer (not the mean / variance pair of --det_dropout)")
         Model.__init__(self, name=owner.name + '_exact', multitask=owner.multitask, is_training=False, device=owner.device,
                        _store=owner._store)
+        self.reads_average = owner.reads_average      # (--polyak_decay: the weights the owner reads, raw or averaged)
         self.owner = owner
         self.L = owner.L + (1 if owner.preprocess else 0)
         self.preprocess, self.placeholders = owner.preprocess, owner.placeholders

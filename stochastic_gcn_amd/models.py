@@ -28,7 +28,7 @@ import torch
 
 from . import ops
 from ._ffi import check, lib as _lib
-from .flags import FLAGS
+from .flags import FLAGS, check_polyak
 from .layers import (AugmentedDropoutDense, Dense, DetDropoutFC, Dropout, SparseInput)
 from .full_batch import StaticBatch, StaticCur, dense_bf16
 from .scheduler import PackedBatch, build_plan
@@ -57,6 +57,10 @@ class VariableStore(object):
     def __init__(self):
         self.theta = None
         self.layout = None
+        # --polyak_decay > 0: the exponential moving average of ``theta`` (same layout), moved by the training model's
+        # optimizer launch and read as ``theta`` by the models that only evaluate; None: the flag is off
+        self.average = None
+        self.decay = 0.0
 
 
 def make_template(name, func):
@@ -240,6 +244,9 @@ class Model(object):
             dev = torch.device('cuda', torch.cuda.current_device())
         self.device = torch.device(dev)
         self._store = kwargs.get('_store') or VariableStore()
+        # does this model read the store's average as its weights when there is one (--polyak_decay)?  Every model that does
+        # not train; an exact twin follows its owner (exact_history.ExactTwin)
+        self.reads_average = not self.is_training
         self.dropout = 0.0
         self.cur = None
         self._want_grad = False
@@ -287,7 +294,9 @@ class Model(object):
         self.join_history()
         path = path or "tmp/%s.ckpt.npz" % self.name
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        blob = {"var/" + n: v.detach().cpu().numpy() for n, v in self.named_vars()}
+        blob = {"var/" + n: v.detach().cpu().numpy() for n, v in self._named_views(self._store.theta)}
+        if self._store.average is not None:      # (--polyak_decay: the averaged weights beside the raw ones)
+            blob.update(("avg/" + n, v.detach().cpu().numpy()) for n, v in self._named_views(self._store.average))
         for i, h in enumerate(self.history_vars):
             # (a bfloat16 history is stored WIDENED -- exact --, so fp32 and bf16 runs read each other's checkpoints)
             blob["history/%d" % i] = (h if h.dtype == torch.float32 else ops.history_widen(h)).detach().cpu().numpy()
@@ -298,8 +307,15 @@ class Model(object):
     def load(self, sess=None, load_history=False, path=None):
         path = path or "tmp/%s.ckpt.npz" % self.name
         z = np.load(path)
-        for n, v in self.named_vars():
+        for n, v in self._named_views(self._store.theta):
             v.copy_(torch.from_numpy(z["var/" + n]).to(self.device))
+        if self._store.average is not None:      # (--polyak_decay; without the flag a file's avg/* keys are ignored)
+            views = self._named_views(self._store.average)
+            if all("avg/" + n in z.files for n, _ in views):
+                for n, v in views:
+                    v.copy_(torch.from_numpy(z["avg/" + n]).to(self.device))
+            else:
+                self.reset_average("[sgcn] %s holds no averaged weights: the average starts from the loaded weights" % path)
         if load_history:
             self.join_history()
             for i, h in enumerate(self.history_vars):
@@ -498,7 +514,10 @@ class GCN(Model):
         else:
             assert st.layout == [(n, s) for n, s, _, _, _ in layout], \
                 "template re-used with a different variable layout"
-        self.theta = st.theta
+        if st.average is None and check_polyak() > 0:
+            # (whichever model of the template is built first: the average starts as the weights training starts from)
+            st.average, st.decay = st.theta.clone(), check_polyak()
+        self.theta = st.average if (st.average is not None and self.reads_average) else st.theta
         self.grad = torch.zeros_like(self.theta)
         self._layout = layout
         by_layer = {l.name: l for l in self.layers}
@@ -523,6 +542,10 @@ class GCN(Model):
                 self._wd_range = (lo, hi)
                 break
         self.vars = [v for _, v in self.named_vars()]
+
+    def _named_views(self, flat):
+        """[(name, view of ``flat``)] in the layout of the flat parameter buffer (the raw weights or their average)"""
+        return [(name, flat[off:off + n].view(shape)) for name, shape, _, off, n in self._layout]
 
     def named_vars(self):
         out = []
@@ -677,11 +700,34 @@ class GCN(Model):
             ops.l2_penalty(self.theta, self._wd_range[0], self._wd_range[1], FLAGS.weight_decay, grad=self.grad)
         return self.grad
 
+    @property
+    def average(self):
+        """the averaged weights this model's optimizer keeps (--polyak_decay), or None"""
+        return self._store.average if self.is_training else None
+
+    @property
+    def polyak_decay(self):
+        return self._store.decay
+
+    def reset_average(self, note=None):
+        """The average takes the current weights (what the first training step starts from: after a broadcast, after loading
+        a checkpoint that has none).  A no-op without --polyak_decay."""
+        st = self._store
+        if st.average is not None:
+            st.average.copy_(st.theta)
+            if note:
+                print(note)
+
     def adam_step(self):
         """tf.train.AdamOptimizer(lr, beta1, beta2, eps=1e-8) on the flat buffers."""
         self.adam_t += 1
         b1, b2 = float(FLAGS.beta1), float(FLAGS.beta2)
-        ops.adam_step(self.theta, self.grad, self.adam_m, self.adam_v, self._adam_lr(self.adam_t), b1, b2, 1e-8)
+        lr_t = self._adam_lr(self.adam_t)
+        if self.average is None:
+            ops.adam_step(self.theta, self.grad, self.adam_m, self.adam_v, lr_t, b1, b2, 1e-8)
+        else:
+            ops.adam_ema_step(self.theta, self.grad, self.adam_m, self.adam_v, self.average, lr_t, b1, b2, 1e-8,
+                              decay=self.polyak_decay)
 
     @staticmethod
     def _adam_lr(t):
@@ -746,6 +792,7 @@ class GCN(Model):
                bool(getattr(getattr(self, '_par', None), 'exchange_overlap', False)),
                self.theta.data_ptr(), self.grad.data_ptr(),
                self.adam_m.data_ptr() if self.is_training else 0, self.adam_v.data_ptr() if self.is_training else 0,
+               self.average.data_ptr() if self.average is not None else 0,
                self.features_dev.data_ptr() if isinstance(self.features_dev, torch.Tensor) else 0,
                tuple(h.data_ptr() for hs in self._history for h in hs),
                bool(FLAGS.group_dw), bool(FLAGS.lean_sync), bool(FLAGS.agg_overlap))

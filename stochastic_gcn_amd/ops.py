@@ -510,6 +510,25 @@ def adam_step(theta, grad, m, v, lr_t, beta1, beta2, eps=1e-8):
                             _stream()))
 
 
+def polyak_factors(decay):
+    """(decay, one_minus) as sgcn_adam_ema_f32 takes them: fp32(decay) and fl(1.0f - decay), both as Python floats."""
+    d = np.float32(decay)
+    return float(d), float(np.float32(1.0) - d)
+
+
+def adam_ema_step(theta, grad, m, v, avg, lr_t, beta1, beta2, eps=1e-8, decay=0.0):
+    """adam_step that also moves the weights' average: avg <- fl(fl(avg * decay) + fl(theta_new * fl(1 - decay)))
+    (sgcn_adam_ema_f32; --polyak_decay)."""
+    n = int(theta.numel())
+    for t, name in ((theta, "theta"), (grad, "grad"), (m, "m"), (v, "v"), (avg, "avg")):
+        _dev(t, torch.float32, name)
+        if not t.is_contiguous() or int(t.numel()) != n:
+            raise ValueError("%s must be a contiguous fp32 array of %d elements" % (name, n))
+    d, om = polyak_factors(decay)
+    check(lib.sgcn_adam_ema_f32(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), avg.data_ptr(), n,
+                                float(lr_t), float(beta1), float(beta2), float(eps), d, om, _stream()))
+
+
 # ---- running statistics of the --gradvar study (sgcn_stats.hip; gcn/stats.py, gcn/train.py:241-276) ----
 def moments_add(x, count, mean, m2):
     """Fold the fp32 sample x into the running fp64 (mean, m2) that already hold ``count`` samples (Welford;

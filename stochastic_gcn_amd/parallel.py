@@ -212,6 +212,9 @@ class DataParallel(object):
         model._par = self                                         # (for the exchange's block capacity: history_cap)
         model.dropout_seed = int(getattr(model, "dropout_seed", 0)) + 7919 * self.rank   # independent masks per rank
         self.broadcast_(model.theta)
+        # --polyak_decay: the average restarts from the weights every replica now holds; from here on the replicas apply the
+        # same averaged gradient to the same bits, so their averages stay identical without any exchange
+        model.reset_average()
 
     def set_history_cap(self, cap, d_max):
         """The job-wide bound of the rows a step can update (``cap``, or None) and the widest history (``d_max`` floats).

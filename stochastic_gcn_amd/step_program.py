@@ -36,7 +36,9 @@ OP = dict(DENSE_FWD=1, DENSE_BWD=2, VR_AGG=3, SPMM=4, SOFTMAX_CE=5, ADAM=6, SCAT
           DET_RELU_BWD=41, GAUSS=42, GAUSS_BWD=43, DET_AGG_PREP=44, DET_AGG_PREP_BWD=45, RELU_EPS=46, GATE=47,
           # the same ops on a bfloat16 history (--history_dtype bf16): argument lists as their fp32 forms
           VR_AGG_H16=48, VR_AGG_PRE_H16=49, VR_AGG_POST_H16=50, SCATTER_ROWS_H16=51, AUX_SCATTER_ROWS_H16=52,
-          HIST_APPLY_H16=53)
+          HIST_APPLY_H16=53,
+          # the optimizer that also keeps the weights' moving average (--polyak_decay): sgcn_adam_ema_f32's argument list
+          ADAM_EMA=54)
 MAX_ARGS = 48
 GEMM_WS_BOUND = 256 * 32 * 128 + 64    # sgcn_gemm_ws_floats(M, N, K) = S * M * N with S <= 256 / (tiles of 32 x 128): never above this
 ARENA_LIMIT_BYTES = 2 << 30
@@ -947,8 +949,15 @@ class StepProgram(object):
             if self.native_world:
                 self._emit('ALLREDUCE_AVG', [K(m.grad.data_ptr()), K(m.grad.numel())])
             self._cur = self.ops_opt
-            self._emit('ADAM', [K(m.theta.data_ptr()), K(m.grad.data_ptr()), K(m.adam_m.data_ptr()), K(m.adam_v.data_ptr()),
-                                K(m.theta.numel()), self._lr(), K(_fbits(FLAGS.beta1)), K(_fbits(FLAGS.beta2)), K(_fbits(1e-8))])
+            lr, betas = self._lr(), [K(_fbits(FLAGS.beta1)), K(_fbits(FLAGS.beta2)), K(_fbits(1e-8))]
+            state = [K(m.theta.data_ptr()), K(m.grad.data_ptr()), K(m.adam_m.data_ptr()), K(m.adam_v.data_ptr())]
+            avg = m.average
+            if avg is None:
+                self._emit('ADAM', state + [K(m.theta.numel()), lr] + betas)
+            else:          # (--polyak_decay: the same launch keeps the average the evaluation models read)
+                decay, one_minus = ops.polyak_factors(m.polyak_decay)
+                self._emit('ADAM_EMA', state + [K(avg.data_ptr()), K(m.theta.numel()), lr] + betas +
+                           [K(_fbits(decay)), K(_fbits(one_minus))])
         self._cur = self.ops_hist
         for l, nh in ({} if (local_hist and not self._hist_last) else self.new_history).items():
             if self.native_world:

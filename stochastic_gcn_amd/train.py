@@ -25,7 +25,7 @@ import scipy.sparse as sp
 import torch
 
 from . import ops
-from .flags import FLAGS, check_exact_history, check_history_dtype
+from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
 from .full_batch import (StaticBatch, StaticMatrix, check_feature_dtype, check_full_batch, full_batch_bf16, full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
@@ -235,6 +235,8 @@ class Trainer(object):
         # (--history_init exact / --history_refresh / --history_error without a history, with two of them, on several ranks: too)
         self.history_init_exact, self.history_refresh, self.history_error = \
             check_exact_history(world=int(os.environ.get("WORLD_SIZE", "1")))
+        # (--polyak_decay outside [0, 1), or with --gradvar: too)
+        self.polyak_decay = check_polyak()
         if not torch.cuda.is_available():
             raise RuntimeError("training needs an MI355X (no CPU fallback for the SpMM/history path)")
         check_history_dtype()             # (--history_dtype bf16 with --det_dropout: refused before anything is built)
@@ -287,6 +289,10 @@ class Trainer(object):
         self.test_model = create_model(test_cls, nbr_features=test_features, adj=full_adj,
                                        preprocess=FLAGS.test_preprocess, is_training=False, cvd=FLAGS.test_cvd)
         log('Finised in {} seconds'.format(time() - t))
+        if self.polyak_decay > 0:
+            log('[sgcn] --polyak_decay {:g}: validation and test read an exponential moving average of the weights '
+                '(decay {:g} per Adam step, kept by the optimizer\'s launch); training keeps the raw weights'.format(
+                    self.polyak_decay, float(np.float32(self.polyak_decay))))
         if par.active:
             par.attach(self.train_model)
             self.train_d = par.shard_ids(train_d, num_data).astype(np.int32)
