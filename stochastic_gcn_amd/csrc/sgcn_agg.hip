@@ -40,7 +40,6 @@ struct AggArgsT {
     // accP[row * ldw ...] instead of living in registers across the two halves of the fused pass
     float* accP_out; const float* accP_in;
 };
-typedef AggArgsT<float> AggArgs;
 
 // hraw / hwiden / hpin / hload -- the load of a bfloat16 table and its widening -- live in sgcn_dev.h (shared with the
 // static-graph SpMM kernels)
@@ -140,7 +139,7 @@ __device__ __forceinline__ void agg_finish(const AggArgsT<HT>& a, int row, int v
 // plan's workspace) -- never from h / mu / the outputs, which _pre does not see -- so the fused pass and _pre sum every
 // P row in the same order even when the fused pass runs narrower vectors (more lanes per group, fewer groups): its
 // groups then take several chunks each.
-static int p_chunks(int32_t d, const float* Hbar, int64_t ldh, const float* ws) {
+static int p_chunks(int32_t d, const void* Hbar, int64_t ldh, const float* ws) {
     const int vw = pick_vw(d, {Hbar, ws}, {ldh, ((int64_t)d + 3) / 4 * 4});
     return kBlock / group_lanes((d + vw - 1) / vw) - 1;
 }
@@ -323,24 +322,37 @@ static int launch_agg(int G, const AggArgsT<HT>& a, const sgcn_plan_t* plan, hip
 
 using namespace sgcn;
 
-extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_col,
-                                     const float* a_val, const int32_t* f_rowptr,
-                                     const int32_t* f_col, const float* f_val, int32_t n1,
-                                     int32_t n0, int32_t nf, int32_t d, const float* h,
-                                     const float* mu, int64_t ldx, const float* Hbar, int64_t ldh,
-                                     const int32_t* ifield, const int32_t* ffield, const float* s,
-                                     float* out_h, float* out_mu, int64_t ldo, int32_t cvd,
-                                     int32_t concat_self, const sgcn_plan_t* f_plan, void* stream) {
-    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && nf >= 0 && d >= 0, "vr_aggregate: negative size");
-    if (n1 == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(a_rowptr && f_rowptr && h && Hbar && ifield && out_h, "vr_aggregate: null operand");
-    SGCN_REQUIRE(nf == 0 || ffield, "vr_aggregate: null ffield");
-    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "vr_aggregate: cvd needs mu, s, out_mu");
-    SGCN_REQUIRE(n1 <= n0 || !concat_self, "vr_aggregate: concat_self needs n1 <= n0");
-    const int64_t width = concat_self ? 2 * (int64_t)d : d;
-    SGCN_REQUIRE(ldx >= d && ldh >= d && ldo >= width, "vr_aggregate: leading dimension too small");
+// ---- the host side: one body per entry point, two instantiations ---------------------------------------------------------
+// HT = float: sgcn_vr_aggregate_f32 / _pre_f32 / _post_f32 on an N x ldh fp32 history.  HT = uint16_t: the _h16 forms on a
+// bfloat16 one (--history_dtype bf16; the storage contract is h16_table_ok's), read by 2 * VW-byte loads and widened in
+// registers; the kernels are one template, so every sum is taken in the order the fp32 call takes it on an fp32 table that
+// holds the widened values.  The two instantiations differ in two places only:
+//   - the bfloat16 table is checked (null, pitch, alignment) BEFORE the n1 == 0 / d == 0 return, the fp32 one after it with
+//     the other operands;
+//   - a table of that layout never limits the vector width, so its pointer is left out of pick_vw / p_chunks (`vw_table`;
+//     its pitch is not): VW, G and p_chunks are what the fp32 call picks for a 16-byte aligned fp32 table of the same pitch.
+// `who` is the entry point's name in the messages.
+template <class HT>
+static const void* vw_table(const HT* Hbar) { return std::is_same<HT, float>::value ? Hbar : nullptr; }
 
-    AggArgs a{};
+template <class HT>
+static int vr_aggregate(const char* who, const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
+                        const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1, int32_t n0, int32_t nf,
+                        int32_t d, const float* h, const float* mu, int64_t ldx, const HT* Hbar, int64_t ldh,
+                        const int32_t* ifield, const int32_t* ffield, const float* s, float* out_h, float* out_mu, int64_t ldo,
+                        int32_t cvd, int32_t concat_self, const sgcn_plan_t* f_plan, void* stream) {
+    constexpr bool kH16 = !std::is_same<HT, float>::value;
+    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && nf >= 0 && d >= 0, "%s: negative size", who);
+    if constexpr (kH16) { if (int rc = h16_table_ok(who, Hbar, ldh, d)) return rc; }
+    if (n1 == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(a_rowptr && f_rowptr && h && Hbar && ifield && out_h, "%s: null operand", who);
+    SGCN_REQUIRE(nf == 0 || ffield, "%s: null ffield", who);
+    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "%s: cvd needs mu, s, out_mu", who);
+    SGCN_REQUIRE(n1 <= n0 || !concat_self, "%s: concat_self needs n1 <= n0", who);
+    const int64_t width = concat_self ? 2 * (int64_t)d : d;
+    SGCN_REQUIRE(ldx >= d && ldh >= d && ldo >= width, "%s: leading dimension too small", who);
+
+    AggArgsT<HT> a{};
     a.a_rowptr = a_rowptr; a.a_col = a_col; a.a_val = a_val;
     a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
     a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh;
@@ -349,20 +361,20 @@ extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_c
     a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
     a.nseg = n1;
     if (f_plan) {
-        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "vr_aggregate: malformed plan");
+        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "%s: malformed plan", who);
         a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg;
         a.ws = f_plan->dev_ws; a.ldw = ((int64_t)d + 3) / 4 * 4;
         if (f_plan->nfix > 0) {
-            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "vr_aggregate: plan needs dev_fix/dev_ws");
-            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "vr_aggregate: workspace too small");
+            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "%s: plan needs dev_fix/dev_ws", who);
+            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "%s: workspace too small", who);
         }
     }
     // the output offset `off` = d must keep vector alignment too
-    int vw = pick_vw(d, {h, mu, Hbar, out_h, out_mu, f_plan ? f_plan->dev_ws : nullptr}, {ldx, ldh, ldo});
+    int vw = pick_vw(d, {h, mu, vw_table(Hbar), out_h, out_mu, f_plan ? f_plan->dev_ws : nullptr}, {ldx, ldh, ldo});
     if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
-    a.pchunks = p_chunks(d, Hbar, ldh, f_plan ? f_plan->dev_ws : nullptr);
+    a.pchunks = p_chunks(d, vw_table(Hbar), ldh, f_plan ? f_plan->dev_ws : nullptr);
     a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     hipStream_t st = (hipStream_t)stream;
     if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
@@ -377,34 +389,36 @@ extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_c
 // that produce h / mu (the step program issues it on the auxiliary stream); _post is the rest of the
 // fused pass.  Per element the two phases perform exactly the fused kernel's operations in the fused
 // kernel's order -- accP only takes a round trip through memory, and both cut a P row into the same chunks (p_chunks),
-// whatever vector width h / mu / the outputs allow the fused pass -- so pre + post == sgcn_vr_aggregate_f32 bit for bit
-// (tests/test_kernels_gpu.py, tests/test_sparse_exact_gpu.py).
-extern "C" int sgcn_vr_aggregate_pre_f32(const int32_t* f_rowptr, const int32_t* f_col, const float* f_val,
-                                         int32_t n1, int32_t nf, int32_t d, const float* Hbar, int64_t ldh,
-                                         const int32_t* ffield, float* accP, const sgcn_plan_t* f_plan,
-                                         void* stream) {
-    SGCN_REQUIRE(n1 >= 0 && nf >= 0 && d >= 0, "vr_aggregate_pre: negative size");
+// whatever vector width h / mu / the outputs allow the fused pass -- so pre + post == the fused call bit for bit
+// (tests/test_kernels_gpu.py, tests/test_sparse_exact_gpu.py, tests/test_history_bf16_gpu.py).
+template <class HT>
+static int vr_aggregate_pre(const char* who, const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
+                            int32_t nf, int32_t d, const HT* Hbar, int64_t ldh, const int32_t* ffield, float* accP,
+                            const sgcn_plan_t* f_plan, void* stream) {
+    constexpr bool kH16 = !std::is_same<HT, float>::value;
+    SGCN_REQUIRE(n1 >= 0 && nf >= 0 && d >= 0, "%s: negative size", who);
+    if constexpr (kH16) { if (int rc = h16_table_ok(who, Hbar, ldh, d)) return rc; }
     if (n1 == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(f_rowptr && Hbar && accP && ldh >= d, "vr_aggregate_pre: bad operand");
-    SGCN_REQUIRE(nf == 0 || ffield, "vr_aggregate_pre: null ffield");
-    AggArgs a{};
+    SGCN_REQUIRE(f_rowptr && Hbar && accP && ldh >= d, "%s: bad operand", who);
+    SGCN_REQUIRE(nf == 0 || ffield, "%s: null ffield", who);
+    AggArgsT<HT> a{};
     a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
     a.H = Hbar; a.ldh = ldh; a.ffield = ffield; a.d = d;
     a.ldw = ((int64_t)d + 3) / 4 * 4;
     a.accP_out = accP;
     a.nseg = n1;
     if (f_plan) {
-        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "vr_aggregate_pre: malformed plan");
+        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "%s: malformed plan", who);
         a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg; a.ws = f_plan->dev_ws;
         if (f_plan->nfix > 0) {
-            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "vr_aggregate_pre: plan needs dev_fix/dev_ws");
-            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "vr_aggregate_pre: workspace too small");
+            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "%s: plan needs dev_fix/dev_ws", who);
+            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "%s: workspace too small", who);
         }
     }
-    const int vw = pick_vw(d, {Hbar, accP, f_plan ? f_plan->dev_ws : nullptr}, {ldh, a.ldw});
+    const int vw = pick_vw(d, {vw_table(Hbar), accP, f_plan ? f_plan->dev_ws : nullptr}, {ldh, a.ldw});
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
-    a.pchunks = p_chunks(d, Hbar, ldh, f_plan ? f_plan->dev_ws : nullptr);
+    a.pchunks = p_chunks(d, vw_table(Hbar), ldh, f_plan ? f_plan->dev_ws : nullptr);
     a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     hipStream_t st = (hipStream_t)stream;
     if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
@@ -412,26 +426,28 @@ extern "C" int sgcn_vr_aggregate_pre_f32(const int32_t* f_rowptr, const int32_t*
     return launch_agg<1>(G, a, f_plan, st);
 }
 
-extern "C" int sgcn_vr_aggregate_post_f32(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
-                                          int32_t n1, int32_t n0, int32_t d, const float* h, const float* mu,
-                                          int64_t ldx, const float* Hbar, int64_t ldh, const int32_t* ifield,
-                                          const float* s, float* out_h, float* out_mu, int64_t ldo, int32_t cvd,
-                                          int32_t concat_self, const float* accP, void* stream) {
-    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && d >= 0, "vr_aggregate_post: negative size");
+template <class HT>
+static int vr_aggregate_post(const char* who, const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int32_t n1,
+                             int32_t n0, int32_t d, const float* h, const float* mu, int64_t ldx, const HT* Hbar, int64_t ldh,
+                             const int32_t* ifield, const float* s, float* out_h, float* out_mu, int64_t ldo, int32_t cvd,
+                             int32_t concat_self, const float* accP, void* stream) {
+    constexpr bool kH16 = !std::is_same<HT, float>::value;
+    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && d >= 0, "%s: negative size", who);
+    if constexpr (kH16) { if (int rc = h16_table_ok(who, Hbar, ldh, d)) return rc; }
     if (n1 == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(a_rowptr && h && Hbar && ifield && out_h && accP, "vr_aggregate_post: null operand");
-    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "vr_aggregate_post: cvd needs mu, s, out_mu");
-    SGCN_REQUIRE(n1 <= n0 || !concat_self, "vr_aggregate_post: concat_self needs n1 <= n0");
+    SGCN_REQUIRE(a_rowptr && h && Hbar && ifield && out_h && accP, "%s: null operand", who);
+    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "%s: cvd needs mu, s, out_mu", who);
+    SGCN_REQUIRE(n1 <= n0 || !concat_self, "%s: concat_self needs n1 <= n0", who);
     const int64_t width = concat_self ? 2 * (int64_t)d : d;
-    SGCN_REQUIRE(ldx >= d && ldh >= d && ldo >= width, "vr_aggregate_post: leading dimension too small");
-    AggArgs a{};
+    SGCN_REQUIRE(ldx >= d && ldh >= d && ldo >= width, "%s: leading dimension too small", who);
+    AggArgsT<HT> a{};
     a.a_rowptr = a_rowptr; a.a_col = a_col; a.a_val = a_val;
     a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh; a.ifield = ifield; a.s = s;
     a.out_h = out_h; a.out_mu = out_mu; a.ldo = ldo;
     a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
     a.ldw = ((int64_t)d + 3) / 4 * 4;
     a.accP_in = accP;
-    int vw = pick_vw(d, {h, mu, Hbar, out_h, out_mu, accP}, {ldx, ldh, ldo, a.ldw});
+    int vw = pick_vw(d, {h, mu, vw_table(Hbar), out_h, out_mu, accP}, {ldx, ldh, ldo, a.ldw});
     if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
@@ -441,127 +457,53 @@ extern "C" int sgcn_vr_aggregate_post_f32(const int32_t* a_rowptr, const int32_t
     return launch_agg_post<1>(G, a, n1, st);
 }
 
-// ---- the same three entry points on a bfloat16 history (--history_dtype bf16) ----------------------------------------
-// The table is N x ldh uint16 (ldh in ELEMENTS, a multiple of 8, base 16-byte aligned), read by 2 * VW-byte loads and
-// widened in registers; the kernels are the instantiations above with HT = uint16_t, so every sum is taken in the order
-// sgcn_vr_aggregate_f32 (resp. _pre_f32 + _post_f32) takes it on an fp32 table that holds the widened values.  A table of
-// that layout never limits the vector width, so VW, G and p_chunks are what the fp32 call picks for a 16-byte aligned fp32
-// table of the same element pitch (the table's pointer is left out of pick_vw, its pitch is not).
-static int h16_table_ok(const char* who, const uint16_t* Hbar, int64_t ldh, int32_t d) {
-    SGCN_REQUIRE(Hbar, "%s: null history", who);
-    SGCN_REQUIRE(ldh >= d && ldh % 8 == 0, "%s: a bfloat16 history needs ldh >= d and ldh %% 8 == 0 (ldh %lld, d %d)", who,
-                 (long long)ldh, d);
-    SGCN_REQUIRE(aligned16(Hbar), "%s: a bfloat16 history needs a 16-byte aligned base", who);
-    return SGCN_OK;
+extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
+                                     const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
+                                     int32_t n0, int32_t nf, int32_t d, const float* h, const float* mu, int64_t ldx,
+                                     const float* Hbar, int64_t ldh, const int32_t* ifield, const int32_t* ffield,
+                                     const float* s, float* out_h, float* out_mu, int64_t ldo, int32_t cvd,
+                                     int32_t concat_self, const sgcn_plan_t* f_plan, void* stream) {
+    return vr_aggregate<float>("vr_aggregate", a_rowptr, a_col, a_val, f_rowptr, f_col, f_val, n1, n0, nf, d, h, mu, ldx, Hbar,
+                               ldh, ifield, ffield, s, out_h, out_mu, ldo, cvd, concat_self, f_plan, stream);
 }
 
-/* mirrors sgcn_vr_aggregate_f32 */
+extern "C" int sgcn_vr_aggregate_pre_f32(const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
+                                         int32_t nf, int32_t d, const float* Hbar, int64_t ldh, const int32_t* ffield,
+                                         float* accP, const sgcn_plan_t* f_plan, void* stream) {
+    return vr_aggregate_pre<float>("vr_aggregate_pre", f_rowptr, f_col, f_val, n1, nf, d, Hbar, ldh, ffield, accP, f_plan, stream);
+}
+
+extern "C" int sgcn_vr_aggregate_post_f32(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int32_t n1,
+                                          int32_t n0, int32_t d, const float* h, const float* mu, int64_t ldx,
+                                          const float* Hbar, int64_t ldh, const int32_t* ifield, const float* s,
+                                          float* out_h, float* out_mu, int64_t ldo, int32_t cvd, int32_t concat_self,
+                                          const float* accP, void* stream) {
+    return vr_aggregate_post<float>("vr_aggregate_post", a_rowptr, a_col, a_val, n1, n0, d, h, mu, ldx, Hbar, ldh, ifield, s,
+                                    out_h, out_mu, ldo, cvd, concat_self, accP, stream);
+}
+
 extern "C" int sgcn_vr_aggregate_h16(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
                                      const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
                                      int32_t n0, int32_t nf, int32_t d, const float* h, const float* mu, int64_t ldx,
                                      const uint16_t* Hbar, int64_t ldh, const int32_t* ifield, const int32_t* ffield,
                                      const float* s, float* out_h, float* out_mu, int64_t ldo, int32_t cvd,
                                      int32_t concat_self, const sgcn_plan_t* f_plan, void* stream) {
-    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && nf >= 0 && d >= 0, "vr_aggregate_h16: negative size");
-    if (int rc = h16_table_ok("vr_aggregate_h16", Hbar, ldh, d)) return rc;
-    if (n1 == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(a_rowptr && f_rowptr && h && ifield && out_h, "vr_aggregate_h16: null operand");
-    SGCN_REQUIRE(nf == 0 || ffield, "vr_aggregate_h16: null ffield");
-    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "vr_aggregate_h16: cvd needs mu, s, out_mu");
-    SGCN_REQUIRE(n1 <= n0 || !concat_self, "vr_aggregate_h16: concat_self needs n1 <= n0");
-    const int64_t width = concat_self ? 2 * (int64_t)d : d;
-    SGCN_REQUIRE(ldx >= d && ldo >= width, "vr_aggregate_h16: leading dimension too small");
-
-    AggArgsT<uint16_t> a{};
-    a.a_rowptr = a_rowptr; a.a_col = a_col; a.a_val = a_val;
-    a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
-    a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh;
-    a.ifield = ifield; a.ffield = ffield; a.s = s;
-    a.out_h = out_h; a.out_mu = out_mu; a.ldo = ldo;
-    a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
-    a.nseg = n1;
-    if (f_plan) {
-        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "vr_aggregate_h16: malformed plan");
-        a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg;
-        a.ws = f_plan->dev_ws; a.ldw = ((int64_t)d + 3) / 4 * 4;
-        if (f_plan->nfix > 0) {
-            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "vr_aggregate_h16: plan needs dev_fix/dev_ws");
-            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "vr_aggregate_h16: workspace too small");
-        }
-    }
-    int vw = pick_vw(d, {h, mu, out_h, out_mu, f_plan ? f_plan->dev_ws : nullptr}, {ldx, ldh, ldo});
-    if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
-    a.nvec = (d + vw - 1) / vw;
-    const int G = group_lanes(a.nvec);
-    a.pchunks = p_chunks(d, nullptr, ldh, f_plan ? f_plan->dev_ws : nullptr);
-    a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
-    hipStream_t st = (hipStream_t)stream;
-    if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
-    if (vw == 2) return launch_agg<2>(G, a, f_plan, st);
-    return launch_agg<1>(G, a, f_plan, st);
+    return vr_aggregate<uint16_t>("vr_aggregate_h16", a_rowptr, a_col, a_val, f_rowptr, f_col, f_val, n1, n0, nf, d, h, mu, ldx,
+                                  Hbar, ldh, ifield, ffield, s, out_h, out_mu, ldo, cvd, concat_self, f_plan, stream);
 }
 
-/* mirrors sgcn_vr_aggregate_pre_f32 */
 extern "C" int sgcn_vr_aggregate_pre_h16(const int32_t* f_rowptr, const int32_t* f_col, const float* f_val, int32_t n1,
                                          int32_t nf, int32_t d, const uint16_t* Hbar, int64_t ldh, const int32_t* ffield,
                                          float* accP, const sgcn_plan_t* f_plan, void* stream) {
-    SGCN_REQUIRE(n1 >= 0 && nf >= 0 && d >= 0, "vr_aggregate_pre_h16: negative size");
-    if (int rc = h16_table_ok("vr_aggregate_pre_h16", Hbar, ldh, d)) return rc;
-    if (n1 == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(f_rowptr && accP, "vr_aggregate_pre_h16: bad operand");
-    SGCN_REQUIRE(nf == 0 || ffield, "vr_aggregate_pre_h16: null ffield");
-    AggArgsT<uint16_t> a{};
-    a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
-    a.H = Hbar; a.ldh = ldh; a.ffield = ffield; a.d = d;
-    a.ldw = ((int64_t)d + 3) / 4 * 4;
-    a.accP_out = accP;
-    a.nseg = n1;
-    if (f_plan) {
-        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "vr_aggregate_pre_h16: malformed plan");
-        a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg; a.ws = f_plan->dev_ws;
-        if (f_plan->nfix > 0) {
-            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "vr_aggregate_pre_h16: plan needs dev_fix/dev_ws");
-            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "vr_aggregate_pre_h16: workspace too small");
-        }
-    }
-    const int vw = pick_vw(d, {accP, f_plan ? f_plan->dev_ws : nullptr}, {ldh, a.ldw});
-    a.nvec = (d + vw - 1) / vw;
-    const int G = group_lanes(a.nvec);
-    a.pchunks = p_chunks(d, nullptr, ldh, f_plan ? f_plan->dev_ws : nullptr);
-    a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
-    hipStream_t st = (hipStream_t)stream;
-    if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
-    if (vw == 2) return launch_agg<2>(G, a, f_plan, st);
-    return launch_agg<1>(G, a, f_plan, st);
+    return vr_aggregate_pre<uint16_t>("vr_aggregate_pre_h16", f_rowptr, f_col, f_val, n1, nf, d, Hbar, ldh, ffield, accP, f_plan,
+                                      stream);
 }
 
-/* mirrors sgcn_vr_aggregate_post_f32 */
 extern "C" int sgcn_vr_aggregate_post_h16(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int32_t n1,
                                           int32_t n0, int32_t d, const float* h, const float* mu, int64_t ldx,
                                           const uint16_t* Hbar, int64_t ldh, const int32_t* ifield, const float* s,
                                           float* out_h, float* out_mu, int64_t ldo, int32_t cvd, int32_t concat_self,
                                           const float* accP, void* stream) {
-    SGCN_REQUIRE(n1 >= 0 && n0 >= 0 && d >= 0, "vr_aggregate_post_h16: negative size");
-    if (int rc = h16_table_ok("vr_aggregate_post_h16", Hbar, ldh, d)) return rc;
-    if (n1 == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(a_rowptr && h && ifield && out_h && accP, "vr_aggregate_post_h16: null operand");
-    SGCN_REQUIRE(!cvd || (mu && s && out_mu), "vr_aggregate_post_h16: cvd needs mu, s, out_mu");
-    SGCN_REQUIRE(n1 <= n0 || !concat_self, "vr_aggregate_post_h16: concat_self needs n1 <= n0");
-    const int64_t width = concat_self ? 2 * (int64_t)d : d;
-    SGCN_REQUIRE(ldx >= d && ldo >= width, "vr_aggregate_post_h16: leading dimension too small");
-    AggArgsT<uint16_t> a{};
-    a.a_rowptr = a_rowptr; a.a_col = a_col; a.a_val = a_val;
-    a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh; a.ifield = ifield; a.s = s;
-    a.out_h = out_h; a.out_mu = out_mu; a.ldo = ldo;
-    a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
-    a.ldw = ((int64_t)d + 3) / 4 * 4;
-    a.accP_in = accP;
-    int vw = pick_vw(d, {h, mu, out_h, out_mu, accP}, {ldx, ldh, ldo, a.ldw});
-    if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
-    a.nvec = (d + vw - 1) / vw;
-    const int G = group_lanes(a.nvec);
-    hipStream_t st = (hipStream_t)stream;
-    if (vw == 4) return launch_agg_post<4>(G, a, n1, st);
-    if (vw == 2) return launch_agg_post<2>(G, a, n1, st);
-    return launch_agg_post<1>(G, a, n1, st);
+    return vr_aggregate_post<uint16_t>("vr_aggregate_post_h16", a_rowptr, a_col, a_val, n1, n0, d, h, mu, ldx, Hbar, ldh, ifield,
+                                       s, out_h, out_mu, ldo, cvd, concat_self, accP, stream);
 }

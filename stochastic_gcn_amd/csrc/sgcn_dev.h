@@ -139,6 +139,16 @@ __device__ __forceinline__ typename Vec<VW>::type hload(const HT* p) { return hw
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
+// The storage contract of a bfloat16 history (--history_dtype bf16): N x ldh uint16, ldh in ELEMENTS and a multiple of 8, base
+// 16-byte aligned -- every row then starts on a 16-byte boundary, so the table never limits a kernel's vector width.
+inline int h16_table_ok(const char* who, const uint16_t* H, int64_t ldh, int32_t d) {
+    SGCN_REQUIRE(H, "%s: null history", who);
+    SGCN_REQUIRE(ldh >= d && ldh % 8 == 0, "%s: a bfloat16 history needs ldh >= d and ldh %% 8 == 0 (ldh %lld, d %d)", who,
+                 (long long)ldh, d);
+    SGCN_REQUIRE(aligned16(H), "%s: a bfloat16 history needs a 16-byte aligned base", who);
+    return SGCN_OK;
+}
+
 // Pick the widest vector the operands allow.  A ragged last vector may over-READ up to
 // VW-1 floats inside the row pitch (never used) and is stored element-wise.
 inline int pick_vw(int d, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds) {

@@ -62,6 +62,9 @@ __device__ __forceinline__ uint16_t bf16_round(float x) {
     if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);       // NaN: quiet, sign kept
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
+// one fp32 value into a table of either element type
+__device__ __forceinline__ void store_elem(float* p, float x) { *p = x; }
+__device__ __forceinline__ void store_elem(uint16_t* p, float x) { *p = bf16_round(x); }
 
 // SCATTER: H[r[i], :] = round(src[i, :]) with r[i] < 0 skipped; else out[i, :] = widen(H[r[i], :]).  r == nullptr: rows
 // 0 .. n-1 in place.  VW is what the fp32 side allows (the table's layout never limits it): VW fp32 elements move as one
@@ -128,12 +131,12 @@ static int launch_rows_h16(uint16_t* H, int64_t ldh, const int32_t* r, int32_t n
     return SGCN_OK;
 }
 
-static int h16_table_ok(const char* who, const uint16_t* H, int64_t ldh, int32_t d) {
-    SGCN_REQUIRE(H, "%s: null history", who);
-    SGCN_REQUIRE(ldh >= d && ldh % 8 == 0, "%s: a bfloat16 history needs ldh >= d and ldh %% 8 == 0 (ldh %lld, d %d)", who,
-                 (long long)ldh, d);
-    SGCN_REQUIRE(aligned16(H), "%s: a bfloat16 history needs a 16-byte aligned base", who);
-    return SGCN_OK;
+// H[r[i], :] = src[i, :] on a table of either element type (hist_apply<HT>)
+static int scatter_rows(float* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, const float* src, int64_t lds, hipStream_t st) {
+    return launch_rows<true>(src, lds, r, n, d, H, ldh, st);
+}
+static int scatter_rows(uint16_t* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, const float* src, int64_t lds, hipStream_t st) {
+    return launch_rows_h16<true>(H, ldh, r, n, d, const_cast<float*>(src), lds, st);
 }
 
 // One wavefront per output row: copies values and column ids, optionally writes COO row ids.
@@ -346,7 +349,7 @@ extern "C" int sgcn_scatter_rows_f32(float* H, int64_t ldh, const int32_t* r, in
     return launch_rows<true>(src, lds, r, n, d, H, ldh, (hipStream_t)stream);
 }
 
-/* mirrors sgcn_gather_rows_f32: out[i, :] = widen(H[r[i], :]); r == NULL: rows 0 .. n-1 */
+// sgcn_gather_rows_f32 on a bfloat16 table: out[i, :] = widen(H[r[i], :]); r == NULL: rows 0 .. n-1
 extern "C" int sgcn_gather_rows_h16(const uint16_t* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, float* out,
                                     int64_t ldo, void* stream) {
     SGCN_REQUIRE(n >= 0 && d >= 0, "gather_rows_h16: negative size");
@@ -356,7 +359,7 @@ extern "C" int sgcn_gather_rows_h16(const uint16_t* H, int64_t ldh, const int32_
     return launch_rows_h16<false>(const_cast<uint16_t*>(H), ldh, r, n, d, out, ldo, (hipStream_t)stream);
 }
 
-/* mirrors sgcn_scatter_rows_f32: H[r[i], :] = round(src[i, :]), r[i] < 0 skipped; r == NULL: rows 0 .. n-1 */
+// sgcn_scatter_rows_f32 on a bfloat16 table: H[r[i], :] = round(src[i, :]), r[i] < 0 skipped; r == NULL: rows 0 .. n-1
 extern "C" int sgcn_scatter_rows_h16(uint16_t* H, int64_t ldh, const int32_t* r, int32_t n, int32_t d, const float* src,
                                      int64_t lds, void* stream) {
     SGCN_REQUIRE(n >= 0 && d >= 0, "scatter_rows_h16: negative size");
@@ -408,7 +411,9 @@ __global__ __launch_bounds__(kBlock) void hist_claim_kernel(const int32_t* __res
     if (id >= 0) atomicMax(&owner[id], (int32_t)k + 1);
 }
 
-__global__ __launch_bounds__(kBlock) void hist_write_kernel(float* __restrict__ H, int64_t ldh, const int32_t* __restrict__ recv,
+// HT: the table's element -- float, or uint16_t for a bfloat16 history, into which the fp32 payload row is rounded on the way
+template <class HT>
+__global__ __launch_bounds__(kBlock) void hist_write_kernel(HT* __restrict__ H, int64_t ldh, const int32_t* __restrict__ recv,
                                                             int32_t world, int32_t cap, int32_t d, int64_t per,
                                                             int32_t* __restrict__ owner) {
     const int lane = threadIdx.x & (kWave - 1);
@@ -418,75 +423,52 @@ __global__ __launch_bounds__(kBlock) void hist_write_kernel(float* __restrict__ 
     const int32_t id = recv[r * per + i];
     if (id < 0 || owner[id] != (int32_t)k + 1) return;
     const float* src = reinterpret_cast<const float*>(recv + r * per + cap) + (int64_t)i * d;
-    float* dst = H + (int64_t)id * ldh;
-    for (int c = lane; c < d; c += kWave) dst[c] = src[c];
+    HT* dst = H + (int64_t)id * ldh;
+    for (int c = lane; c < d; c += kWave) {
+        const float x = src[c];                       // (read first, as `dst[c] = src[c]` does: the operands' order shows in the schedule)
+        store_elem(dst + c, x);
+    }
     if (lane == 0) owner[id] = 0;                     // (only the owner of a vertex touches its word in this launch)
+}
+
+// HT = float: sgcn_hist_apply_f32.  HT = uint16_t: sgcn_hist_apply_h16 -- the payload is what sgcn_hist_pack_f32 makes either
+// way (fp32 row bits); every replica rounds the same fp32 rows into its bfloat16 table, so the replicas stay bit-identical.
+// The bfloat16 table is checked (h16_table_ok) before the cap == 0 / d == 0 return, the fp32 one after it; `who` is the entry
+// point's name in the messages.
+template <class HT>
+static int hist_apply(const char* who, HT* H, int64_t ldh, const int32_t* recv, int32_t world, int32_t cap, int32_t d,
+                      int32_t* owner, void* stream) {
+    constexpr bool kH16 = !std::is_same<HT, float>::value;
+    SGCN_REQUIRE(world >= 1 && cap >= 0 && d >= 0, "%s: bad size", who);
+    if constexpr (kH16) { if (int rc = h16_table_ok(who, H, ldh, d)) return rc; }
+    if (cap == 0 || d == 0) return SGCN_OK;
+    SGCN_REQUIRE(H && recv && ldh >= d, "%s: bad operand", who);
+    const int64_t per = (int64_t)cap * (d + 1);
+    if (owner && world > 2) {
+        const int64_t n = (int64_t)world * cap;
+        hipLaunchKernelGGL(hist_claim_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                           recv, world, cap, per, owner);
+        hipLaunchKernelGGL(hist_write_kernel<HT>, dim3((unsigned)((n + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0,
+                           (hipStream_t)stream, H, ldh, recv, world, cap, d, per, owner);
+        SGCN_HIP_TRY(hipGetLastError());
+        return SGCN_OK;
+    }
+    for (int32_t r = 0; r < world; r++) {
+        const int32_t* blk = recv + r * per;
+        const int rc = scatter_rows(H, ldh, blk, cap, d, reinterpret_cast<const float*>(blk + cap), d, (hipStream_t)stream);
+        if (rc != SGCN_OK) return rc;
+    }
+    return SGCN_OK;
 }
 
 extern "C" int sgcn_hist_apply_f32(float* H, int64_t ldh, const int32_t* recv, int32_t world, int32_t cap, int32_t d,
                                    int32_t* owner, void* stream) {
-    SGCN_REQUIRE(world >= 1 && cap >= 0 && d >= 0, "hist_apply: bad size");
-    if (cap == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(H && recv && ldh >= d, "hist_apply: bad operand");
-    const int64_t per = (int64_t)cap * (d + 1);
-    if (owner && world > 2) {
-        const int64_t n = (int64_t)world * cap;
-        hipLaunchKernelGGL(hist_claim_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                           recv, world, cap, per, owner);
-        hipLaunchKernelGGL(hist_write_kernel, dim3((unsigned)((n + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0,
-                           (hipStream_t)stream, H, ldh, recv, world, cap, d, per, owner);
-        SGCN_HIP_TRY(hipGetLastError());
-        return SGCN_OK;
-    }
-    for (int32_t r = 0; r < world; r++) {
-        const int32_t* blk = recv + r * per;
-        const int rc = launch_rows<true>(reinterpret_cast<const float*>(blk + cap), d, blk, cap, d, H, ldh, (hipStream_t)stream);
-        if (rc != SGCN_OK) return rc;
-    }
-    return SGCN_OK;
+    return hist_apply<float>("hist_apply", H, ldh, recv, world, cap, d, owner, stream);
 }
 
-// the owners' copy of sgcn_hist_apply_f32 into a bfloat16 table: the fp32 payload row is rounded on the way in
-__global__ __launch_bounds__(kBlock) void hist_write_h16_kernel(uint16_t* __restrict__ H, int64_t ldh, const int32_t* __restrict__ recv,
-                                                                int32_t world, int32_t cap, int32_t d, int64_t per,
-                                                                int32_t* __restrict__ owner) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t k = (int64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    if (k >= (int64_t)world * cap) return;
-    const int32_t r = (int32_t)(k / cap), i = (int32_t)(k % cap);
-    const int32_t id = recv[r * per + i];
-    if (id < 0 || owner[id] != (int32_t)k + 1) return;
-    const float* src = reinterpret_cast<const float*>(recv + r * per + cap) + (int64_t)i * d;
-    uint16_t* dst = H + (int64_t)id * ldh;
-    for (int c = lane; c < d; c += kWave) dst[c] = bf16_round(src[c]);
-    if (lane == 0) owner[id] = 0;                     // (only the owner of a vertex touches its word in this launch)
-}
-
-/* mirrors sgcn_hist_apply_f32: the payload is what sgcn_hist_pack_f32 makes (fp32 row bits), the table bfloat16 -- every
- * replica rounds the same fp32 rows, so the replicas stay bit-identical */
 extern "C" int sgcn_hist_apply_h16(uint16_t* H, int64_t ldh, const int32_t* recv, int32_t world, int32_t cap, int32_t d,
                                    int32_t* owner, void* stream) {
-    SGCN_REQUIRE(world >= 1 && cap >= 0 && d >= 0, "hist_apply_h16: bad size");
-    if (int rc = h16_table_ok("hist_apply_h16", H, ldh, d)) return rc;
-    if (cap == 0 || d == 0) return SGCN_OK;
-    SGCN_REQUIRE(recv, "hist_apply_h16: bad operand");
-    const int64_t per = (int64_t)cap * (d + 1);
-    if (owner && world > 2) {
-        const int64_t n = (int64_t)world * cap;
-        hipLaunchKernelGGL(hist_claim_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                           recv, world, cap, per, owner);
-        hipLaunchKernelGGL(hist_write_h16_kernel, dim3((unsigned)((n + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0,
-                           (hipStream_t)stream, H, ldh, recv, world, cap, d, per, owner);
-        SGCN_HIP_TRY(hipGetLastError());
-        return SGCN_OK;
-    }
-    for (int32_t r = 0; r < world; r++) {
-        const int32_t* blk = recv + r * per;
-        float* rows = const_cast<float*>(reinterpret_cast<const float*>(blk + cap));
-        const int rc = launch_rows_h16<true>(H, ldh, blk, cap, d, rows, d, (hipStream_t)stream);
-        if (rc != SGCN_OK) return rc;
-    }
-    return SGCN_OK;
+    return hist_apply<uint16_t>("hist_apply_h16", H, ldh, recv, world, cap, d, owner, stream);
 }
 
 // o_p of a row slice on the device (what sgcn_csr_slice_indptr computes on the host, gcn/history.cpp:50-58): ONE workgroup,

@@ -137,6 +137,12 @@ struct CeOp {
     }
 };
 inline bool is_adam(int32_t op) { return op == SGCN_OP_ADAM || op == SGCN_OP_ADAM_EMA; }   // the optimizer, with or without the average
+// the fp32-history op whose argument list, stream and joins a bfloat16-history op shares (any other op: itself)
+constexpr int32_t f32_op(int32_t op) {
+    return op == SGCN_OP_VR_AGG_H16 ? SGCN_OP_VR_AGG : op == SGCN_OP_VR_AGG_PRE_H16 ? SGCN_OP_VR_AGG_PRE
+         : op == SGCN_OP_VR_AGG_POST_H16 ? SGCN_OP_VR_AGG_POST : op == SGCN_OP_SCATTER_ROWS_H16 ? SGCN_OP_SCATTER_ROWS
+         : op == SGCN_OP_AUX_SCATTER_ROWS_H16 ? SGCN_OP_AUX_SCATTER_ROWS : op == SGCN_OP_HIST_APPLY_H16 ? SGCN_OP_HIST_APPLY : op;
+}
 inline bool is_ce(int32_t op) { return op == SGCN_OP_SOFTMAX_CE || op == SGCN_OP_SIGMOID_CE; }
 
 }  // namespace
@@ -360,19 +366,23 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
         sgcn_plan_t pl;
         // weight-gradient work forked onto the auxiliary stream (DENSE_BWD) is joined before anything that
         // reads or writes gradients outside the backward chain
-        if (is_adam(op.op) || op.op == SGCN_OP_L2_PENALTY || op.op == SGCN_OP_SCATTER_ROWS || op.op == SGCN_OP_SCATTER_ROWS_H16 ||
-            op.op == SGCN_OP_MEMSET0 || op.op == SGCN_OP_VR_AGG_POST || op.op == SGCN_OP_VR_AGG_POST_H16 ||
-            (op.op == SGCN_OP_DENSE_BWD && memset_on_aux)) {
+        const int32_t base = f32_op(op.op);
+        const bool h16 = base != op.op;      // the history operand of this op is a bfloat16 table
+        if (is_adam(op.op) || base == SGCN_OP_L2_PENALTY || base == SGCN_OP_SCATTER_ROWS || base == SGCN_OP_MEMSET0 ||
+            base == SGCN_OP_VR_AGG_POST || (base == SGCN_OP_DENSE_BWD && memset_on_aux)) {
             rc = sgcn::aux_join(stream);
             if (rc != SGCN_OK) return rc;
             memset_on_aux = false;
         }
         void* side = stream;                 // where an AUX_* / *_PRE op runs
-        if (overlap && (op.op == SGCN_OP_VR_AGG_PRE || op.op == SGCN_OP_AUX_SCATTER_ROWS || op.op == SGCN_OP_AUX_MEMSET0 ||
-                        op.op == SGCN_OP_VR_AGG_PRE_H16 || op.op == SGCN_OP_AUX_SCATTER_ROWS_H16)) {
+        if (overlap && (base == SGCN_OP_VR_AGG_PRE || base == SGCN_OP_AUX_SCATTER_ROWS || base == SGCN_OP_AUX_MEMSET0)) {
             rc = sgcn::aux_fork(stream, &side);
             if (rc != SGCN_OK) return rc;
         }
+        // the last argument of an exchange op: 0 = on `stream`, 1 = forked onto the auxiliary stream, 2 = onto the exchange stream
+        auto fork_to = [&](int64_t where) {
+            return where == 0 ? (int)SGCN_OK : where == 2 ? xchg_fork(stream, &side) : sgcn::aux_fork(stream, &side);
+        };
         switch (op.op) {
         case SGCN_OP_DENSE_FWD: {
             DenseFwdOp f;
@@ -630,19 +640,23 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
             rc = sgcn_gather_f32(src, idx, n, out, stream);
             break;
         }
-        case SGCN_OP_VR_AGG: {
+        // (VR_AGG*, *SCATTER_ROWS, HIST_APPLY: the _H16 op has the same argument list, the table bfloat16 and ldh in its elements)
+        case SGCN_OP_VR_AGG:
+        case SGCN_OP_VR_AGG_H16: {
             const int32_t* arp = a.p<const int32_t>(); const int32_t* ac = a.p<const int32_t>(); const float* av = a.p<const float>();
             const int32_t* frp = a.p<const int32_t>(); const int32_t* fc = a.p<const int32_t>(); const float* fv = a.p<const float>();
             const int32_t n1 = a.i(), n0 = a.i(), nf = a.i(), d = a.i();
             const float* h = a.p<const float>(); const float* mu = a.p<const float>(); const int64_t ldx = a.next();
-            const float* H = a.p<const float>(); const int64_t ldh = a.next();
+            const void* H = a.p<const void>(); const int64_t ldh = a.next();
             const int32_t* ifi = a.p<const int32_t>(); const int32_t* ffi = a.p<const int32_t>();
             const float* s = a.p<const float>();
             float* oh = a.p<float>(); float* om = a.p<float>(); const int64_t ldo = a.next();
             const int32_t cvd = a.i(), concat = a.i();
             const sgcn_plan_t* p = a.plan(&pl);
-            rc = sgcn_vr_aggregate_f32(arp, ac, av, frp, fc, fv, n1, n0, nf, d, h, mu, ldx, H, ldh, ifi, ffi, s, oh, om, ldo,
-                                       cvd, concat, p, stream);
+            rc = h16 ? sgcn_vr_aggregate_h16(arp, ac, av, frp, fc, fv, n1, n0, nf, d, h, mu, ldx, (const uint16_t*)H, ldh, ifi, ffi,
+                                             s, oh, om, ldo, cvd, concat, p, stream)
+                     : sgcn_vr_aggregate_f32(arp, ac, av, frp, fc, fv, n1, n0, nf, d, h, mu, ldx, (const float*)H, ldh, ifi, ffi,
+                                             s, oh, om, ldo, cvd, concat, p, stream);
             break;
         }
         case SGCN_OP_SPMM: {
@@ -738,109 +752,65 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
             // (last argument != 0: on the auxiliary stream, forked here -- the exchange then runs beside the rest of the
             // step and is joined with the other auxiliary work in front of the gradient all-reduce / the optimizer)
             const int64_t where = a.next();
-            if (where != 0) { rc = where == 2 ? xchg_fork(stream, &side) : sgcn::aux_fork(stream, &side); if (rc != SGCN_OK) break; }
+            if ((rc = fork_to(where)) != SGCN_OK) break;
             rc = sgcn_hist_pack_f32(ids, n, rows, ld, d, cap, send, side);
             break;
         }
         case SGCN_OP_ALLGATHER_I32: {
             const int32_t* send = a.p<const int32_t>(); int32_t* recv = a.p<int32_t>(); const int64_t n = a.next();
             const int64_t where = a.next();
-            if (where != 0) { rc = where == 2 ? xchg_fork(stream, &side) : sgcn::aux_fork(stream, &side); if (rc != SGCN_OK) break; }
+            if ((rc = fork_to(where)) != SGCN_OK) break;
             rc = where == 2 ? sgcn_coll_allgather_x_i32(send, recv, n, side) : sgcn_coll_allgather_i32(send, recv, n, side);
             break;
         }
-        case SGCN_OP_HIST_APPLY: {
-            float* H = a.p<float>(); const int64_t ldh = a.next();
+        case SGCN_OP_HIST_APPLY:
+        case SGCN_OP_HIST_APPLY_H16: {
+            void* H = a.p<void>(); const int64_t ldh = a.next();
             const int32_t* recv = a.p<const int32_t>(); const int32_t world = a.i(), cap = a.i(), d = a.i();
             int32_t* owner = a.p<int32_t>();
             const int64_t where = a.next();
-            if (where != 0) { rc = where == 2 ? xchg_fork(stream, &side) : sgcn::aux_fork(stream, &side); if (rc != SGCN_OK) break; }
-            rc = sgcn_hist_apply_f32(H, ldh, recv, world, cap, d, owner, side);
+            if ((rc = fork_to(where)) != SGCN_OK) break;
+            rc = h16 ? sgcn_hist_apply_h16((uint16_t*)H, ldh, recv, world, cap, d, owner, side)
+                     : sgcn_hist_apply_f32((float*)H, ldh, recv, world, cap, d, owner, side);
             break;
         }
         case SGCN_OP_SCATTER_ROWS:
-        case SGCN_OP_AUX_SCATTER_ROWS: {
-            float* H = a.p<float>(); const int64_t ldh = a.next();
+        case SGCN_OP_AUX_SCATTER_ROWS:
+        case SGCN_OP_SCATTER_ROWS_H16:
+        case SGCN_OP_AUX_SCATTER_ROWS_H16: {
+            void* H = a.p<void>(); const int64_t ldh = a.next();
             const int32_t* r = a.p<const int32_t>(); const int32_t n = a.i(), d = a.i();
             const float* src = a.p<const float>(); const int64_t lds = a.next();
-            rc = sgcn_scatter_rows_f32(H, ldh, r, n, d, src, lds, side);
+            rc = h16 ? sgcn_scatter_rows_h16((uint16_t*)H, ldh, r, n, d, src, lds, side)
+                     : sgcn_scatter_rows_f32((float*)H, ldh, r, n, d, src, lds, side);
             break;
         }
-        case SGCN_OP_VR_AGG_PRE: {
-            const int32_t* frp = a.p<const int32_t>(); const int32_t* fc = a.p<const int32_t>(); const float* fv = a.p<const float>();
-            const int32_t n1 = a.i(), nf = a.i(), d = a.i();
-            const float* H = a.p<const float>(); const int64_t ldh = a.next();
-            const int32_t* ffi = a.p<const int32_t>();
-            float* accP = a.p<float>();
-            const sgcn_plan_t* p = a.plan(&pl);
-            rc = sgcn_vr_aggregate_pre_f32(frp, fc, fv, n1, nf, d, H, ldh, ffi, accP, p, side);
-            break;
-        }
-        case SGCN_OP_VR_AGG_POST: {
-            const int32_t* arp = a.p<const int32_t>(); const int32_t* ac = a.p<const int32_t>(); const float* av = a.p<const float>();
-            const int32_t n1 = a.i(), n0 = a.i(), d = a.i();
-            const float* h = a.p<const float>(); const float* mu = a.p<const float>(); const int64_t ldx = a.next();
-            const float* H = a.p<const float>(); const int64_t ldh = a.next();
-            const int32_t* ifi = a.p<const int32_t>(); const float* s = a.p<const float>();
-            float* oh = a.p<float>(); float* om = a.p<float>(); const int64_t ldo = a.next();
-            const int32_t cvd = a.i(), concat = a.i();
-            const float* accP = a.p<const float>();
-            rc = sgcn_vr_aggregate_post_f32(arp, ac, av, n1, n0, d, h, mu, ldx, H, ldh, ifi, s, oh, om, ldo, cvd, concat, accP, stream);
-            break;
-        }
-        // ---- the same ops on a bfloat16 history (argument lists as above, the table's leading dimension in elements) ----
-        case SGCN_OP_VR_AGG_H16: {
-            const int32_t* arp = a.p<const int32_t>(); const int32_t* ac = a.p<const int32_t>(); const float* av = a.p<const float>();
-            const int32_t* frp = a.p<const int32_t>(); const int32_t* fc = a.p<const int32_t>(); const float* fv = a.p<const float>();
-            const int32_t n1 = a.i(), n0 = a.i(), nf = a.i(), d = a.i();
-            const float* h = a.p<const float>(); const float* mu = a.p<const float>(); const int64_t ldx = a.next();
-            const uint16_t* H = a.p<const uint16_t>(); const int64_t ldh = a.next();
-            const int32_t* ifi = a.p<const int32_t>(); const int32_t* ffi = a.p<const int32_t>();
-            const float* s = a.p<const float>();
-            float* oh = a.p<float>(); float* om = a.p<float>(); const int64_t ldo = a.next();
-            const int32_t cvd = a.i(), concat = a.i();
-            const sgcn_plan_t* p = a.plan(&pl);
-            rc = sgcn_vr_aggregate_h16(arp, ac, av, frp, fc, fv, n1, n0, nf, d, h, mu, ldx, H, ldh, ifi, ffi, s, oh, om, ldo,
-                                       cvd, concat, p, stream);
-            break;
-        }
+        case SGCN_OP_VR_AGG_PRE:
         case SGCN_OP_VR_AGG_PRE_H16: {
             const int32_t* frp = a.p<const int32_t>(); const int32_t* fc = a.p<const int32_t>(); const float* fv = a.p<const float>();
             const int32_t n1 = a.i(), nf = a.i(), d = a.i();
-            const uint16_t* H = a.p<const uint16_t>(); const int64_t ldh = a.next();
+            const void* H = a.p<const void>(); const int64_t ldh = a.next();
             const int32_t* ffi = a.p<const int32_t>();
             float* accP = a.p<float>();
             const sgcn_plan_t* p = a.plan(&pl);
-            rc = sgcn_vr_aggregate_pre_h16(frp, fc, fv, n1, nf, d, H, ldh, ffi, accP, p, side);
+            rc = h16 ? sgcn_vr_aggregate_pre_h16(frp, fc, fv, n1, nf, d, (const uint16_t*)H, ldh, ffi, accP, p, side)
+                     : sgcn_vr_aggregate_pre_f32(frp, fc, fv, n1, nf, d, (const float*)H, ldh, ffi, accP, p, side);
             break;
         }
+        case SGCN_OP_VR_AGG_POST:
         case SGCN_OP_VR_AGG_POST_H16: {
             const int32_t* arp = a.p<const int32_t>(); const int32_t* ac = a.p<const int32_t>(); const float* av = a.p<const float>();
             const int32_t n1 = a.i(), n0 = a.i(), d = a.i();
             const float* h = a.p<const float>(); const float* mu = a.p<const float>(); const int64_t ldx = a.next();
-            const uint16_t* H = a.p<const uint16_t>(); const int64_t ldh = a.next();
+            const void* H = a.p<const void>(); const int64_t ldh = a.next();
             const int32_t* ifi = a.p<const int32_t>(); const float* s = a.p<const float>();
             float* oh = a.p<float>(); float* om = a.p<float>(); const int64_t ldo = a.next();
             const int32_t cvd = a.i(), concat = a.i();
             const float* accP = a.p<const float>();
-            rc = sgcn_vr_aggregate_post_h16(arp, ac, av, n1, n0, d, h, mu, ldx, H, ldh, ifi, s, oh, om, ldo, cvd, concat, accP, stream);
-            break;
-        }
-        case SGCN_OP_SCATTER_ROWS_H16:
-        case SGCN_OP_AUX_SCATTER_ROWS_H16: {
-            uint16_t* H = a.p<uint16_t>(); const int64_t ldh = a.next();
-            const int32_t* r = a.p<const int32_t>(); const int32_t n = a.i(), d = a.i();
-            const float* src = a.p<const float>(); const int64_t lds = a.next();
-            rc = sgcn_scatter_rows_h16(H, ldh, r, n, d, src, lds, side);
-            break;
-        }
-        case SGCN_OP_HIST_APPLY_H16: {
-            uint16_t* H = a.p<uint16_t>(); const int64_t ldh = a.next();
-            const int32_t* recv = a.p<const int32_t>(); const int32_t world = a.i(), cap = a.i(), d = a.i();
-            int32_t* owner = a.p<int32_t>();
-            const int64_t where = a.next();
-            if (where != 0) { rc = where == 2 ? xchg_fork(stream, &side) : sgcn::aux_fork(stream, &side); if (rc != SGCN_OK) break; }
-            rc = sgcn_hist_apply_h16(H, ldh, recv, world, cap, d, owner, side);
+            rc = h16 ? sgcn_vr_aggregate_post_h16(arp, ac, av, n1, n0, d, h, mu, ldx, (const uint16_t*)H, ldh, ifi, s, oh, om, ldo, cvd,
+                                                  concat, accP, stream)
+                     : sgcn_vr_aggregate_post_f32(arp, ac, av, n1, n0, d, h, mu, ldx, (const float*)H, ldh, ifi, s, oh, om, ldo, cvd,
+                                                  concat, accP, stream);
             break;
         }
         case SGCN_OP_GATHER_ROWS: {

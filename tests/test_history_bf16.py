@@ -123,3 +123,43 @@ def test_new_exports_validate_their_arguments_before_any_hip_call(name, call):
     refused(call(_X + 2, 48, 4, 41))
     assert call(_X, 48, 0, 41) == 0          # n == 0: nothing to do
     assert hasattr(ctypes.CDLL(_ffi.LIB_PATH), "sgcn_" + name)
+
+
+# the fp32 entry points those mirror, as (message prefix, export, call(table address, ldh, n, d)): the table is checked
+# AFTER the early return here, so n == 0 is fine with no table at all
+def _agg_f32(H, ldh, n, d):
+    return lib.sgcn_vr_aggregate_f32(_X, _X, _X, _X, _X, _X, n, max(n, 0), max(n, 0), d, _X, _X, max(d, 1), H, ldh, _X, _X, _X,
+                                     _X, _X, 2 * max(d, 1), 1, 1, None, None)
+
+
+def _pre_f32(H, ldh, n, d):
+    return lib.sgcn_vr_aggregate_pre_f32(_X, _X, _X, n, max(n, 0), d, H, ldh, _X, _X, None, None)
+
+
+def _post_f32(H, ldh, n, d):
+    return lib.sgcn_vr_aggregate_post_f32(_X, _X, _X, n, max(n, 0), d, _X, _X, max(d, 1), H, ldh, _X, _X, _X, _X,
+                                          2 * max(d, 1), 1, 1, _X, None)
+
+
+def _apply_f32(H, ldh, n, d):
+    return lib.sgcn_hist_apply_f32(H, ldh, _X, 2, n, d, None, None)
+
+
+ENTRY_F32 = [("vr_aggregate", "sgcn_vr_aggregate_f32", _agg_f32), ("vr_aggregate_pre", "sgcn_vr_aggregate_pre_f32", _pre_f32),
+             ("vr_aggregate_post", "sgcn_vr_aggregate_post_f32", _post_f32), ("hist_apply", "sgcn_hist_apply_f32", _apply_f32)]
+
+
+@pytest.mark.parametrize("name,export,call", ENTRY_F32, ids=[e[1] for e in ENTRY_F32])
+def test_fp32_counterparts_validate_their_arguments_before_any_hip_call(name, export, call):
+    def refused(rc):
+        msg = (lib.sgcn_last_error() or b"").decode()
+        assert rc == -1 and msg.startswith(name + ":"), (rc, msg)
+    refused(call(_X, 48, -1, 41))            # negative size
+    refused(call(_X, 48, 4, -1))
+    refused(call(_X, 40, 4, 41))             # ldh < d
+    refused(call(None, 48, 4, 41))           # null table, once there is something to do
+    assert call(_X, 48, 0, 41) == 0          # n == 0: nothing to do ...
+    assert call(None, 48, 0, 41) == 0        # ... returns before the table is looked at (the bfloat16 forms refuse this)
+    assert call(None, 0, 0, 41) == 0
+    assert call(None, 48, 4, 0) == 0         # d == 0 likewise
+    assert hasattr(ctypes.CDLL(_ffi.LIB_PATH), export)
