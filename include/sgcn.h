@@ -53,7 +53,8 @@ const char* sgcn_last_error(void);
  *       sgcn_scatter_rows_h16, sgcn_gather_rows_h16, sgcn_hist_apply_h16, step ops 48 .. 53; the losses over a row
  *       subset of N-row tables -- sgcn_softmax_ce_rows_f32 / sgcn_sigmoid_ce_rows_f32; a bfloat16 dense operand for the
  *       static-graph products -- sgcn_spmm_csr_b16 / _csr_add_b16 / sgcn_spmm_cs_b16 / sgcn_spmm_cs_variant_b16; the staleness
- *       of a history -- sgcn_hist_error_f32 / _h16 / _ws_doubles) */
+ *       of a history -- sgcn_hist_error_f32 / _h16 / _ws_doubles; the value array of a static plan re-drawn under an
+ *       edge mask -- sgcn_edge_revalue_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -537,6 +538,30 @@ typedef struct {
 /* out[i, 0:d] = x[i, 0:d] * mask / keep   (the unfused form; also its own backward) */
 int sgcn_dropout_f32(const float* dev_x, int64_t ldx, int32_t n, int32_t d, const sgcn_dropout_t* drop,
                      float* dev_out, int64_t ldo, void* stream);
+
+/* Edge dropout of a STATIC adjacency (--edge_dropout, full-graph training): once per training step the VALUE ARRAY of the
+ * matrix's plan is re-drawn from its base values and a counter-based edge mask; every product kernel of the library then
+ * runs unmodified on the re-drawn values.  An undirected edge is dropped as a whole: the mask is a function of the
+ * unordered pair, so A and A^T agree whatever order their plans store the nonzeros in.  For the entry at (i, j) of the
+ * original matrix, u = min(i, j) and v = max(i, j) as uint32 (all arithmetic mod 2^32, fmix32 as above):
+ *     pair(i, j) = fmix32(fmix32(u * 0x9E3779B1 + 0x27D4EB2F) + v * 0x85EBCA77),  stored as 0xFFFFFFFE if it is 0xFFFFFFFF
+ *     ALWAYS     = 0xFFFFFFFF       for i == j (the self loops of the gcn normalisation) and for a plan's pad entries
+ *     kept       iff pair == ALWAYS  or  fmix32(pair + key) < thr          thr from keep as for sgcn_dropout_t
+ *     out[p]     = base[p], bits unchanged         if pair[p] == ALWAYS
+ *                = base[p] * (1.0f / keep)         if kept (one fp32 multiply)
+ *                = +0.0f                           otherwise
+ * A dropped entry is +0.0f, never -0.0f: the G = 2 / 4 column-sweep plans mark their pads with the value bits 0x80000000,
+ * and a pad's bits pass through unchanged.  keep = 1 - p; nothing is renormalised: off-diagonal entries are scaled by
+ * 1 / keep and the diagonal is kept as it is, so the expectation of the re-drawn matrix is the matrix.  The pair keys are
+ * computed once on the host, one per stored entry of a plan layout (ops.edge_pair_keys).  key = the dropout key of
+ * (seed, SGCN_EDGE_SITE, step) with the step counter that keys the activation dropout of the same step; no dropout layer
+ * has that index (a layer's sites are its position in the stack and that plus 4096). */
+#define SGCN_EDGE_SITE 0x45444745
+#define SGCN_EDGE_ALWAYS 0xFFFFFFFFu
+/* out[p] as above for p < n: elementwise, no atomics, the same bits on every call.  out must overlap neither base nor the pair keys;
+ * keep outside (0, 1]: SGCN_ERR_INVALID; keep == 1 copies the bits; n == 0 is a no-op. */
+int sgcn_edge_revalue_f32(const float* dev_base, const uint32_t* dev_pair, int64_t n, uint32_t key, float keep,
+                          float* dev_out, void* stream);
 
 /* fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32, exact fp32) for the dense weight layers:
  *   C[M x N] = op(A) . op(B) (+ C when accumulate != 0);  trans_a: A is stored [K x M];

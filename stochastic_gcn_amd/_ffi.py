@@ -207,6 +207,8 @@ SIGNATURES = {
     "sgcn_relu_eps_f32": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_float, P, C.c_int64, P]),
     "sgcn_gate_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, P]),
     "sgcn_dropout_f32": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, P, C.c_int64, P]),
+    # the value array of a static plan under an edge mask (--edge_dropout): (base, pair, n, key, keep, out, stream)
+    "sgcn_edge_revalue_f32": (C.c_int, [P, P, C.c_int64, C.c_uint32, C.c_float, P, P]),
     "sgcn_softmax_ce_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64,
                                       P, C.c_int64, P, P, P]),
     "sgcn_sigmoid_ce_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64,

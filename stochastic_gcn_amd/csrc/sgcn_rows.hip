@@ -333,6 +333,66 @@ extern "C" int sgcn_gather_f32(const float* src, const int32_t* idx, int64_t n, 
     return SGCN_OK;
 }
 
+// The value array of a static plan re-drawn under an edge mask (include/sgcn.h, --edge_dropout): one entry of (base, pair)
+// in, one value out, whatever plan layout the arrays belong to.  A pad or diagonal entry (pair == kEdgeAlways) passes its
+// bits on untouched -- a G = 2 / 4 plan's pad marker 0x80000000 among them --, a kept entry takes ONE fp32 multiply, a
+// dropped one is the literal +0.0f (never base * 0: that is -0.0f, the pad marker, for a negative base).
+constexpr uint32_t kEdgeAlways = 0xffffffffu;
+
+__device__ __forceinline__ float edge_value(float base, uint32_t pair, uint32_t key, uint32_t thr, float scale) {
+    if (pair == kEdgeAlways) return base;
+    return fmix32(pair + key) < thr ? base * scale : 0.0f;
+}
+
+// Elements [0, 4 nvec) as float4 / uint4 per lane (the three arrays 16-byte aligned, checked by the caller), the rest one
+// per thread; nvec == 0: the scalar path alone.  Grid-stride on 64-bit indices.
+__global__ __launch_bounds__(kBlock) void edge_revalue_kernel(const float* __restrict__ base, const uint32_t* __restrict__ pair,
+                                                              int64_t n, int64_t nvec, uint32_t key, uint32_t thr, float scale,
+                                                              float* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t t0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    for (int64_t j = t0; j < nvec; j += stride) {
+        const float4 b = *reinterpret_cast<const float4*>(base + 4 * j);
+        const uint4 p = *reinterpret_cast<const uint4*>(pair + 4 * j);
+        float4 o;
+        o.x = edge_value(b.x, p.x, key, thr, scale);
+        o.y = edge_value(b.y, p.y, key, thr, scale);
+        o.z = edge_value(b.z, p.z, key, thr, scale);
+        o.w = edge_value(b.w, p.w, key, thr, scale);
+        *reinterpret_cast<float4*>(out + 4 * j) = o;
+    }
+    for (int64_t i = 4 * nvec + t0; i < n; i += stride) out[i] = edge_value(base[i], pair[i], key, thr, scale);
+}
+
+extern "C" int sgcn_edge_revalue_f32(const float* base, const uint32_t* pair, int64_t n, uint32_t key, float keep, float* out,
+                                     void* stream) {
+    SGCN_REQUIRE(n >= 0, "edge_revalue: negative size");
+    SGCN_REQUIRE(keep > 0.0f && keep <= 1.0f, "edge_revalue: keep must lie in (0, 1], got %g", (double)keep);      // (NaN too)
+    if (n == 0) return SGCN_OK;
+    SGCN_REQUIRE(base && pair && out, "edge_revalue: null operand");
+    SGCN_REQUIRE(((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(pair) | reinterpret_cast<uintptr_t>(out)) & 3u) == 0,
+                 "edge_revalue: operand not aligned to its element size");
+    const uintptr_t ob = reinterpret_cast<uintptr_t>(out), bb = reinterpret_cast<uintptr_t>(base),
+                    pb = reinterpret_cast<uintptr_t>(pair), len = (uintptr_t)n * 4u;
+    SGCN_REQUIRE((ob + len <= bb || bb + len <= ob) && (ob + len <= pb || pb + len <= ob),
+                 "edge_revalue: out must not alias base or the pair keys");
+    if (keep == 1.0f) {               // nothing is dropped or scaled: the bits, NaN payloads included
+        SGCN_HIP_TRY(hipMemcpyAsync(out, base, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return SGCN_OK;
+    }
+    sgcn_dropout_t d{};
+    d.key = key;
+    d.keep = keep;
+    const DropArgs a = drop_args(&d);             // thr and 1 / keep exactly as every dropout site derives them
+    const int64_t nvec = aligned16(base) && aligned16(pair) && aligned16(out) ? n / 4 : 0;
+    const int64_t work = std::max<int64_t>(nvec, n - 4 * nvec);
+    const unsigned blocks = (unsigned)std::min<int64_t>((work + kBlock - 1) / kBlock, 4096);
+    hipLaunchKernelGGL(edge_revalue_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, base, pair, n, nvec, key, a.thr,
+                       a.scale, out);
+    SGCN_HIP_TRY(hipGetLastError());
+    return SGCN_OK;
+}
+
 extern "C" int sgcn_gather_rows_f32(const float* in, int64_t ldi, const int32_t* r, int32_t n,
                                     int32_t d, float* out, int64_t ldo, void* stream) {
     SGCN_REQUIRE(n >= 0 && d >= 0, "gather_rows: negative size");

@@ -12,6 +12,9 @@ two products).
                  column-offset view, ``add=`` / ``add_rows=``): it decides on alignment and, with ``bf16`` (--full_batch_dtype
                  bf16), rounds the dense operand into a bfloat16 scratch table the kernel gathers from (sgcn_spmm_*_b16)
   model_matrix   the StaticMatrix of one model's aggregation layers (the operand width its plan is made for)
+  EdgeMask       --edge_dropout: the mask a StaticMatrix and its transpose share; inside a training step (begin_step .. end_step)
+                 every product of either reads a value array re-drawn from the base values under the step's key
+                 (ops.edge_revalue), outside of one the base values -- the product kernels are the same either way
   static_kernel_for   the cost model 'auto' decides by; train.py builds on this module, never the other way round
   StaticBatch    what Model.upload / get_data accept in place of a PackedBatch: fields[l] = arange(N), unit scales,
                  the N x C label table, and ``rows`` -- the sorted subset of vertices the loss runs over
@@ -95,6 +98,25 @@ def check_feature_dtype(flags=None):
     return bool(f.full_batch), bool(f.test_full_batch)
 
 
+def check_edge_dropout(flags=None):
+    """--edge_dropout as a float (0.0 = off), with what it has no kernel or no meaning for refused.  Needs no device; a sibling
+    of check_full_batch, called beside it."""
+    f = FLAGS if flags is None else flags
+    p = float(getattr(f, 'edge_dropout', 0.0))
+    if not (0.0 <= p < 1.0):                  # (NaN too; 1 - p is then at least 2^-53, which fp32 holds)
+        raise ValueError("--edge_dropout must lie in [0, 1) (0 = off), got %r" % (getattr(f, 'edge_dropout', 0.0),))
+    if p > 0:
+        if not f.full_batch:
+            raise ValueError("--edge_dropout needs --full_batch: it re-draws the values of the static training adjacency once "
+                             "per full-graph step, and no other mode trains on one")
+        if f.full_batch_kernel == 'lds':
+            raise ValueError("--edge_dropout is not supported with --full_batch_kernel lds: the LDS-staged sweep runs unit "
+                             "plans, which carry no value array to re-draw")
+        if getattr(f, 'gradvar', False):
+            raise ValueError("--edge_dropout is not supported with --gradvar: the study compares two samplers on one adjacency")
+    return p
+
+
 def full_batch_bf16(flags=None):
     """--full_batch_dtype as a bool (bfloat16 operand?)."""
     return getattr(FLAGS if flags is None else flags, 'full_batch_dtype', 'fp32') == 'bf16'
@@ -142,6 +164,15 @@ def _aligned(t):
     return t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % 4 == 0)
 
 
+class EdgeMask(object):
+    """The edge mask of one adjacency (--edge_dropout; the contract: include/sgcn.h SGCN_EDGE_SITE), shared by a StaticMatrix
+    and its transpose: ``keep`` = 1 - p, and between begin_step and end_step the step's ``key``.  ``serial`` counts the
+    steps: an array drawn for an earlier step is drawn again before it is read."""
+
+    def __init__(self, p):
+        self.keep, self.key, self.serial = 1.0 - float(p), None, 0
+
+
 class StaticMatrix(object):
     """A static sparse matrix on the device, multiplied many times: ``kernel`` is 'rows' (the row-gather kernel on a
     DeviceCSR), 'cs' (column sweep) or 'lds' (LDS-staged sweep + residual), or 'auto': static_kernel_for(nnz, d, products)
@@ -152,15 +183,33 @@ class StaticMatrix(object):
     ``bf16``: every product rounds ``x`` to nearest even into a bfloat16 scratch table -- one per operand width, allocated
     once and reused every epoch -- and runs the kernel's bfloat16-operand form: half the operand's bytes per nonzero, the
     sums and ``out`` fp32, bit for bit the fp32 product of the rounded operand.  The transpose inherits it.  The LDS sweep
-    has no such form: forcing it is refused, 'auto' never picks it."""
+    has no such form: forcing it is refused, 'auto' never picks it.
+
+    ``edge_dropout`` p > 0: the matrix keeps its base value arrays untouched and owns, per value array a product can read
+    (its plan's; the row kernel's CSR where ``kernel_for`` falls back to it; the same for the transpose), the entries' pair
+    keys and one re-drawn array.  ``begin_step(key)`` .. ``end_step()`` bracket a training step: in between, every product
+    of the matrix and of its transpose reads values re-drawn under ``key`` -- each array once per step, before its first
+    use --, outside the base values.  The values stay fp32, so ``bf16`` is unaffected; the plan cache stores base values;
+    the LDS sweep's unit plans have no value array: refused like ``bf16``."""
 
     bf16 = False          # (the fp32 operand is the default of every instance)
+    edge = None           # (no edge mask)
 
-    def __init__(self, a, device, kernel='auto', products=1, d=128, cache_path=None, _transpose_of=None, bf16=False):
+    def __init__(self, a, device, kernel='auto', products=1, d=128, cache_path=None, _transpose_of=None, bf16=False,
+                 edge_dropout=0.0):
         a = a.tocsr()
         self.bf16, self._scratch, self._widened = bool(bf16), {}, {}
         if self.bf16 and kernel == 'lds':
             raise ValueError("the LDS-staged sweep has no bfloat16-operand form")
+        if _transpose_of is not None:
+            self.edge = _transpose_of.edge
+        elif edge_dropout:
+            if not 0.0 < float(edge_dropout) < 1.0:
+                raise ValueError("edge_dropout must lie in [0, 1), got %r" % (edge_dropout,))
+            self.edge = EdgeMask(edge_dropout)
+        if self.edge is not None and kernel == 'lds':
+            raise ValueError("the LDS-staged sweep runs unit plans: there is no value array to re-draw under an edge mask")
+        self._redrawn = {}
         self.a, self.device, self.shape, self.nnz = a, device, (int(a.shape[0]), int(a.shape[1])), int(a.nnz)
         self.requested, self.products, self.d_hint, self.cache_path = kernel, int(products), int(d), cache_path
         self._transpose = _transpose_of
@@ -168,6 +217,8 @@ class StaticMatrix(object):
         self._tuned = set()
         self.plan_from_cache = False
         self.kernel = self._choose(kernel)
+        if self.edge is not None:
+            self._edge_slot(self.kernel)         # the pair keys of the matrix's own plan: decoded and uploaded once, here
 
     def _choose(self, kernel):
         a, d = self.a, self.d_hint
@@ -182,7 +233,7 @@ class StaticMatrix(object):
                 return 'rows'
             # a large graph WITH communities (>= 90 % of its nonzeros inside tiles that share their columns): the LDS-staged
             # sweep + the column sweep on the rest; anything else: the column sweep alone
-            if self.cache_path is None and self.nnz >= 2000000 and d >= 128 and not self.bf16:
+            if self.cache_path is None and self.nnz >= 2000000 and d >= 128 and not self.bf16 and self.edge is None:
                 self._plan = ops.LdsSweepCSR.for_graph(a, self.device)
                 if self._plan is not None:
                     return 'lds'
@@ -205,6 +256,51 @@ class StaticMatrix(object):
         if self._rows is None:
             self._rows = ops.DeviceCSR.from_scipy(self.a, self.device)
         return self._rows
+
+    # ---- edge dropout ------------------------------------------------------------------------------------------------------
+    def _edge_slot(self, k):
+        """What kernel ``k`` ('rows' or the matrix's own sweep) reads inside a step: the base value array of its plan, the
+        pair key of every stored entry (decoded from the plan's own records, ops.plan_entries), the array the step's
+        values are drawn into and -- for the row kernel -- the CSR that carries it."""
+        slot = self._redrawn.get(k)
+        if slot is None:
+            plan = self.rows_csr if k == 'rows' else self._plan
+            # (the row kernel's CSR is the host matrix in its stored order: nothing to read back from the device)
+            entries = ops.csr_entries(self.a.indptr, self.a.indices) if k == 'rows' else ops.plan_entries(plan)
+            pair = torch.from_numpy(ops.edge_pair_keys(*entries).view(np.int32)).to(self.device)
+            out = torch.empty_like(plan.val)
+            csr = ops.DeviceCSR(plan.shape, plan.rowptr, plan.col, out, plan.plan, host_rowptr=plan.host_rowptr) \
+                if k == 'rows' else None
+            slot = self._redrawn[k] = dict(base=plan.val, pair=pair, out=out, csr=csr, serial=0)
+        return slot
+
+    def _edge_values(self, k):
+        """None outside a step; inside one, kernel k's slot with the step's values drawn (once per step and array)."""
+        e = self.edge
+        if e is None or e.key is None:
+            return None
+        slot = self._edge_slot(k)
+        if slot['serial'] != e.serial:
+            ops.edge_revalue(slot['base'], slot['pair'], e.key, e.keep, out=slot['out'])
+            slot['serial'] = e.serial
+        return slot
+
+    def begin_step(self, key):
+        """From here to end_step the products of this matrix and of its transpose read values re-drawn under ``key``: the
+        matrix's own array now, ahead of the forward; every other one before its first use in the step."""
+        e = self.edge
+        if e is not None:
+            e.key, e.serial = int(key) & 0xFFFFFFFF, e.serial + 1
+            self._edge_values(self.kernel)
+
+    def end_step(self):
+        """The base values are back in effect (nothing was written to them)."""
+        if self.edge is not None:
+            self.edge.key = None
+
+    def _rows_now(self):
+        slot = self._edge_values('rows')
+        return self.rows_csr if slot is None else slot['csr']
 
     def _autotune(self, x, d):
         key = (d, x.dtype == torch.bfloat16)
@@ -265,9 +361,16 @@ class StaticMatrix(object):
         if k not in ('rows', self.kernel):
             raise ValueError("this matrix runs on %r or on the row kernel, not on %r" % (self.kernel, k))
         if k == 'rows':
-            return ops.spmm(self.rows_csr, x, out=out, beta=beta)
+            return ops.spmm(self._rows_now(), x, out=out, beta=beta)
         self._autotune(x, d)
-        return (ops.spmm_lds if k == 'lds' else ops.spmm_cs)(self._plan, x, out=out, beta=beta, d=d)
+        slot = self._edge_values(k)
+        if slot is None:
+            return (ops.spmm_lds if k == 'lds' else ops.spmm_cs)(self._plan, x, out=out, beta=beta, d=d)
+        self._plan.live_val = slot['out']         # (the sweep reads the step's values for this product only)
+        try:
+            return ops.spmm_cs(self._plan, x, out=out, beta=beta, d=d)
+        finally:
+            self._plan.live_val = None
 
     def product(self, x, out=None, add=None, add_rows=0):
         """out = A x (+ add on the first ``add_rows`` rows), the keyword set of ops.spmm that PlainAggregator uses.  The row
@@ -279,7 +382,7 @@ class StaticMatrix(object):
         if add is None:
             return self.multiply(x, out=out, kernel=k)
         if k == 'rows':
-            return ops.spmm(self.rows_csr, x, out=out, add=add, add_rows=add_rows)
+            return ops.spmm(self._rows_now(), x, out=out, add=add, add_rows=add_rows)
         if out is None:
             out = torch.empty((M, d), dtype=torch.float32, device=x.device)
         r = int(add_rows)
@@ -298,14 +401,17 @@ class StaticMatrix(object):
                     kernel=kernel, products=self.products)
 
 
-def model_matrix(adj, device, model, products, cache_path=None, kernel=None, bf16=False, layers=None):
+def model_matrix(adj, device, model, products, cache_path=None, kernel=None, bf16=False, layers=None, edge_dropout=0.0):
     """The StaticMatrix of ``adj`` for the aggregation layers of ``model``: the kernel of --full_batch_kernel unless one is
     given, the plan made for the widest operand -- agg0_dim at layer 0, --hidden1 behind it -- of the first ``layers``
     aggregation layers (default: all; an exact history pass counts one less).  ``products`` is the caller's to know."""
     n = model.L if layers is None else max(int(layers), 1)
     widths = [model.agg0_dim if l == 0 else FLAGS.hidden1 for l in range(n)]
+    # (the keyword is passed only when set: with the flag off the call is the one the matrix classes -- the recording
+    # stand-ins of the CPU tests among them -- have always taken)
+    edge = dict(edge_dropout=edge_dropout) if edge_dropout else {}
     return StaticMatrix(adj, device, FLAGS.full_batch_kernel if kernel is None else kernel, products,
-                        max(widths or [FLAGS.hidden1]), cache_path, bf16=bf16)
+                        max(widths or [FLAGS.hidden1]), cache_path, bf16=bf16, **edge)
 
 
 class StaticCur(object):

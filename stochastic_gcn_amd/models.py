@@ -1011,8 +1011,14 @@ class GCN(Model):
         self.g_t += time() - t
 
         t = time()
+        # --edge_dropout: a TRAINING step over a static batch multiplies by the adjacency re-drawn under the step's edge mask
+        # (keyed by the counter that keys the step's activation dropout); the base values are back when the step returns
+        masked = feed_dict.matrix if (self.is_training and isinstance(feed_dict, StaticBatch)
+                                      and getattr(feed_dict.matrix, 'edge', None) is not None) else None
         ops.pin_stream()
         try:
+            if masked is not None:
+                masked.begin_step(ops.edge_key(self.dropout_seed, self.dropout_step))
             self.forward(cur)
             loss, acc, pred, dlogits = self.loss_and_grad(cur.labels)
             if self.is_training:
@@ -1022,6 +1028,8 @@ class GCN(Model):
                 self.adam_step()
             self.update_history(cur)
         finally:
+            if masked is not None:
+                masked.end_step()
             ops.unpin_stream()
         self.dropout_step += 1          # the next step draws fresh masks at every dropout site
         if sync:

@@ -776,6 +776,8 @@ class ColumnSweepCSR(object):
         self._clocks = clocks or (SweepClock(), SweepClock())                     # (fp32 operand, bfloat16 operand)
         self._tuning, self._cache = False, None                                    # (_cache: where ``cached`` wants it stored)
         self.tile_ptr, self.colrow, self.val = to(p["tile_ptr"]), to(p["colrow"]), to(p["val"])
+        self.live_val = None       # a re-drawn value array the products read instead of ``val`` (full_batch.StaticMatrix,
+                                   # inside a training step under --edge_dropout); ``val``, the base values, is what is saved
         self.tile_rows, self.tile_slots = to(p["tile_rows"]), to(p["tile_slots"])
         self.fix = to(p["fix"]) if self.nfix else None
         self.ws, self.device = None, device
@@ -1128,7 +1130,8 @@ class ColumnSweepCSR(object):
             self._hint = np.ascontiguousarray(pad.reshape(nl, rnd).max(axis=1))
             self._hint_round = rnd
         return _ffi.CsPlan(self.R, self.ntiles, self.tile_ptr.data_ptr(), self.colrow.data_ptr(),
-                           self.val.data_ptr(), self.tile_rows.data_ptr(), self.tile_slots.data_ptr(),
+                           (self.val if self.live_val is None else self.live_val).data_ptr(), self.tile_rows.data_ptr(),
+                           self.tile_slots.data_ptr(),
                            _ptr(self.fix), self.nfix, self.nslots, _ptr(self.ws),
                            0 if self.ws is None else self.ws.numel(), rnd, self._hint.ctypes.data,
                            -1 if self.grouped else int(self.clock(bf16).pace.get(d, 0)), self.G,
@@ -1650,6 +1653,103 @@ def dropout(x, drop, out=None):
     op, ldo = _rows2d(out, "out")
     st = drop.struct(d)
     check(lib.sgcn_dropout_f32(xp, ldx, n, d, C.byref(st), op, ldo, _stream()))
+    return out
+
+
+# ---- edge dropout of a static adjacency (include/sgcn.h SGCN_EDGE_SITE / sgcn_edge_revalue_f32) ------------------------
+EDGE_SITE = 0x45444745          # the dropout site of the edge mask: no layer index (a layer's sites: i and i + 4096)
+EDGE_ALWAYS = 0xFFFFFFFF        # the pair key of an entry no mask drops: the diagonal, a plan's pads
+CS_PAD_BITS = 0x80000000        # the value bits of a pad entry of a G = 2 / 4 column-sweep plan (sgcn_csplang_*)
+
+
+def _fmix32_np(h):
+    """``_fmix32`` on a uint64 array holding 32-bit values."""
+    m = np.uint64(0xFFFFFFFF)
+    h = h & m
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x85EBCA6B)) & m
+    h = h ^ (h >> np.uint64(13))
+    h = (h * np.uint64(0xC2B2AE35)) & m
+    return h ^ (h >> np.uint64(16))
+
+
+def edge_key(seed, step):
+    """The key of the edge mask of one training step (the step counter that keys the step's activation dropout)."""
+    return dropout_key(seed, EDGE_SITE, step)
+
+
+def edge_pair_keys(row, col, pad=None):
+    """One uint32 per stored entry: the hash of the unordered pair {row, col} of the ORIGINAL matrix (a matrix and its
+    transpose give an edge the same key), EDGE_ALWAYS on the diagonal and where ``pad`` is set."""
+    row, col = np.asarray(row, dtype=np.int64), np.asarray(col, dtype=np.int64)
+    m = np.uint64(0xFFFFFFFF)
+    u, v = np.minimum(row, col).astype(np.uint64) & m, np.maximum(row, col).astype(np.uint64) & m
+    h = _fmix32_np(_fmix32_np(u * np.uint64(0x9E3779B1) + np.uint64(0x27D4EB2F)) + ((v * np.uint64(0x85EBCA77)) & m))
+    h[h == np.uint64(EDGE_ALWAYS)] = np.uint64(EDGE_ALWAYS - 1)
+    always = row == col
+    if pad is not None:
+        always = always | np.asarray(pad, dtype=bool)
+    h[always] = np.uint64(EDGE_ALWAYS)
+    return np.ascontiguousarray(h.astype(np.uint32))
+
+
+def csr_entries(rowptr, col):
+    """(row, col, pad) of every stored entry of a CSR (a DeviceCSR's value array): no pads."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    row = np.repeat(np.arange(rowptr.shape[0] - 1, dtype=np.int64), np.diff(rowptr))
+    return row, np.asarray(col, dtype=np.int64), np.zeros(row.shape[0], dtype=bool)
+
+
+def cs_entries(tile_ptr, colrow, val, tile_rows, G=1):
+    """(row, col, pad) of every stored entry of an unlabelled column-sweep plan without column ranges, decoded from the
+    plan's own host records (a built plan and one loaded from the cache alike): entry e of tile t belongs to bin
+    g = e mod G, its local row is colrow >> 28, its output row tile_rows[t * 16 G + 16 g + local row] (the virtual rows of
+    a split row name the same output row); with G = 2 / 4 an entry whose value bits are CS_PAD_BITS is a pad."""
+    G = max(int(G), 1)
+    tile_ptr = np.asarray(tile_ptr, dtype=np.int64)
+    cr = np.ascontiguousarray(colrow, dtype=np.int32).view(np.uint32).astype(np.int64)
+    n = cr.shape[0]
+    if tile_ptr.shape[0] == 0 or int(tile_ptr[-1]) != n:
+        raise ValueError("the tile pointer does not cover the plan's %d entries" % n)
+    tile = np.repeat(np.arange(tile_ptr.shape[0] - 1, dtype=np.int64), np.diff(tile_ptr))
+    e = np.arange(n, dtype=np.int64) - tile_ptr[:-1][tile]
+    pad = np.zeros(n, dtype=bool) if G == 1 else \
+        np.ascontiguousarray(val, dtype=np.float32).view(np.uint32) == np.uint32(CS_PAD_BITS)
+    slot = tile * (16 * G) + (e % G) * 16 + (cr >> 28)
+    row = np.where(pad, -1, np.asarray(tile_rows, dtype=np.int64)[np.where(pad, 0, slot)] if n else np.zeros(0, np.int64))
+    if n and int(row[~pad].min(initial=0)) < 0:
+        raise ValueError("a stored entry of the plan sits on a pad row")
+    return row, np.where(pad, -1, cr & ((1 << 28) - 1)), pad
+
+
+def plan_entries(plan):
+    """(row, col, pad) of every stored entry of a device plan's value array: a DeviceCSR, or a ColumnSweepCSR as
+    full_batch.StaticMatrix builds it (unlabelled, no column ranges); anything else has no decode."""
+    if isinstance(plan, DeviceCSR):
+        return csr_entries(plan.host_rowptr if plan.host_rowptr is not None else plan.rowptr.cpu().numpy(), plan.col.cpu().numpy())
+    if isinstance(plan, ColumnSweepCSR):
+        if plan.grouped or plan.ranged or plan.pos2col is not None or plan.R != 16:
+            raise ValueError("edge dropout decodes unlabelled column-sweep plans without column ranges only")
+        return cs_entries(plan.tile_ptr.cpu().numpy(), plan.colrow.cpu().numpy(), plan.val.cpu().numpy(),
+                          plan.tile_rows.cpu().numpy(), plan.G)
+    raise ValueError("edge dropout has no decode for a %s (the LDS sweep's unit plans carry no value array)" % type(plan).__name__)
+
+
+def edge_revalue(base, pair, key, keep, out=None):
+    """out[p] = base[p] under the edge mask of ``key`` (sgcn_edge_revalue_f32): the bits of base where pair is EDGE_ALWAYS,
+    base * (1 / keep) where the pair is kept, +0.0 where it is dropped.  ``out`` must overlap neither ``base`` nor ``pair``."""
+    _dev(base, torch.float32, "base")
+    _dev(pair, torch.int32, "pair")            # (uint32 bits; torch has no unsigned 32-bit device type)
+    n = int(base.numel())
+    if base.dim() != 1 or pair.dim() != 1 or int(pair.numel()) != n or not (base.is_contiguous() and pair.is_contiguous()):
+        raise ValueError("base and pair must be contiguous 1-D arrays of one length")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=base.device)
+    _dev(out, torch.float32, "out")
+    if out.dim() != 1 or int(out.numel()) != n or not out.is_contiguous():
+        raise ValueError("out must be a contiguous 1-D array of base's length")
+    check(lib.sgcn_edge_revalue_f32(base.data_ptr(), pair.data_ptr(), n, int(key) & 0xFFFFFFFF, float(keep), out.data_ptr(),
+                                    _stream()))
     return out
 
 

@@ -26,7 +26,8 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
-from .full_batch import (StaticBatch, StaticMatrix, check_feature_dtype, check_full_batch, full_batch_bf16, full_batch_products,
+from .full_batch import (StaticBatch, StaticMatrix, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
+                         full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
 from .parallel import DataParallel
@@ -230,6 +231,8 @@ class Trainer(object):
         torch.manual_seed(FLAGS.seed)
         # (--full_batch / --test_full_batch with an estimator, a sampler option or several ranks: refused before a device is touched)
         self.full_batch, self.test_full_batch = check_full_batch(world=int(os.environ.get("WORLD_SIZE", "1")))
+        # (--edge_dropout outside [0, 1), without --full_batch, on the LDS sweep or with --gradvar: too)
+        self.edge_dropout = check_edge_dropout()
         # (--feature_dtype bf16 without the bf16 GEMMs or without a full-graph mode: too; which model's table it selects)
         self.feature_bf16 = check_feature_dtype()
         # (--history_init exact / --history_refresh / --history_error without a history, with two of them, on several ranks: too)
@@ -327,7 +330,13 @@ class Trainer(object):
         if self.full_batch:
             # exact full-graph training: no sampler, no prefetcher, no staging slots -- one static batch over train_adj
             t = time()
-            self.train_static = self._static_batch(train_adj, 'train', caches[0], self.train_model, self.train_d)
+            self.train_static = self._static_batch(train_adj, 'train', caches[0], self.train_model, self.train_d,
+                                                   edge_dropout=self.edge_dropout)
+            if self.edge_dropout > 0:
+                log('[sgcn] --edge_dropout {:g}: every training step multiplies by the adjacency re-drawn under an edge mask '
+                    '(keep {:g}; an undirected edge is dropped as a whole, kept entries are scaled by 1 / keep, the diagonal '
+                    'is never dropped); evaluation and every other product read the adjacency itself'.format(
+                        self.edge_dropout, float(np.float32(1.0 - self.edge_dropout))))
             self.static_setup_s += time() - t
         else:
             self.train_sch = PyScheduler(train_adj, labels, L, train_degrees, placeholders,
@@ -374,10 +383,11 @@ class Trainer(object):
         self.last_epoch = {}
 
     # ---- the full-graph modes (full_batch.py) -----------------------------------------------------
-    def _static_batch(self, adj, which, cache_path, model, rows):
+    def _static_batch(self, adj, which, cache_path, model, rows, edge_dropout=0.0):
         """The static batch of one adjacency for one model: the matrix with its plan (kernel by --full_batch_kernel; auto:
         static_kernel_for on the number of times the plan will run), the label table, the loss rows."""
-        mat = model_matrix(adj, self.device, model, full_batch_products(which), cache_path, bf16=full_batch_bf16())
+        mat = model_matrix(adj, self.device, model, full_batch_products(which), cache_path, bf16=full_batch_bf16(),
+                           edge_dropout=edge_dropout)
         self.static_matrices.append((adj, mat))
         if self._labels_dev is None:
             self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
