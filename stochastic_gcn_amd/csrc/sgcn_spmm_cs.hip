@@ -29,6 +29,7 @@
 //   cs_spmm16_kernel<U, EXTRA>     one 16-row tile per wavefront, pinned accumulators, up to 320 columns per pass
 //   cs_spmm16g2k_kernel<U, WIDE>   two 16-row bins per wavefront on 128-column passes, software-pipelined, packed FMAs:
 //                                  what ColumnSweepCSR.choose_g selects for most widths (bench default at d = 602)
+//   cs_epilogue<G>                 the end of the G = 2 / G = 4 kernels: row ids and slots read once per wave, 16 stores back to back
 //   cs_fix_kernel<VW>              ordered sum of a split row's workspace slots
 // Every asm statement that enters the VGPR-indexing mode (s_set_gpr_idx_*: the index lives in M0) or points M0 at an
 // LDS-DMA destination lists "m0" as a clobber, so that LLVM's M0-initialisation merging never carries a value across
@@ -93,6 +94,106 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 #define SGCN_CS_ROWS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+
+// ---- the epilogue of the two- and four-group sweep kernels ----------------------------------------------------------------
+// All waves of a launch reach the end of the sweep together (that is the design), so whatever a wave waits for here it waits
+// for behind 4,095 others.  On gfx9 the vector memory counter counts stores as well as loads: an epilogue that reads a row's
+// id, waits, reads its slot, waits, stores, and goes on to the next row is a chain of 32 dependent round trips per wave, each
+// queued behind that wave's previous store.  So: the tile's 16 G row ids and slots are ONE coalesced load each (lane l reads
+// entry l), issued together and waited for once; the lane that holds an entry makes the entry's destination of them -- the
+// address of the C row or of the workspace slot, bit 0 set for a slot (rows are 16-byte aligned), 0 for an entry without a
+// row -- and its row scale (one gathered load; 1 for a slot, which is stored unscaled: x * 1 is x); row r's pair reaches the
+// lanes of its bin by ds_bpermute, and the 16 rows are stored back to back.  Rows without an owner, lanes past d and the
+// ragged last vector are execution masks around stores, and nothing between two stores waits for memory.  beta != 0: the
+// old rows are read four rows at a time in front of those rows' stores.
+// The arithmetic is what the kernels have always done, spelled out so that it cannot be contracted differently:
+// acc * rs, then fma(beta, old, .).
+// (cs_spmm16_kernel, one group per wave, keeps its own row loop: DESIGN.md 3.2.)
+template <int G, class Acc>
+__device__ __forceinline__ void cs_epilogue(const CsArgs& a, Acc&& acc) {
+    static_assert(G == 2 || G == 4, "lane groups per wavefront");
+    typedef Vec<4>::type VT;
+    constexpr int kEnt = 16 * G;                                 // row entries of a tile
+    // The lane's geometry is made again here, from a thread id the optimiser cannot see through: nothing of the epilogue is
+    // computed in front of the sweep and carried across it (these kernels used to spill such values around the loop).
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & (kWave - 1);
+    const int64_t tile = cs_first_tile(a) + tid / kWave;
+    const int f4 = a.slab * (4 * (kWave / G)) + (lane & (kWave / G - 1)) * 4;     // my float4
+    const bool act4 = f4 < a.d;
+    const int ent = lane < kEnt ? lane : 0;                      // (lanes without an entry re-read entry 0)
+    const int32_t myrow = a.tile_rows[tile * kEnt + ent];
+    const int32_t myslot = a.tile_slots[tile * kEnt + ent];
+    const bool owned = myrow >= 0, split = owned & (myslot >= 0);       // (&: the slot is read whatever the row id says)
+    const int32_t rrow = owned ? myrow : 0;
+    float myrs = 1.0f;
+    if (a.rscale) myrs = a.rscale[rrow];
+    if (split) myrs = 1.0f;
+    uint64_t mydst = split ? (((uint64_t)(uintptr_t)a.ws + (uint64_t)((int64_t)myslot * a.ldw) * 4u) | 1u)
+                           : (uint64_t)(uintptr_t)a.C + (uint64_t)((int64_t)rrow * a.ldc) * 4u;
+    if (!owned) mydst = 0;
+    const int sel = (lane / (kWave / G)) * 64;                   // ds_bpermute byte address of my bin's entry 0
+    auto bcast = [&](int x, int r) -> int { return __builtin_amdgcn_ds_bpermute(sel + 4 * r, x); };
+    // (an address made of integers is a generic one to the compiler, and a flat store counts on two counters: say global)
+    typedef __attribute__((address_space(1))) float gfloat;
+    typedef __attribute__((address_space(1))) VT gvec;
+    struct Row { gfloat* p; bool on, ws; float rs; };
+    auto row_of = [&](int r) -> Row {
+        const uint64_t dst = (uint64_t)(uint32_t)bcast((int)(uint32_t)mydst, r) |
+                             ((uint64_t)(uint32_t)bcast((int)(uint32_t)(mydst >> 32), r) << 32);
+        Row w;
+        w.p = (gfloat*)(uintptr_t)(dst & ~(uint64_t)1);
+        w.on = dst != 0;
+        w.ws = (dst & 1u) != 0;
+        w.rs = __int_as_float(bcast(__float_as_int(myrs), r));
+        return w;
+    };
+    const int left = a.d - f4;
+    auto store = [&](const Row& w, VT res) {
+        if (w.on && act4) {
+            if (left >= 4) *(gvec*)(w.p + f4) = res;
+            else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (k < left) w.p[f4 + k] = res[k];
+            }
+        }
+    };
+    if (a.beta == 0.f) {
+        static_for<16>([&](auto rc) {
+            const Row w = row_of(decltype(rc)::value);
+            store(w, acc(rc) * w.rs);
+        });
+        return;
+    }
+    constexpr int kGroup = 4;                                    // rows whose old values are in flight together
+    static_for<16 / kGroup>([&](auto gc) {
+        constexpr int r0 = decltype(gc)::value * kGroup;
+        Row w[kGroup];
+        VT old[kGroup];
+        static_for<kGroup>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            w[i] = row_of(r0 + i);
+            old[i] = vzero<4>();
+            if (w[i].on && !w[i].ws && act4) {
+                if (left >= 4) old[i] = *(const gvec*)(w[i].p + f4);
+                else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) if (e < left) old[i][e] = w[i].p[f4 + e];
+                }
+            }
+        });
+        static_for<kGroup>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            VT res = acc(std::integral_constant<int, r0 + i>{}) * w[i].rs;
+            if (!w[i].ws) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) res[k] = __builtin_fmaf(a.beta, old[i][k], res[k]);
+            }
+            store(w[i], res);
+        });
+    });
+}
 
 // R = 16 specialisation with the accumulators PINNED to fixed VGPRs and updated by ONE indexed FMA
 // group per nonzero:
@@ -476,28 +577,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         entries(p0 + 2 * kWave, ncr, nv);
     }
 
-    const int32_t* rows = a.tile_rows + tile * 32 + (hi ? 16 : 0);
-    const int32_t* slots = a.tile_slots + tile * 32 + (hi ? 16 : 0);
-    const int left = a.d - f4;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int row = rows[r];
-        const VT accv = {axy[2 * r], axy[2 * r + 1], azw[2 * r], azw[2 * r + 1]};
-        if (row < 0 || !act) continue;
-        const int slot = slots[r];
-        if (slot >= 0) {
-            vstore<4>(a.ws + (int64_t)slot * a.ldw + f4, accv);
-        } else {
-            float* out = a.C + (int64_t)row * a.ldc;
-            const float rs = a.rscale ? a.rscale[row] : 1.0f;
-            VT res = accv * rs;
-            if (a.beta != 0.f) {
-                if (left >= 4) res += a.beta * vload<4>(out + f4);
-                else for (int e = 0; e < left; e++) res[e] += a.beta * out[f4 + e];
-            }
-            if (left >= 4) vstore<4>(out + f4, res); else vstore_head<4>(out + f4, res, left);
-        }
-    }
+    cs_epilogue<2>(a, [&](auto rc) -> VT {
+        constexpr int r = decltype(rc)::value;
+        return VT{axy[2 * r], axy[2 * r + 1], azw[2 * r], azw[2 * r + 1]};
+    });
 }
 
 // ---- four lane groups per wavefront (plan->G == 4): every row of the graph resident in ONE round of tiles ---------------
@@ -696,28 +779,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         entries(p0 + 2 * kWave, ncr, nv);
     }
 
-    const int32_t* rows = a.tile_rows + tile * 64 + bin * 16;
-    const int32_t* slots = a.tile_slots + tile * 64 + bin * 16;
-    const int left = a.d - f4;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int row = rows[r];
-        const VT accv = {axy[2 * r], axy[2 * r + 1], azw[2 * r], azw[2 * r + 1]};
-        if (row < 0 || !act) continue;
-        const int slot = slots[r];
-        if (slot >= 0) {
-            vstore<4>(a.ws + (int64_t)slot * a.ldw + f4, accv);
-        } else {
-            float* out = a.C + (int64_t)row * a.ldc;
-            const float rs = a.rscale ? a.rscale[row] : 1.0f;
-            VT res = accv * rs;
-            if (a.beta != 0.f) {
-                if (left >= 4) res += a.beta * vload<4>(out + f4);
-                else for (int e = 0; e < left; e++) res[e] += a.beta * out[f4 + e];
-            }
-            if (left >= 4) vstore<4>(out + f4, res); else vstore_head<4>(out + f4, res, left);
-        }
-    }
+    cs_epilogue<4>(a, [&](auto rc) -> VT {
+        constexpr int r = decltype(rc)::value;
+        return VT{axy[2 * r], axy[2 * r + 1], azw[2 * r], azw[2 * r + 1]};
+    });
 }
 
 // fix-up of split rows: ordered slot sum + epilogue (float4 path only).  An ITEM = 64 float4 columns of one split row.
