@@ -54,7 +54,8 @@ const char* sgcn_last_error(void);
  *       subset of N-row tables -- sgcn_softmax_ce_rows_f32 / sgcn_sigmoid_ce_rows_f32; a bfloat16 dense operand for the
  *       static-graph products -- sgcn_spmm_csr_b16 / _csr_add_b16 / sgcn_spmm_cs_b16 / sgcn_spmm_cs_variant_b16; the staleness
  *       of a history -- sgcn_hist_error_f32 / _h16 / _ws_doubles; the value array of a static plan re-drawn under an
- *       edge mask -- sgcn_edge_revalue_f32) */
+ *       edge mask -- sgcn_edge_revalue_f32; the element-wise neighbour maximum over a CSR pattern and its backward --
+ *       sgcn_spmax_csr_f32 / sgcn_spmax_csr_bwd_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -437,6 +438,46 @@ int sgcn_spmm_cs_b16(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
                      float* dev_C, int64_t ldc, float beta, void* stream);
 /* sgcn_spmm_cs_variant for sgcn_spmm_cs_b16: the same kernel and geometry, marked "[bf16 operand]". */
 int sgcn_spmm_cs_variant_b16(const sgcn_csplan_t* plan, int32_t d, char* buf, int32_t buflen);
+
+/* ---- element-wise neighbour maximum over a CSR pattern (--aggregator max; additive, still v16) ------------------------
+ * GraphSAGE's pooling aggregator without its MLP, for the full-graph modes.  No reference counterpart in gcn/ (the
+ * reference aggregates by the adjacency's linear map only, gcn/layers.py:214-257).
+ *
+ * Forward.  For the CSR pattern (dev_rowptr, dev_col) with M rows, K columns and UNIQUE column ids per row, N(i) is the
+ * stored entries of row i in stored order (the diagonal entry a normalisation put there included); stored VALUES are not
+ * read.  With B a dense K x d fp32 table of pitch ldb:
+ *     C[i, c]   = max over j in N(i) of B[j, c]
+ *     arg[i, c] = the column id j of the FIRST maximum in stored order
+ * The best starts as the first entry; a later entry replaces it only when v > best, strictly (np.argmax's rule: the first
+ * of +0.0 / -0.0 and the first of equal values is kept).  An empty row gives C = +0.0 and arg = -1.  +-inf are ordinary
+ * values.  The input must be NaN-free: that is the caller's promise, nothing checks it.  C holds bits of B -- there is
+ * no arithmetic.  dev_arg is nullable (an evaluation needs no backward); C, arg are M x d with pitches ldc, ldarg.
+ * plan is nullable (then one wavefront group per whole row).  With a plan, a row longer than T is cut into segments
+ * (sgcn_plan_t, above: a 31k-entry hub row must not sit on one wavefront); each segment writes its partial (value, id) to
+ * its slot -- values to plan->dev_ws, ids to dev_ws_arg, an int32 array of the same slot geometry ([nslots x ldw],
+ * ldw = 4*ceil(d/4)), required when the plan has split rows -- and an ordered fix-up pass walks a split row's slots in
+ * order with the same strict comparison: the first maximum of the whole row survives, wherever the cuts fall.
+ *
+ * Backward.  dB[j, c] = sum over the rows i with arg[i, c] == j of G[i, c], the terms taken in ascending i.  It is a
+ * gather over the TRANSPOSED pattern: row j of A^T (dev_t_rowptr, dev_t_row; K rows over M columns) lists its source
+ * rows i ascending, as sgcn_csr_transpose_host produces them; for each the kernel reads G[i, :] and arg[i, :] and adds
+ * where the id equals j.  No atomics: the result is bitwise reproducible.  With add != NULL: dB[r, :] += add[r, :] for
+ * r < add_rows in the epilogue, exactly as in sgcn_spmm_csr_add_f32 (the self half of a concat aggregator).  t_plan is a
+ * plan over dev_t_rowptr (nullable); a split row's partial sums go to its slots and the ordered fix-up adds them in slot
+ * order (the scheme of the row SpMM).  G, arg are M x d, dB is K x d.
+ *
+ * Both validate before any HIP call: a null operand, d <= 0, a pitch below d, a plan with split rows but without
+ * dev_ws / dev_ws_arg, or a workspace smaller than nslots x ldw give SGCN_ERR_INVALID with nothing written. */
+int sgcn_spmax_csr_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d,
+                       const float* dev_B, int64_t ldb, float* dev_C, int64_t ldc,
+                       int32_t* dev_arg /* nullable */, int64_t ldarg,
+                       const sgcn_plan_t* plan /* nullable */, int32_t* dev_ws_arg /* with a plan that splits rows */,
+                       void* stream);
+int sgcn_spmax_csr_bwd_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t_row, int32_t K, int32_t M, int32_t d,
+                           const float* dev_G, int64_t ldg, const int32_t* dev_arg, int64_t ldarg,
+                           float* dev_dB, int64_t lddb,
+                           const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                           const sgcn_plan_t* t_plan /* nullable */, void* stream);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-

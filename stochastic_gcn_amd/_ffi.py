@@ -153,6 +153,11 @@ SIGNATURES = {
     "sgcn_spmm_cs_b16": (C.c_int, [C.POINTER(CsPlan), C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P,
                                    P, P, P, C.c_int64, C.c_float, P]),
     "sgcn_spmm_cs_variant_b16": (C.c_int, [C.POINTER(CsPlan), C.c_int32, C.c_char_p, C.c_int32]),
+    # element-wise neighbour maximum over a CSR pattern and its backward (--aggregator max)
+    "sgcn_spmax_csr_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64,
+                                     C.POINTER(Plan), P, P]),
+    "sgcn_spmax_csr_bwd_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64,
+                                         P, C.c_int64, C.c_int32, C.POINTER(Plan), P]),
     "sgcn_coll_available": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgcn_coll_retain": (C.c_int, []),
     "sgcn_coll_abort": (C.c_int, []),

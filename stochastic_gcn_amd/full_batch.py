@@ -10,7 +10,9 @@ two products).
                  kernel, tunes and stores the plan and dispatches to ops.spmm / ops.spmm_cs / ops.spmm_lds.  ``multiply`` is
                  the plain product (train.pp_products); ``product`` is the method PlainAggregator calls (``out=`` with a
                  column-offset view, ``add=`` / ``add_rows=``): it decides on alignment and, with ``bf16`` (--full_batch_dtype
-                 bf16), rounds the dense operand into a bfloat16 scratch table the kernel gathers from (sgcn_spmm_*_b16)
+                 bf16), rounds the dense operand into a bfloat16 scratch table the kernel gathers from (sgcn_spmm_*_b16);
+                 ``max_product`` / ``max_backward`` are what it calls under --aggregator max: the element-wise maximum over the
+                 matrix's pattern and its gradient (ops.spmax / ops.spmax_bwd on the row kernel's CSR)
   model_matrix   the StaticMatrix of one model's aggregation layers (the operand width its plan is made for)
   EdgeMask       --edge_dropout: the mask a StaticMatrix and its transpose share; inside a training step (begin_step .. end_step)
                  every product of either reads a value array re-drawn from the base values under the step's key
@@ -115,6 +117,34 @@ def check_edge_dropout(flags=None):
         if getattr(f, 'gradvar', False):
             raise ValueError("--edge_dropout is not supported with --gradvar: the study compares two samplers on one adjacency")
     return p
+
+
+AGGREGATORS = _CHOICES['aggregator']
+
+
+def check_aggregator(flags=None):
+    """--aggregator as a bool (element-wise maximum?), with the combinations the maximum has no kernel or no meaning for
+    refused.  Needs no device; a sibling of check_full_batch, called beside it."""
+    f = FLAGS if flags is None else flags
+    agg = getattr(f, 'aggregator', 'sum')
+    if agg not in AGGREGATORS:
+        raise ValueError("--aggregator must be one of %s, got %r" % ('/'.join(AGGREGATORS), agg))
+    if agg != 'max':
+        return False
+    if not (f.full_batch and f.test_full_batch):
+        raise ValueError("--aggregator max needs --full_batch and --test_full_batch: a maximum is not linear, so no sampled "
+                         "estimator carries it and sampled steps have no such kernel, and the training and the test model "
+                         "must aggregate alike")
+    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
+        raise ValueError("--aggregator max is not supported with --full_batch_dtype bf16: the maximum kernels gather from an "
+                         "fp32 table; there is no bfloat16-table form yet")
+    if getattr(f, 'feature_dtype', 'fp32') == 'bf16':
+        raise ValueError("--aggregator max is not supported with --feature_dtype bf16: the maximum kernels gather from an "
+                         "fp32 table; there is no bfloat16-table form yet")
+    if float(getattr(f, 'edge_dropout', 0.0)) > 0:
+        raise ValueError("--aggregator max is not supported with --edge_dropout: the maximum reads the adjacency's pattern, "
+                         "not its values; there is no edge-masked form yet")
+    return True
 
 
 def full_batch_bf16(flags=None):
@@ -391,6 +421,26 @@ class StaticMatrix(object):
             out[r:].zero_()
         return self.multiply(x, out=out, beta=1.0, kernel=k)
 
+    # ---- the element-wise maximum (--aggregator max) -------------------------------------------------------------------------
+    def max_product(self, x, out=None, want_arg=True):
+        """(out, arg) of ops.spmax over this matrix's PATTERN: out[i] = the element-wise maximum of the rows of ``x`` that
+        row i stores an entry for (its own where the normalisation put a diagonal entry), arg the winners' column ids for
+        ``max_backward`` (None with ``want_arg=False``).  Reads the row kernel's CSR -- pattern and segment plan -- only: no
+        sweep plan, no value array, no operand rounding."""
+        if self.bf16 or x.dtype != torch.float32:
+            raise ValueError("the element-wise maximum has no bfloat16-operand form")
+        if self.edge is not None:
+            raise ValueError("the element-wise maximum has no edge-masked form")
+        return ops.spmax(self.rows_csr, x, out=out, want_arg=want_arg)
+
+    def max_backward(self, g, arg, add=None, add_rows=0):
+        """Called on the TRANSPOSE of the matrix whose ``max_product`` gave ``arg``: the gradient of that maximum with respect
+        to its operand, out[j] = the sum of g[i] over the rows i whose winner was j, in ascending i (+ add on the first
+        ``add_rows`` rows) -- ops.spmax_bwd, a gather over this matrix's pattern."""
+        if self.bf16 or self.edge is not None:
+            raise ValueError("the element-wise maximum has no bfloat16-operand and no edge-masked form")
+        return ops.spmax_bwd(self.rows_csr, g, arg, add=add, add_rows=add_rows)
+
     def describe(self, d):
         """What train.pp_products records of a product of width d: where the plan came from, the sweep clock (the column
         sweep only), the kernel variant, the product count the kernel was chosen for."""
@@ -410,6 +460,10 @@ def model_matrix(adj, device, model, products, cache_path=None, kernel=None, bf1
     # (the keyword is passed only when set: with the flag off the call is the one the matrix classes -- the recording
     # stand-ins of the CPU tests among them -- have always taken)
     edge = dict(edge_dropout=edge_dropout) if edge_dropout else {}
+    if kernel is None and getattr(FLAGS, 'aggregator', 'sum') == 'max':
+        # every aggregation of the model is a maximum over the pattern (max_product reads rows_csr and its segment plan):
+        # no column-sweep or LDS plan, tune or cache file is made for products that never run
+        kernel = 'rows'
     return StaticMatrix(adj, device, FLAGS.full_batch_kernel if kernel is None else kernel, products,
                         max(widths or [FLAGS.hidden1]), cache_path, bf16=bf16, **edge)
 

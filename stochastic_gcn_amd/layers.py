@@ -399,6 +399,21 @@ class PlainAggregator(Layer):
         x = dense_of(x)
         n1, d = A.shape[0], x.shape[1]
         self._A, self._concat, self._d = A, concat, d
+        # --aggregator max on a full-graph matrix: the element-wise maximum over the adjacency's pattern in place of its
+        # linear map; a training model keeps the winners' ids for the backward, an evaluation model allocates none
+        self._max = FLAGS.aggregator == 'max'
+        if self._max:
+            if not hasattr(A, 'max_product'):
+                raise RuntimeError("--aggregator max runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
+                                   "minibatch adjacency has no maximum kernel")
+            want = bool(getattr(self.model, 'is_training', True))
+            if not concat:
+                out, self._arg = A.max_product(x, want_arg=want)
+                return out
+            out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
+            out[:, :d] = x[:n1]
+            _, self._arg = A.max_product(x, out=out[:, d:], want_arg=want)
+            return out
         if not concat:
             return A.product(x)
         out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
@@ -417,6 +432,11 @@ class PlainAggregator(Layer):
                 return ops.spmm(A.transpose, g[0]), ops.spmm(A2.transpose, g[1])
             return (ops.spmm(A.transpose, g[0][:, d:], add=g[0][:, :d], add_rows=n1),
                     ops.spmm(A2.transpose, g[1][:, d:], add=g[1][:, :d], add_rows=n1))
+        if self._max:
+            # the maximum's gradient goes to each element's winner: one gather over A^T, the self half in its epilogue
+            if not self._concat:
+                return A.transpose.max_backward(g, self._arg)
+            return A.transpose.max_backward(g[:, d:], self._arg, add=g[:, :d], add_rows=A.shape[0])
         if not self._concat:
             return A.transpose.product(g)
         # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep

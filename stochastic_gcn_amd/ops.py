@@ -14,6 +14,8 @@ Reference seams replaced:
   spmm_cs         the same product as spmm for a STATIC graph (column sweep, ColumnSweepCSR)
   moments_add / moments_summary   Stat.add + np.mean / np.std of the kept draws   gcn/stats.py,
                   gcn/train.py:241-276 (running fp64 statistics on the device, stats.DeviceStat)
+  spmax / spmax_bwd   the element-wise neighbour maximum over a CSR pattern and its backward (--aggregator max: GraphSAGE's pooling
+                  aggregator without its MLP; no reference counterpart)
   history_error   how far a stored history is from the exact activations (no reference counterpart; exact_history.py)
 """
 import ctypes as C
@@ -145,10 +147,19 @@ class DevicePlan(object):
         self.ws = None
         self.device = device
 
+    ws_ids = None         # (only spmax allocates it)
+
     def struct(self, d):
         self.ws = _fixup_ws(self.ws, self.nslots, d, self.device)
         return _ffi.Plan(self.seg.data_ptr(), self.nseg, _ptr(self.fix), self.nfix, self.nslots,
                          _ptr(self.ws), 0 if self.ws is None else self.ws.numel())
+
+    def ids(self, d):
+        """The int32 twin of the fix-up workspace (sgcn_spmax_csr_f32 dev_ws_arg: the slots' column ids), same geometry."""
+        need = self.nslots * ((d + 3) // 4 * 4)
+        if need and (self.ws_ids is None or self.ws_ids.numel() < need):
+            self.ws_ids = torch.empty(need, dtype=torch.int32, device=self.device)
+        return self.ws_ids
 
 
 class DeviceCSR(object):
@@ -234,6 +245,80 @@ def spmm(A, B, out=None, gidx=None, rscale=None, cscale=None, beta=0.0, d=None, 
         _ptr(_dev(gidx, torch.int32, "gidx")), _ptr(_dev(rscale, torch.float32, "rscale")),
         _ptr(_dev(cscale, torch.float32, "cscale")), cptr, ldc, float(beta),
         C.byref(plan) if plan is not None else None, _stream()))
+    return out
+
+
+def check_unique_cols(A):
+    """ValueError unless every row of the DeviceCSR ``A`` stores each column id at most once (what spmax's `first maximum`
+    and its backward's `arg == j` mean something for).  A host pass over the pattern, made once per matrix."""
+    if getattr(A, '_unique_cols', False):
+        return
+    col = A.col.cpu().numpy().astype(np.int64)
+    rowptr = (A.host_rowptr if A.host_rowptr is not None else A.rowptr.cpu().numpy()).astype(np.int64)
+    # one key per entry, (row, column) in row-major order: strictly rising as stored when every row is sorted and unique
+    key = np.repeat(np.arange(rowptr.size - 1, dtype=np.int64), np.diff(rowptr)) * max(int(A.shape[1]), 1) + col
+    if key.size > 1 and not np.all(np.diff(key) > 0):
+        key.sort()                                        # (rows stored in another order: look for equal neighbours)
+        if np.any(np.diff(key) == 0):
+            raise ValueError("spmax needs unique column ids within each row: the %d x %d pattern stores a column twice "
+                             "in some row" % A.shape)
+    A._unique_cols = True
+
+
+def spmax(A, x, out=None, want_arg=True, arg=None):
+    """(out, arg): out[i, c] = max over the stored entries j of row i of the DeviceCSR ``A`` of x[j, c], arg[i, c] = the
+    column id of the first maximum in stored order (int32; -1 and +0.0 on an empty row) -- sgcn_spmax_csr_f32.  The stored
+    values are not read.  ``want_arg=False`` (an evaluation): arg is None, nothing is allocated for it; ``arg``: an existing
+    (M, >= d) int32 tensor to store the ids into."""
+    check_unique_cols(A)
+    M, K = A.shape
+    bptr, ldb = _rows2d(x, "x")
+    d = int(x.shape[1])
+    if x.shape[0] < K:
+        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
+    if out is None:
+        out = torch.empty((M, d), dtype=torch.float32, device=x.device)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != M or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
+    ldarg = d
+    if not want_arg:
+        arg = None
+    elif arg is None:
+        arg = torch.empty((M, d), dtype=torch.int32, device=x.device)
+    else:
+        _dev(arg, torch.int32, "arg")
+        if arg.dim() != 2 or arg.shape[0] != M or arg.shape[1] < d or (arg.shape[1] > 1 and arg.stride(1) != 1):
+            raise ValueError("arg has shape %s, need (%d, >=%d) with unit column stride" % (tuple(arg.shape), M, d))
+        ldarg = arg.stride(0) if M > 1 else max(arg.stride(0), arg.shape[1])
+    plan = A.plan.struct(d) if A.plan is not None else None
+    ids = A.plan.ids(d) if A.plan is not None else None
+    check(lib.sgcn_spmax_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, bptr, ldb, cptr, ldc, _ptr(arg), ldarg,
+                                 C.byref(plan) if plan is not None else None, _ptr(ids), _stream()))
+    return out, arg
+
+
+def spmax_bwd(At, g, arg, out=None, add=None, add_rows=0):
+    """out[j, c] = sum over the rows i with arg[i, c] == j of g[i, c] in ascending i (+ add[j] for j < add_rows, in the same
+    launch) -- sgcn_spmax_csr_bwd_f32, a gather over ``At``, the DeviceCSR of the TRANSPOSED pattern (ops.transpose_host:
+    source rows ascending).  No atomics: bitwise reproducible."""
+    K, M = At.shape
+    gptr, ldg = _rows2d(g, "g")
+    d = int(g.shape[1])
+    _dev(arg, torch.int32, "arg")
+    if arg.dim() != 2 or (arg.shape[1] > 1 and arg.stride(1) != 1) or tuple(arg.shape) != (M, d) or g.shape[0] != M:
+        raise ValueError("g and arg must be (%d, d) with unit column stride, got %s and %s" % (M, tuple(g.shape), tuple(arg.shape)))
+    ldarg = arg.stride(0) if M > 1 else max(arg.stride(0), d)
+    if out is None:
+        out = torch.empty((K, d), dtype=torch.float32, device=g.device)
+    optr, ldo = _rows2d(out, "out")
+    if out.shape[0] != K or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), K, d))
+    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
+    plan = At.plan.struct(d) if At.plan is not None else None
+    check(lib.sgcn_spmax_csr_bwd_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, gptr, ldg, arg.data_ptr(), ldarg, optr, ldo,
+                                     aptr, ldadd, int(add_rows) if add is not None else 0,
+                                     C.byref(plan) if plan is not None else None, _stream()))
     return out
 
 
