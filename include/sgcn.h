@@ -300,6 +300,11 @@ int sgcn_lds_profile_buffer(void* dev_buf);
  *   0 = unpaced), cs_slack (columns), cs_noextra (no fifth fp32 accumulator plane), cs_g2_wide (G = 2 plans: force the
  *   64-bit row offsets), cs_last_pct (default 80: clock of a last pass that covers <= 3/4 of a slab, in percent of the
  *   plan's pace; 0 = off) : column-sweep kernels
+ *   cs_deal (default 1), read when a lane-group plan (G = 2 / 4) is BUILT: 1 = virtual rows dealt to the bins by weight and
+ *   by column spread -- among the lightest bins the one whose cumulative column curve the row leaves closest to the clock's
+ *   line -- and a plan of several launch rounds keeps its tiles longest first: fewer pads, a shorter heaviest tile per
+ *   round, the same products bit for bit; 0 = dealt by weight alone (the plan every build before the knob made).  G = 1
+ *   plans are dealt by weight either way.
  *   step_overlap (library default 1; the step program sets it from its flags, 0 unless --agg_overlap or a non-lean mode):
  *   in sgcn_step_run the AUX_* / VR_AGG_PRE ops (and, without --group_dw / --lean_sync, weight-gradient GEMMs and loss
  *   statistics) go to an auxiliary stream

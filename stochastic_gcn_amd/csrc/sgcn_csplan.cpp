@@ -8,6 +8,7 @@
 // stable MERGE of its rows' column-sorted runs (the CSR's rows are sorted -- checked, and sorted into a private copy
 // if they are not), tiles are claimed by the threads a few at a time and written to per-thread arenas, and the export
 // copies them out in tile order.  The plan does not depend on the thread count (tests/test_csplan.py).
+// Lane-group plans deal their rows by weight AND column spread (deal_aware below; sgcn_tune "cs_deal"), serial as well.
 #include "sgcn_host.h"
 #include "../../include/sgcn.h"
 
@@ -24,6 +25,7 @@
 #include <new>
 #include <numeric>
 #include <queue>
+#include <set>
 #include <thread>
 #include <vector>
 
@@ -162,6 +164,67 @@ void deal(const VRow* v, int64_t nv, int64_t vbase, int32_t R, int64_t nbins, in
     }
 }
 
+// ---- column-aware dealing (sgcn_tune "cs_deal" = 1; lane-group plans only) ------------------------------------------
+// The weight of a bin is settled by the LPT dealing; how many PADS its tile gets is settled by how far the sorted column
+// lists of the tile's bins drift apart (gn_schedule lets a bin advance only `align` sweep positions past the slowest), and
+// a paced launch lasts as long as the heaviest tile of its round, pads included.  So the dealing also looks at WHERE a
+// row's nonzeros lie: every bin keeps the curve of its entries over kDealBuckets equal ranges of the sweep's positions
+// (column ids, or their warp table entries -- the coordinates of Ent.pos and of `align`), and a row goes to that one of
+// the kDealCand lightest open bins whose cumulative curve it leaves closest to the diagonal (the clock's line).  Only
+// bins within max(8, nnz / 2) of the lightest are candidates, so the LPT balance survives.  Serial, and a function of
+// the matrix alone.  A plan of several launch rounds then keeps its tiles longest first (build_plan): only the first
+// round lasts as long as the plan's heaviest tile.  Rows stay whole inside one bin and in column order, so every output
+// element sees the fused multiply-adds of the weight-only plan in the same order: the same bits (tests/test_csplan_deal*.py).
+constexpr int kDealBuckets = 64, kDealCand = 32;
+
+struct DealCols {                      // the prepared matrix and the sweep's coordinates
+    const int32_t* rowptr;
+    const int32_t* col;
+    const uint32_t* warp;
+    int32_t wshift;
+    uint64_t scale;                    // 2^32 x kDealBuckets / (positions in the sweep), rounded down
+    inline int bucket(int64_t p) const {            // (no division per nonzero; positions are below 2^28)
+        const uint32_t c = (uint32_t)col[p];
+        return (int)(((uint64_t)(warp ? warp[c >> wshift] : c) * scale) >> 32);
+    }
+};
+
+// assign[bin * R + k] = index into v (or -1)
+void deal_aware(const VRow* v, int64_t nv, int32_t R, int64_t nbins, const DealCols& A, int64_t* assign) {
+    constexpr int NB = kDealBuckets;
+    std::fill(assign, assign + nbins * R, (int64_t)-1);
+    // off[bin][k] = NB x (entries of the bin in buckets <= k) - (k + 1) x (entries of the bin): NB times the distance of
+    // its cumulative curve from the diagonal, exact in integers (no rounding decides a tie), additive over rows
+    std::vector<int64_t> off((size_t)nbins * NB, 0), w((size_t)nbins, 0);
+    std::vector<int32_t> fill((size_t)nbins, 0);
+    std::set<std::pair<int64_t, int64_t>> open;                 // (weight, bin): lightest first, ties -> low bin id
+    for (int64_t t = 0; t < nbins; t++) open.insert(open.end(), {0, t});
+    int64_t h[NB];
+    for (int64_t i = 0; i < nv; i++) {
+        const VRow& x = v[i];
+        std::fill(h, h + NB, 0);
+        for (int64_t p = (int64_t)A.rowptr[x.row] + x.piece; p < A.rowptr[x.row + 1]; p += x.npieces) h[A.bucket(p)]++;
+        for (int64_t k = 0, cum = 0; k < NB; k++) { cum += h[k]; h[k] = cum * NB - (int64_t)x.nnz * (k + 1); }
+        const int64_t wmin = open.begin()->first, tol = std::max<int64_t>(8, x.nnz / 2);
+        int64_t best = -1, best_dev = INT64_MAX;
+        int seen = 0;
+        for (auto it = open.begin(); it != open.end() && seen < kDealCand && it->first <= wmin + tol; ++it, ++seen) {
+            const int64_t* ob = off.data() + (size_t)it->second * NB;
+            int64_t dev = 0;
+            // (every eighth bucket first: a candidate that is already no better than the best so far is dropped early)
+            for (int k0 = 0; k0 < 8 && dev < best_dev; k0++)
+                for (int k = 7 - k0; k < NB; k += 8) dev = std::max<int64_t>(dev, std::llabs(ob[k] + h[k]));
+            if (dev < best_dev) { best_dev = dev; best = it->second; }  // ties: the lighter bin, then the lower id (set order)
+        }
+        open.erase({w[(size_t)best], best});
+        assign[best * R + fill[(size_t)best]++] = i;
+        int64_t* ob = off.data() + (size_t)best * NB;
+        for (int k = 0; k < NB; k++) ob[k] += h[k];
+        w[(size_t)best] += x.nnz;
+        if (fill[(size_t)best] < R) open.insert({w[(size_t)best], best});
+    }
+}
+
 struct Layout {
     int32_t R = 16;                   // virtual rows per bin
     int32_t NG = 1;                   // bins per tile (lane groups per wavefront)
@@ -193,7 +256,8 @@ void layout_g1(const int32_t* rowptr, int32_t M, int32_t R, int32_t T, const int
 
 // NG = 2 / 4 lane groups: ungrouped, the tile count rounded up to whole launches of `round_tiles` resident waves
 constexpr int kG2R = 16;
-void layout_gn(const int32_t* rowptr, int32_t M, int32_t T, int32_t round_tiles, int NG, Layout& L) {
+// `cols`: the prepared matrix with the sweep's coordinates for the column-aware dealing, null for the dealing by weight alone
+void layout_gn(const int32_t* rowptr, int32_t M, int32_t T, int32_t round_tiles, int NG, const DealCols* cols, Layout& L) {
     std::vector<int32_t> rows((size_t)M);
     std::iota(rows.begin(), rows.end(), 0);
     make_vrows(rowptr, rows.data(), M, T, L.v);
@@ -203,7 +267,8 @@ void layout_gn(const int32_t* rowptr, int32_t M, int32_t T, int32_t round_tiles,
         nt = (nt + round_tiles - 1) / round_tiles * round_tiles;
     L.R = kG2R; L.NG = NG; L.ntiles = nt;
     L.assign.resize((size_t)nt * NG * kG2R);
-    deal(L.v.data(), nv, 0, kG2R, nt * NG, L.assign.data());
+    if (!cols) { deal(L.v.data(), nv, 0, kG2R, nt * NG, L.assign.data()); return; }
+    deal_aware(L.v.data(), nv, kG2R, nt * NG, *cols, L.assign.data());
 }
 
 // ---- the matrix: rows column-sorted (or a sorted private copy) ------------------------------------------------
@@ -415,8 +480,23 @@ int build_plan(const int32_t* rowptr, const int32_t* col, const float* val, int3
         if (rc == 2) return sgcn::fail(SGCN_ERR_INVALID, "csplan_build: out of host memory");
     }
     Layout L;
+    const bool aware = G != 1 && M > 0 && sgcn_tune_get("cs_deal") > 0;       // (read when the plan is built)
     if (G == 1) layout_g1(rowptr, M, R, T, row_group, L);
-    else layout_gn(rowptr, M, T, round_tiles, G, L);
+    else if (!aware) layout_gn(rowptr, M, T, round_tiles, G, nullptr, L);
+    else {
+        DealCols dc{A.rowptr, A.col, warp, wshift, 0};
+        std::vector<int64_t> top((size_t)nthr, 0);                     // the largest sweep position, for the histograms' buckets
+        if (!parallel_chunks((int64_t)rowptr[M] - rowptr[0], 1 << 18, nthr, [&](int64_t b, int64_t e, int tid) {
+                int64_t m = top[(size_t)tid];
+                for (int64_t p = rowptr[0] + b; p < rowptr[0] + e; p++) {
+                    const uint32_t c = (uint32_t)A.col[p];
+                    m = std::max<int64_t>(m, warp ? warp[c >> wshift] : c);
+                }
+                top[(size_t)tid] = m;
+            })) return sgcn::fail(SGCN_ERR_INVALID, "csplan_build: out of host memory");
+        dc.scale = ((uint64_t)kDealBuckets << 32) / (uint64_t)(*std::max_element(top.begin(), top.end()) + 1);
+        layout_gn(rowptr, M, T, round_tiles, G, &dc, L);
+    }
     const int64_t nt = L.ntiles;
     const int32_t RR = L.R * L.NG;                                   // row slots per tile
     B->ntiles = nt;
@@ -499,6 +579,21 @@ int build_plan(const int32_t* rowptr, const int32_t* col, const float* val, int3
         }
     });
     if (!ok) return sgcn::fail(SGCN_ERR_INVALID, "csplan_build: out of host memory");
+    if (aware && round_tiles > 0 && nt > round_tiles) {
+        // more than one launch round: the longest tiles first (ties in tile order), so that only the first round lasts as
+        // long as the plan's heaviest tile and every later one as long as the heaviest of what is left
+        std::vector<int64_t> perm((size_t)nt);
+        std::iota(perm.begin(), perm.end(), 0);
+        std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return tile_len[(size_t)a] > tile_len[(size_t)b]; });
+        std::vector<int64_t> len(tile_len), off(B->tile_off);
+        std::vector<int32_t> tid(B->tile_tid), rws(B->tile_rows), sls(B->tile_slots);
+        for (int64_t t = 0; t < nt; t++) {
+            const size_t s = (size_t)perm[(size_t)t];
+            tile_len[(size_t)t] = len[s]; B->tile_off[(size_t)t] = off[s]; B->tile_tid[(size_t)t] = tid[s];
+            std::copy(rws.begin() + s * RR, rws.begin() + (s + 1) * RR, B->tile_rows.begin() + t * RR);
+            std::copy(sls.begin() + s * RR, sls.begin() + (s + 1) * RR, B->tile_slots.begin() + t * RR);
+        }
+    }
     for (int64_t t = 0; t < nt; t++) B->tile_ptr[(size_t)t + 1] = B->tile_ptr[(size_t)t] + tile_len[(size_t)t];
     B->nentries = B->tile_ptr[(size_t)nt];
     return SGCN_OK;

@@ -1188,7 +1188,8 @@ class ColumnSweepCSR(object):
         if path is None:
             return cls(a, device, G=G), False
         # the identity of the matrix AND of the build parameters the plan depends on (tiles per launch round)
-        key = "%s:r%d:Tauto:aauto:w1" % (cls.matrix_key(a), _cs_round())   # cached() builds with the default T / align
+        # (cached() builds with the default T / align; d: how the rows were dealt to the bins, sgcn_tune "cs_deal")
+        key = "%s:r%d:Tauto:aauto:w1:d%d" % (cls.matrix_key(a), _cs_round(), _ffi.lib.sgcn_tune_get(b"cs_deal"))
         hit = cls.load(path, device, key, g=G)
         if hit is not None:
             return hit, True
