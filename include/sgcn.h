@@ -55,7 +55,8 @@ const char* sgcn_last_error(void);
  *       static-graph products -- sgcn_spmm_csr_b16 / _csr_add_b16 / sgcn_spmm_cs_b16 / sgcn_spmm_cs_variant_b16; the staleness
  *       of a history -- sgcn_hist_error_f32 / _h16 / _ws_doubles; the value array of a static plan re-drawn under an
  *       edge mask -- sgcn_edge_revalue_f32; the element-wise neighbour maximum over a CSR pattern and its backward --
- *       sgcn_spmax_csr_f32 / sgcn_spmax_csr_bwd_f32) */
+ *       sgcn_spmax_csr_f32 / sgcn_spmax_csr_bwd_f32; softmax dot-product attention over a CSR pattern and its backward --
+ *       sgcn_spattn_csr_f32 / sgcn_spattn_csr_bwd_q_f32 / sgcn_spattn_csr_bwd_kv_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -483,6 +484,63 @@ int sgcn_spmax_csr_bwd_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t_row
                            float* dev_dB, int64_t lddb,
                            const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
                            const sgcn_plan_t* t_plan /* nullable */, void* stream);
+
+/* ---- softmax dot-product attention over a CSR pattern (--aggregator attn; additive, still v16) ---------------------------
+ * Parameter-free attention with Q = K = V for the full-graph modes; the dense layers around the aggregation are the
+ * projections.  No reference counterpart in gcn/.
+ *
+ * Forward.  The CSR pattern (dev_rowptr, dev_col) has M rows, K columns and UNIQUE column ids per row; stored VALUES are
+ * not read.  With Q a dense M x d and B a dense K x d fp32 table (Q may alias B) and a finite scalar `scale`:
+ *     s_ij   = scale * <Q[i, :], B[j, :]>               for j stored in row i
+ *     lse_i  = log sum_j exp(s_ij)                      computed as m_i + log l_i, m_i = max_j s_ij, l_i = sum_j exp(s_ij - m_i)
+ *     C[i,:] = acc_i / l_i,  acc_i = sum_j exp(s_ij - m_i) * B[j, :]
+ * The final normalisation is a TRUE DIVISION, acc / l, correctly rounded per element (not a multiplication by 1 / l).
+ * exp is expf; lse_i is m_i + log l_i evaluated in fp64 and rounded once.  An empty row gives C = +0.0 and lse = -inf.  Finite inputs are the caller's promise.  The
+ * kernel is a fused pass: every gathered row of B is used twice, for its score and for the weighted sum, with an online
+ * softmax per row segment (acc and l are rescaled by exp(m_old - m_new) when the maximum rises); nothing nnz-sized is
+ * written.  dev_lse (M floats) is nullable: an evaluation needs no backward.
+ *
+ * Width.  A score needs the whole row, so there are no feature slabs: one group of lanes holds all d columns, at most 256
+ * vectors of VW elements, VW in {1, 2, 4} the widest vector every operand's pointer and pitch allow (the row kernels'
+ * rule: 16-byte aligned bases and pitches that are multiples of 4 give VW = 4, 8-byte / multiples of 2 give VW = 2).
+ * d <= 256 * VW; any other d is SGCN_ERR_INVALID, the message naming the limit, before any HIP call.
+ *
+ * Plan.  plan is nullable (then one lane group per whole row).  A row the plan splits writes, per segment, its partial
+ * (acc, m, l) to the segment's workspace slot in plan->dev_ws.  SLOT GEOMETRY OF THE FORWARD: ldw = 4*ceil(d/4) + 4 floats
+ * per slot -- acc on floats [0, d), m at float 4*ceil(d/4), l at 4*ceil(d/4) + 1, the last two unused -- so ws_elems >=
+ * nslots * (4*ceil(d/4) + 4).  The ordered fix-up takes the largest m of the row's slots, then adds l_q * exp(m_q - m) and
+ * acc_q * exp(m_q - m) in slot order and divides.  The two backward launches use the row SpMM's geometry, ldw = 4*ceil(d/4).
+ *
+ * Backward, two launches, for G = dL/dC (M x d), the saved C and lse.  With delta_i = <G[i,:], C[i,:]>,
+ * p_ij = exp(s_ij - lse_i) and e_ij = p_ij * (<G[i,:], B[j,:]> - delta_i), both recomputed per entry from the per-row
+ * scalars (nothing nnz-sized is stored, no atomics: the results are bitwise reproducible):
+ *   _bwd_q  over the pattern:            delta[i] (M floats, written) and dQ[i,:] = scale * sum_j e_ij * B[j,:]
+ *   _bwd_kv over the TRANSPOSED pattern: dB[j,:] = sum_i ( p_ij * G[i,:] + scale * e_ij * Q[i,:] ), source rows i ascending
+ *           (dev_t_rowptr, dev_t_row: K rows over M columns, as sgcn_csr_transpose_host produces them); it gathers two
+ *           rows per entry, Q[i] and G[i], and reads lse[i] and the delta[i] the first launch wrote.
+ * Each takes an epilogue addend: out[r, :] += add[r, :] for r < add_rows, as sgcn_spmm_csr_add_f32.  With Q = B = x the
+ * second launch given the first one's result as its addend yields dX = dB + [dQ + g_self ; 0] without a further pass.
+ * A split row's partial sums go to its slots and the ordered fix-up adds them in slot order, then applies the epilogue.
+ *
+ * All three validate before any HIP call: a null operand, d <= 0, a pitch below d, a non-finite scale, a d over the width
+ * limit, a plan with split rows but without dev_fix / dev_ws, or a workspace smaller than nslots x ldw give
+ * SGCN_ERR_INVALID with nothing written. */
+int sgcn_spattn_csr_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d,
+                        const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb, float scale,
+                        float* dev_C, int64_t ldc, float* dev_lse /* nullable */,
+                        const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spattn_csr_bwd_q_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d,
+                              const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb, float scale,
+                              const float* dev_G, int64_t ldg, const float* dev_C, int64_t ldc, const float* dev_lse,
+                              float* dev_delta, float* dev_dQ, int64_t lddq,
+                              const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                              const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spattn_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t_row, int32_t K, int32_t M, int32_t d,
+                               const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb, float scale,
+                               const float* dev_G, int64_t ldg, const float* dev_lse, const float* dev_delta,
+                               float* dev_dB, int64_t lddb,
+                               const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                               const sgcn_plan_t* t_plan /* nullable */, void* stream);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-

@@ -1,0 +1,646 @@
+// Softmax dot-product attention over a CSR pattern for gfx950 (MI355X), and its backward (--aggregator attn):
+//   forward   s_ij = scale * <Q[i], B[j]>,  lse_i = log sum_j exp(s_ij),  p_ij = exp(s_ij - lse_i),  C[i] = sum_j p_ij B[j]
+//   backward  delta_i = <G[i], C[i]>,  e_ij = p_ij (<G[i], B[j]> - delta_i)
+//             dQ[i] = scale * sum_j e_ij B[j]                          (gather over P, row i)
+//             dB[j] = sum_i ( p_ij G[i] + scale e_ij Q[i] )            (gather over P^T, row j, source rows i ascending)
+// The sums run over the stored entries of row i; stored values are never read.  Nothing nnz-sized is written in either
+// direction: the forward keeps a running (m, l, acc) per row segment (online softmax: acc and l are rescaled when the
+// maximum m rises) and uses every gathered row twice, for its score and for the weighted sum; the backward recomputes
+// p_ij and e_ij per entry from the per-row scalars lse_i and delta_i.  No atomics: dB is a gather over the transposed
+// pattern, split rows meet in an ordered fix-up, so every result is bitwise reproducible.
+//
+// Shape of the kernels: the lane geometry of sgcn_spmm.hip / sgcn_spmax.hip -- a group of G lanes (8/16/32/64 from the
+// row width) owns one row segment of the host plan, lane l owns vectors l, l + G, .. of VW elements, the segment's column
+// ids are read G at a time and broadcast, U entries' loads are in flight before the first use.  A score needs the WHOLE
+// row, so there are no feature slabs: one group holds all d columns, NV <= 4 vectors per lane, d <= 256 * VW.  The dot
+// products reduce across the group's lanes with __shfl_xor (no LDS memory); the backward's two dot products per entry
+// travel through the reduction together (group_sum2: log2 G + 2 moves for both instead of 2 log2 G).
+//
+// A chunk of U entries is always processed whole: past the end of the column block the last entry is loaded again and
+// its weight forced to exactly 0 (score -inf), which adds +-0 to the sums -- one code path, no remainder loop.
+#include <cmath>
+#include "sgcn_dev.h"
+
+namespace sgcn {
+
+int group_lanes(int nvec);   // sgcn_spmm.hip: lanes per row group for `nvec` vectors
+
+namespace {
+
+constexpr int kMaxVec = 256;   // vectors per row: 64 lanes x NV <= 4
+
+struct AttnArgs {
+    const int32_t* rowptr;
+    const int32_t* col;      // forward / bwd_q: column ids; bwd_kv: the source rows of the transposed pattern
+    const sgcn_seg_t* seg;   // nullable: implicit one segment per row
+    int64_t nseg;
+    const float* own;        // the table the segment's own row comes from: Q (forward, bwd_q), B (bwd_kv)
+    int64_t ldown;
+    const float* gat;        // the gathered table: B (forward, bwd_q), Q (bwd_kv)
+    int64_t ldgat;
+    const float* G;          // bwd_q: the own row's gradient; bwd_kv: gathered beside `gat`
+    int64_t ldg;
+    const float* Cf;         // bwd_q: the forward's output
+    int64_t ldcf;
+    const float* lse;        // backward
+    const float* delta;      // bwd_kv
+    float* delta_out;        // bwd_q
+    float* lse_out;          // forward, nullable
+    float* out;              // C / dQ / dB
+    int64_t ldo;
+    float scale;
+    int32_t d;
+    int32_t nvec;            // ceil(d / VW)
+    int32_t ragged;          // d % VW != 0: the last vector over-reads pad elements, which are zeroed after the load
+    float* ws;
+    int64_t ldw;
+    const float* add;        // backward: out[row] += add[row] for row < add_rows
+    int64_t ldadd;
+    int32_t add_rows;
+};
+
+template <int G>
+__device__ __forceinline__ bool my_segment(const AttnArgs& a, int& row, int& start, int& end, int& slot) {
+    constexpr int GPB = kBlock / G;
+    const int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / G;
+    if (s >= a.nseg) return false;
+    if (a.seg) {
+        const sgcn_seg_t sg = a.seg[s];
+        row = sg.row; start = sg.start; end = sg.end; slot = sg.slot;
+    } else {
+        row = (int)s; start = a.rowptr[s]; end = a.rowptr[s + 1]; slot = -1;
+    }
+    row = uniform_i<G>(row); start = uniform_i<G>(start);
+    end = uniform_i<G>(end); slot = uniform_i<G>(slot);
+    return true;
+}
+
+// zero the elements e >= cnt: the pad a ragged last vector over-read (cnt < VW), a lane past the row width (cnt == 0)
+template <int VW>
+__device__ __forceinline__ void keep_head(typename Vec<VW>::type& v, int cnt) {
+    if constexpr (VW == 1) v = cnt > 0 ? v : 0.f;
+    else {
+#pragma unroll
+        for (int e = 0; e < VW; e++) v[e] = e < cnt ? v[e] : 0.f;
+    }
+}
+template <int VW>
+__device__ __forceinline__ float vdot(const typename Vec<VW>::type& x, const typename Vec<VW>::type& y, float acc) {
+    if constexpr (VW == 1) return __builtin_fmaf(x, y, acc);
+    else {
+#pragma unroll
+        for (int e = 0; e < VW; e++) acc = __builtin_fmaf(x[e], y[e], acc);
+        return acc;
+    }
+}
+template <int VW>
+__device__ __forceinline__ void vstore_n(float* p, typename Vec<VW>::type v, int cnt) {
+    if (cnt >= VW) vstore<VW>(p, v);
+    else vstore_head<VW>(p, v, cnt);
+}
+
+// lse = m + log l, once per row: the logarithm and the sum in fp64, rounded once (logf alone was measured 2 ulp off at
+// l = 300, and the backward's every weight exp(s - lse) inherits lse's error)
+__device__ __forceinline__ float lse_of(float m, float l) { return (float)((double)m + log((double)l)); }
+
+// the sum of U values over the group's G lanes, every lane getting every total; the U chains are independent
+template <int G, int U>
+__device__ __forceinline__ void group_sum(float (&s)[U]) {
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1)
+#pragma unroll
+        for (int u = 0; u < U; u++) s[u] += __shfl_xor(s[u], o, G);
+}
+// two sums per entry through ONE tree: after the first exchange even lanes carry s and odd lanes t, the steps 2 .. G/2
+// reduce both at once, and the last two moves hand every lane both totals
+template <int G, int U>
+__device__ __forceinline__ void group_sum2(float (&s)[U], float (&t)[U], int lig) {
+    const bool odd = lig & 1;
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const float keep = odd ? t[u] : s[u], send = odd ? s[u] : t[u];
+        v[u] = keep + __shfl_xor(send, 1, G);
+    }
+#pragma unroll
+    for (int o = 2; o < G; o <<= 1)
+#pragma unroll
+        for (int u = 0; u < U; u++) v[u] += __shfl_xor(v[u], o, G);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        s[u] = __shfl(v[u], lig & ~1, G);
+        t[u] = __shfl(v[u], lig | 1, G);
+    }
+}
+
+// what a lane owns of a row: NV vectors, their byte offsets (lanes past the row width re-read the last valid vector
+// instead of branching around the load) and how many of their elements exist
+template <int G, int NV, int VW>
+struct Lane {
+    uint32_t off[NV];
+    int cnt[NV];     // 0: no such vector; VW: whole; between: the ragged last one
+    int vi[NV];
+    __device__ __forceinline__ Lane(const AttnArgs& a, int lig) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            vi[k] = lig + k * G;
+            cnt[k] = vi[k] < a.nvec ? min(VW, a.d - vi[k] * VW) : 0;
+            off[k] = (uint32_t)min(vi[k], a.nvec - 1) * (uint32_t)(VW * sizeof(float));
+        }
+    }
+    // a row of the segment's own: loaded once, pads and absent vectors zeroed -- a zero there keeps the (finite)
+    // gathered element it meets out of every dot product
+    __device__ __forceinline__ void own_row(const float* base, int64_t ld, int row, typename Vec<VW>::type (&v)[NV]) const {
+        const char* src = reinterpret_cast<const char*>(base) + (int64_t)row * ld * (int64_t)sizeof(float);
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            v[k] = vload<VW>(reinterpret_cast<const float*>(src + off[k]));
+            keep_head<VW>(v[k], cnt[k]);
+        }
+    }
+};
+
+template <int NV>
+struct Unroll { static constexpr int fwd = 4, bwd_q = NV >= 3 ? 2 : 4, bwd_kv = NV >= 2 ? 2 : 4; };
+
+// ---- forward ------------------------------------------------------------------------------------------------------------
+template <int G, int NV, int VW>
+__global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
+    typedef typename Vec<VW>::type VT;
+    constexpr int U = Unroll<NV>::fwd;
+    const int lig = threadIdx.x & (G - 1);
+    int row, start, end, slot;
+    if (!my_segment<G>(a, row, start, end, slot)) return;
+    const Lane<G, NV, VW> L(a, lig);
+
+    VT q[NV], acc[NV];
+    L.own_row(a.own, a.ldown, row, q);
+#pragma unroll
+    for (int k = 0; k < NV; k++) acc[k] = vzero<VW>();
+    float m = -INFINITY, l = 0.f;
+    const char* Bb = reinterpret_cast<const char*>(a.gat);
+    const int64_t ldb_bytes = a.ldgat * (int64_t)sizeof(float);
+
+    for (int p0 = start; p0 < end; p0 += G) {
+        const int n = min(G, end - p0);
+        int mycol = 0;
+        if (lig < n) mycol = a.col[p0 + lig];
+        for (int j = 0; j < n; j += U) {
+            VT b[U][NV];
+            float s[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int c = bcast_i<G>(mycol, min(j + u, n - 1));
+                const char* src = Bb + (int64_t)c * ldb_bytes;   // G == 64: scalar base
+#pragma unroll
+                for (int k = 0; k < NV; k++) b[u][k] = vload<VW>(reinterpret_cast<const float*>(src + L.off[k]));
+            }
+            if (a.ragged) {
+#pragma unroll
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int k = 0; k < NV; k++) keep_head<VW>(b[u][k], L.cnt[k]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                s[u] = 0.f;
+#pragma unroll
+                for (int k = 0; k < NV; k++) s[u] = vdot<VW>(q[k], b[u][k], s[u]);
+            }
+            group_sum<G, U>(s);
+            float mn = m;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                s[u] = j + u < n ? s[u] * a.scale : -INFINITY;
+                mn = fmaxf(mn, s[u]);
+            }
+            if (mn > m) {                      // the maximum rises: what was summed so far shrinks by exp(m - mn)
+                const float alpha = expf(m - mn);
+                l *= alpha;
+#pragma unroll
+                for (int k = 0; k < NV; k++) acc[k] *= alpha;
+                m = mn;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const float p = expf(s[u] - m);
+                l += p;
+#pragma unroll
+                for (int k = 0; k < NV; k++) acc[k] = vfma<VW>(p, b[u][k], acc[k]);
+            }
+        }
+    }
+
+    if (slot < 0) {
+        const bool empty = start >= end;
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            if (L.cnt[k]) {
+                VT r = vzero<VW>();
+                if (!empty) r = acc[k] / l;
+                vstore_n<VW>(a.out + (int64_t)row * a.ldo + (int64_t)L.vi[k] * VW, r, L.cnt[k]);
+            }
+        if (a.lse_out && lig == 0) a.lse_out[row] = empty ? -INFINITY : lse_of(m, l);
+    } else {
+        float* w = a.ws + (int64_t)slot * a.ldw;
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            if (L.cnt[k]) vstore<VW>(w + (int64_t)L.vi[k] * VW, acc[k]);
+        if (lig == 0) { w[a.ldw - 4] = m; w[a.ldw - 3] = l; }
+    }
+}
+
+// A split row's slots: the largest m first, then l and acc added in slot order, each slot scaled by exp(m_q - m).
+template <int VW>
+__global__ __launch_bounds__(kBlock) void spattn_fix_kernel(AttnArgs a, const sgcn_fix_t* fix, int64_t nfix) {
+    typedef typename Vec<VW>::type VT;
+    const int64_t f = blockIdx.x;
+    if (f >= nfix) return;
+    const sgcn_fix_t fx = fix[f];
+    const int vi = threadIdx.x;
+    if (vi >= a.nvec) return;
+    const float* w = a.ws + (int64_t)fx.first_slot * a.ldw;
+    float m = -INFINITY;
+    for (int q = 0; q < fx.nslots; q++) m = fmaxf(m, w[(int64_t)q * a.ldw + a.ldw - 4]);
+    float l = 0.f;
+    VT acc = vzero<VW>();
+    for (int q = 0; q < fx.nslots; q++) {
+        const float* wq = w + (int64_t)q * a.ldw;
+        const float lq = wq[a.ldw - 3];
+        if (lq > 0.f) {                        // (a segment always holds an entry; the guard keeps -inf - -inf out)
+            const float sc = expf(wq[a.ldw - 4] - m);
+            l = __builtin_fmaf(lq, sc, l);
+            acc = vfma<VW>(sc, vload<VW>(wq + (int64_t)vi * VW), acc);
+        }
+    }
+    VT r = vzero<VW>();
+    if (l > 0.f) r = acc / l;
+    vstore_n<VW>(a.out + (int64_t)fx.row * a.ldo + (int64_t)vi * VW, r, min(VW, a.d - vi * VW));
+    if (a.lse_out && vi == 0) a.lse_out[fx.row] = l > 0.f ? lse_of(m, l) : -INFINITY;
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------------
+// r = mul * r (+ add[row] for row < add_rows), the first `cnt` elements stored
+template <int VW>
+__device__ __forceinline__ void bwd_store(const AttnArgs& a, int row, int vi, typename Vec<VW>::type r, float mul) {
+    const int left = a.d - vi * VW;   // > 0 by construction
+    r *= mul;
+    if (a.add && row < a.add_rows) {
+        const float* ad = a.add + (int64_t)row * a.ldadd + (int64_t)vi * VW;
+        if (left >= VW) r += vload<VW>(ad);
+        else {
+#pragma unroll
+            for (int e = 0; e < VW; e++)
+                if (e < left) {
+                    if constexpr (VW == 1) r += ad[0]; else r[e] += ad[e];
+                }
+        }
+    }
+    vstore_n<VW>(a.out + (int64_t)row * a.ldo + (int64_t)vi * VW, r, left);
+}
+
+// over P: delta_i and dQ[i] = scale * sum_j e_ij B[j]
+template <int G, int NV, int VW>
+__global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
+    typedef typename Vec<VW>::type VT;
+    constexpr int U = Unroll<NV>::bwd_q;
+    const int lig = threadIdx.x & (G - 1);
+    int row, start, end, slot;
+    if (!my_segment<G>(a, row, start, end, slot)) return;
+    const Lane<G, NV, VW> L(a, lig);
+
+    VT q[NV], g[NV], acc[NV];
+    L.own_row(a.own, a.ldown, row, q);
+    L.own_row(a.G, a.ldg, row, g);
+    float delta;
+    {
+        VT c[NV];
+        L.own_row(a.Cf, a.ldcf, row, c);
+        // through the tree and the per-lane order of the loop's t = <G[i], B[j]>: where C[i] holds the bits of one B[j] (a
+        // softmax that has saturated on one neighbour), t - delta is exactly 0 for it, whatever the sums round to
+        float dd[1] = {0.f}, none[1] = {0.f};
+#pragma unroll
+        for (int k = 0; k < NV; k++) dd[0] = vdot<VW>(g[k], c[k], dd[0]);
+        group_sum2<G, 1>(none, dd, lig);
+        delta = dd[0];
+    }
+    if (lig == 0 && start == a.rowptr[row]) a.delta_out[row] = delta;   // the row's first segment
+    const float lse = a.lse[row];
+#pragma unroll
+    for (int k = 0; k < NV; k++) acc[k] = vzero<VW>();
+    const char* Bb = reinterpret_cast<const char*>(a.gat);
+    const int64_t ldb_bytes = a.ldgat * (int64_t)sizeof(float);
+
+    for (int p0 = start; p0 < end; p0 += G) {
+        const int n = min(G, end - p0);
+        int mycol = 0;
+        if (lig < n) mycol = a.col[p0 + lig];
+        for (int j = 0; j < n; j += U) {
+            VT b[U][NV];
+            float s[U], t[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int c = bcast_i<G>(mycol, min(j + u, n - 1));
+                const char* src = Bb + (int64_t)c * ldb_bytes;
+#pragma unroll
+                for (int k = 0; k < NV; k++) b[u][k] = vload<VW>(reinterpret_cast<const float*>(src + L.off[k]));
+            }
+            if (a.ragged) {
+#pragma unroll
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int k = 0; k < NV; k++) keep_head<VW>(b[u][k], L.cnt[k]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                s[u] = 0.f; t[u] = 0.f;
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    s[u] = vdot<VW>(q[k], b[u][k], s[u]);
+                    t[u] = vdot<VW>(g[k], b[u][k], t[u]);
+                }
+            }
+            group_sum2<G, U>(s, t, lig);
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const float p = j + u < n ? expf(s[u] * a.scale - lse) : 0.f;
+                const float e = p * (t[u] - delta);
+#pragma unroll
+                for (int k = 0; k < NV; k++) acc[k] = vfma<VW>(e, b[u][k], acc[k]);
+            }
+        }
+    }
+
+    if (slot < 0) {
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            if (L.cnt[k]) bwd_store<VW>(a, row, L.vi[k], acc[k], a.scale);
+    } else {
+        float* w = a.ws + (int64_t)slot * a.ldw;
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            if (L.cnt[k]) vstore<VW>(w + (int64_t)L.vi[k] * VW, acc[k]);
+    }
+}
+
+// over P^T: dB[j] = sum_i ( p_ij G[i] + scale e_ij Q[i] ), two gathered rows per entry
+template <int G, int NV, int VW>
+__global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
+    typedef typename Vec<VW>::type VT;
+    constexpr int U = Unroll<NV>::bwd_kv;
+    const int lig = threadIdx.x & (G - 1);
+    int row, start, end, slot;
+    if (!my_segment<G>(a, row, start, end, slot)) return;
+    const Lane<G, NV, VW> L(a, lig);
+
+    VT b[NV], acc[NV];
+    L.own_row(a.own, a.ldown, row, b);
+#pragma unroll
+    for (int k = 0; k < NV; k++) acc[k] = vzero<VW>();
+    const char* Qb = reinterpret_cast<const char*>(a.gat);
+    const char* Gb = reinterpret_cast<const char*>(a.G);
+    const int64_t ldq_bytes = a.ldgat * (int64_t)sizeof(float), ldg_bytes = a.ldg * (int64_t)sizeof(float);
+
+    for (int p0 = start; p0 < end; p0 += G) {
+        const int n = min(G, end - p0);
+        int myrow = 0;
+        if (lig < n) myrow = a.col[p0 + lig];
+        for (int j = 0; j < n; j += U) {
+            VT qi[U][NV], gi[U][NV];
+            float s[U], t[U], lse[U], delta[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int i = bcast_i<G>(myrow, min(j + u, n - 1));
+                const char* qs = Qb + (int64_t)i * ldq_bytes;        // G == 64: scalar bases
+                const char* gs = Gb + (int64_t)i * ldg_bytes;
+                lse[u] = a.lse[i];
+                delta[u] = a.delta[i];
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    qi[u][k] = vload<VW>(reinterpret_cast<const float*>(qs + L.off[k]));
+                    gi[u][k] = vload<VW>(reinterpret_cast<const float*>(gs + L.off[k]));
+                }
+            }
+            if (a.ragged) {
+#pragma unroll
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int k = 0; k < NV; k++) {
+                        keep_head<VW>(qi[u][k], L.cnt[k]);
+                        keep_head<VW>(gi[u][k], L.cnt[k]);
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                s[u] = 0.f; t[u] = 0.f;
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    s[u] = vdot<VW>(qi[u][k], b[k], s[u]);
+                    t[u] = vdot<VW>(gi[u][k], b[k], t[u]);
+                }
+            }
+            group_sum2<G, U>(s, t, lig);
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const float p = j + u < n ? expf(s[u] * a.scale - lse[u]) : 0.f;
+                const float es = a.scale * (p * (t[u] - delta[u]));
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    acc[k] = vfma<VW>(p, gi[u][k], acc[k]);
+                    acc[k] = vfma<VW>(es, qi[u][k], acc[k]);
+                }
+            }
+        }
+    }
+
+    if (slot < 0) {
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            if (L.cnt[k]) bwd_store<VW>(a, row, L.vi[k], acc[k], 1.f);
+    } else {
+        float* w = a.ws + (int64_t)slot * a.ldw;
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            if (L.cnt[k]) vstore<VW>(w + (int64_t)L.vi[k] * VW, acc[k]);
+    }
+}
+
+// Ordered sum of the workspace slots of every split row, then the direct rows' epilogue (the scheme of spmm_fix_kernel).
+template <int VW>
+__global__ __launch_bounds__(kBlock) void spattn_bwd_fix_kernel(AttnArgs a, const sgcn_fix_t* fix, int64_t nfix, float mul) {
+    typedef typename Vec<VW>::type VT;
+    const int64_t f = blockIdx.x;
+    if (f >= nfix) return;
+    const sgcn_fix_t fx = fix[f];
+    const int vi = threadIdx.x;
+    if (vi >= a.nvec) return;
+    const float* w = a.ws + (int64_t)fx.first_slot * a.ldw + (int64_t)vi * VW;
+    VT acc = vzero<VW>();
+    for (int q = 0; q < fx.nslots; q++) acc += vload<VW>(w + (int64_t)q * a.ldw);
+    bwd_store<VW>(a, fx.row, vi, acc, mul);
+}
+
+enum Kind { FWD, BWD_Q, BWD_KV };
+
+template <int KIND, int G, int NV, int VW>
+void launch_seg(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
+    if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+    else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+}
+
+template <int KIND, int VW>
+bool dispatch_gnv(int G, int NV, const AttnArgs& a, int64_t nblocks, hipStream_t st) {
+    switch (G) {
+        case 8: launch_seg<KIND, 8, 1, VW>(a, nblocks, st); return true;
+        case 16: launch_seg<KIND, 16, 1, VW>(a, nblocks, st); return true;
+        case 32: launch_seg<KIND, 32, 1, VW>(a, nblocks, st); return true;
+        case 64:
+            switch (NV) {
+                case 1: launch_seg<KIND, 64, 1, VW>(a, nblocks, st); return true;
+                case 2: launch_seg<KIND, 64, 2, VW>(a, nblocks, st); return true;
+                case 3: launch_seg<KIND, 64, 3, VW>(a, nblocks, st); return true;
+                case 4: launch_seg<KIND, 64, 4, VW>(a, nblocks, st); return true;
+            }
+    }
+    return false;
+}
+
+// the width one group can hold at vector width vw; SGCN_ERR_INVALID beyond it, before any HIP call
+int width_ok(const char* who, int32_t d, int vw) {
+    SGCN_REQUIRE(((int64_t)d + vw - 1) / vw <= kMaxVec,
+                 "%s: d = %d is over the limit of %d columns at vector width %d (d <= 256 * VW; VW = 4 needs 16-byte aligned "
+                 "rows of every operand, VW = 2 8-byte aligned ones)", who, d, kMaxVec * vw, vw);
+    return SGCN_OK;
+}
+
+template <int KIND>
+int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, hipStream_t st) {
+    a.nseg = nrows;
+    if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
+    a.nvec = (a.d + vw - 1) / vw;
+    a.ragged = a.d % vw != 0;
+    const int G = group_lanes(a.nvec);
+    const int NV = G == 64 ? (a.nvec + 63) / 64 : 1;
+    const int64_t nblocks = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
+    SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
+
+    bool ok = false;
+    if (vw == 4) ok = dispatch_gnv<KIND, 4>(G, NV, a, nblocks, st);
+    else if (vw == 2) ok = dispatch_gnv<KIND, 2>(G, NV, a, nblocks, st);
+    else ok = dispatch_gnv<KIND, 1>(G, NV, a, nblocks, st);
+    SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
+    SGCN_HIP_TRY(hipGetLastError());
+
+    if (plan && plan->nfix > 0) {
+        SGCN_REQUIRE(plan->nfix < (1ll << 31), "%s: too many split rows", who);
+        dim3 grid((unsigned)plan->nfix);      // one workgroup per split row: nvec <= 256 = kBlock threads
+        if constexpr (KIND == FWD) {
+            if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+            else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+            else hipLaunchKernelGGL((spattn_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+        } else {
+            const float mul = KIND == BWD_Q ? a.scale : 1.f;
+            if (vw == 4) hipLaunchKernelGGL((spattn_bwd_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
+            else if (vw == 2) hipLaunchKernelGGL((spattn_bwd_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
+            else hipLaunchKernelGGL((spattn_bwd_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
+        }
+        SGCN_HIP_TRY(hipGetLastError());
+    }
+    return SGCN_OK;
+}
+
+int plan_ok(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw) {
+    SGCN_REQUIRE(plan->dev_seg && plan->nseg >= nrows, "%s: malformed plan", who);
+    if (plan->nfix > 0) {
+        SGCN_REQUIRE(plan->dev_fix && plan->dev_ws, "%s: plan with split rows needs dev_fix/dev_ws", who);
+        SGCN_REQUIRE(plan->ws_elems >= plan->nslots * ldw, "%s: workspace too small (%lld < %lld floats)", who,
+                     (long long)plan->ws_elems, (long long)(plan->nslots * ldw));
+    }
+    return SGCN_OK;
+}
+
+inline int64_t ceil4(int64_t d) { return (d + 3) / 4 * 4; }
+
+}  // namespace
+}  // namespace sgcn
+
+using namespace sgcn;
+
+extern "C" int sgcn_spattn_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
+                                   const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                   float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
+    SGCN_REQUIRE(M >= 0 && K >= 0, "spattn: negative size");
+    SGCN_REQUIRE(d > 0, "spattn: d must be positive (got %d)", d);
+    SGCN_REQUIRE(rowptr && C && (Q || M == 0) && (B || K == 0), "spattn: null operand");
+    SGCN_REQUIRE(ldq >= d && ldb >= d && ldc >= d, "spattn: leading dimension smaller than d");
+    SGCN_REQUIRE(std::isfinite(scale), "spattn: scale must be finite");
+    const int64_t ldw = ceil4(d) + 4;            // a slot: the accumulator on a 16-byte pitch, then one vector (m, l, -, -)
+    if (plan) { const int rc = plan_ok("spattn", plan, M, ldw); if (rc) return rc; }
+    const bool split = plan && plan->nfix > 0;
+    const int vw = pick_vw(d, {Q, B, C, split ? (const void*)plan->dev_ws : nullptr}, {ldq, ldb, ldc});
+    { const int rc = width_ok("spattn", d, vw); if (rc) return rc; }
+    if (M == 0) return SGCN_OK;
+
+    AttnArgs a{};
+    a.rowptr = rowptr; a.col = col; a.own = Q; a.ldown = ldq; a.gat = B; a.ldgat = ldb; a.out = C; a.ldo = ldc;
+    a.lse_out = lse; a.scale = scale; a.d = d;
+    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
+    return run<FWD>(a, "spattn", M, plan, vw, (hipStream_t)stream);
+}
+
+extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
+                                         const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                         const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
+                                         float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
+                                         int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
+    SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_q: negative size");
+    SGCN_REQUIRE(d > 0, "spattn_bwd_q: d must be positive (got %d)", d);
+    SGCN_REQUIRE(rowptr && dQ && ((Q && G && C && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_q: null operand");
+    SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && ldc >= d && lddq >= d, "spattn_bwd_q: leading dimension smaller than d");
+    SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_q: scale must be finite");
+    const bool with_add = add && add_rows > 0;
+    if (with_add) SGCN_REQUIRE(ldadd >= d && add_rows <= M, "spattn_bwd_q: bad addend");
+    const int64_t ldw = ceil4(d);
+    if (plan) { const int rc = plan_ok("spattn_bwd_q", plan, M, ldw); if (rc) return rc; }
+    const bool split = plan && plan->nfix > 0;
+    const int vw = pick_vw(d, {Q, B, G, C, dQ, with_add ? add : nullptr, split ? (const void*)plan->dev_ws : nullptr},
+                           {ldq, ldb, ldg, ldc, lddq, with_add ? ldadd : lddq});
+    { const int rc = width_ok("spattn_bwd_q", d, vw); if (rc) return rc; }
+    if (M == 0) return SGCN_OK;
+
+    AttnArgs a{};
+    a.rowptr = rowptr; a.col = col; a.own = Q; a.ldown = ldq; a.gat = B; a.ldgat = ldb; a.G = G; a.ldg = ldg;
+    a.Cf = C; a.ldcf = ldc; a.lse = lse; a.delta_out = delta; a.out = dQ; a.ldo = lddq; a.scale = scale; a.d = d;
+    if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
+    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
+    return run<BWD_Q>(a, "spattn_bwd_q", M, plan, vw, (hipStream_t)stream);
+}
+
+extern "C" int sgcn_spattn_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d,
+                                          const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                          const float* G, int64_t ldg, const float* lse, const float* delta,
+                                          float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
+                                          const sgcn_plan_t* t_plan, void* stream) {
+    SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_kv: negative size");
+    SGCN_REQUIRE(d > 0, "spattn_bwd_kv: d must be positive (got %d)", d);
+    SGCN_REQUIRE(t_rowptr && dB && ((Q && G && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_kv: null operand");
+    SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && lddb >= d, "spattn_bwd_kv: leading dimension smaller than d");
+    SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_kv: scale must be finite");
+    const bool with_add = add && add_rows > 0;
+    if (with_add) SGCN_REQUIRE(ldadd >= d && add_rows <= K, "spattn_bwd_kv: bad addend");
+    const int64_t ldw = ceil4(d);
+    if (t_plan) { const int rc = plan_ok("spattn_bwd_kv", t_plan, K, ldw); if (rc) return rc; }
+    const bool split = t_plan && t_plan->nfix > 0;
+    const int vw = pick_vw(d, {Q, B, G, dB, with_add ? add : nullptr, split ? (const void*)t_plan->dev_ws : nullptr},
+                           {ldq, ldb, ldg, lddb, with_add ? ldadd : lddb});
+    { const int rc = width_ok("spattn_bwd_kv", d, vw); if (rc) return rc; }
+    if (K == 0) return SGCN_OK;
+
+    AttnArgs a{};
+    a.rowptr = t_rowptr; a.col = t_row; a.own = B; a.ldown = ldb; a.gat = Q; a.ldgat = ldq; a.G = G; a.ldg = ldg;
+    a.lse = lse; a.delta = delta; a.out = dB; a.ldo = lddb; a.scale = scale; a.d = d;
+    if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
+    if (split) { a.ws = t_plan->dev_ws; a.ldw = ldw; }
+    return run<BWD_KV>(a, "spattn_bwd_kv", K, t_plan, vw, (hipStream_t)stream);
+}

@@ -12,7 +12,9 @@ two products).
                  column-offset view, ``add=`` / ``add_rows=``): it decides on alignment and, with ``bf16`` (--full_batch_dtype
                  bf16), rounds the dense operand into a bfloat16 scratch table the kernel gathers from (sgcn_spmm_*_b16);
                  ``max_product`` / ``max_backward`` are what it calls under --aggregator max: the element-wise maximum over the
-                 matrix's pattern and its gradient (ops.spmax / ops.spmax_bwd on the row kernel's CSR)
+                 matrix's pattern and its gradient (ops.spmax / ops.spmax_bwd on the row kernel's CSR); ``attn_product`` /
+                 ``attn_backward`` under --aggregator attn: softmax dot-product attention over the same pattern (ops.spattn /
+                 ops.spattn_bwd)
   model_matrix   the StaticMatrix of one model's aggregation layers (the operand width its plan is made for)
   EdgeMask       --edge_dropout: the mask a StaticMatrix and its transpose share; inside a training step (begin_step .. end_step)
                  every product of either reads a value array re-drawn from the base values under the step's key
@@ -129,6 +131,8 @@ def check_aggregator(flags=None):
     agg = getattr(f, 'aggregator', 'sum')
     if agg not in AGGREGATORS:
         raise ValueError("--aggregator must be one of %s, got %r" % ('/'.join(AGGREGATORS), agg))
+    if agg == 'attn':
+        check_attention(f)                    # (its own refusals; this function's answer stays `maximum?`)
     if agg != 'max':
         return False
     if not (f.full_batch and f.test_full_batch):
@@ -145,6 +149,39 @@ def check_aggregator(flags=None):
         raise ValueError("--aggregator max is not supported with --edge_dropout: the maximum reads the adjacency's pattern, "
                          "not its values; there is no edge-masked form yet")
     return True
+
+
+def check_attention(flags=None):
+    """(--aggregator attn?, --attn_scale) with the combinations attention has no kernel or no meaning for refused.  Needs no
+    device; a sibling of check_aggregator, called beside it.  The scale is 0.0 for `1 / sqrt(d) of the layer's own input
+    width` (layers.PlainAggregator works it out per layer) or the positive factor to use as given."""
+    f = FLAGS if flags is None else flags
+    agg = getattr(f, 'aggregator', 'sum')
+    if agg not in AGGREGATORS:
+        raise ValueError("--aggregator must be one of %s, got %r" % ('/'.join(AGGREGATORS), agg))
+    scale = float(getattr(f, 'attn_scale', 0.0))
+    if not (0.0 <= scale < float('inf')):     # (NaN too)
+        raise ValueError("--attn_scale must be finite and >= 0 (0 = 1 / sqrt(d) of each aggregation layer's input width), "
+                         "got %r" % (getattr(f, 'attn_scale', 0.0),))
+    if agg != 'attn':
+        if scale != 0.0:
+            raise ValueError("--attn_scale needs --aggregator attn: it is the factor on the attention scores, and no other "
+                             "aggregator computes any")
+        return False, 0.0
+    if not (f.full_batch and f.test_full_batch):
+        raise ValueError("--aggregator attn needs --full_batch and --test_full_batch: attention is not linear, so no sampled "
+                         "estimator carries it and sampled steps have no such kernel, and the training and the test model "
+                         "must aggregate alike")
+    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
+        raise ValueError("--aggregator attn is not supported with --full_batch_dtype bf16: the attention kernels gather from "
+                         "an fp32 table; there is no bfloat16-table form yet")
+    if getattr(f, 'feature_dtype', 'fp32') == 'bf16':
+        raise ValueError("--aggregator attn is not supported with --feature_dtype bf16: the attention kernels gather from an "
+                         "fp32 table; there is no bfloat16-table form yet")
+    if float(getattr(f, 'edge_dropout', 0.0)) > 0:
+        raise ValueError("--aggregator attn is not supported with --edge_dropout: attention reads the adjacency's pattern, "
+                         "not its values; there is no edge-masked form yet")
+    return True, scale
 
 
 def full_batch_bf16(flags=None):
@@ -441,6 +478,58 @@ class StaticMatrix(object):
             raise ValueError("the element-wise maximum has no bfloat16-operand and no edge-masked form")
         return ops.spmax_bwd(self.rows_csr, g, arg, add=add, add_rows=add_rows)
 
+    # ---- softmax dot-product attention (--aggregator attn) -------------------------------------------------------------------
+    def _attn_staged(self, role, t, d, fill=True):
+        """``t`` (n x d) in this matrix's 16-byte-aligned scratch table of that role and width -- one table per (role, width),
+        allocated on first use and reused, as the ``_scratch`` tables of the bf16 operand are."""
+        key = ('attn', role, int(t.shape[0]), d)
+        tab = self._scratch.get(key)
+        if tab is None:
+            tab = self._scratch[key] = torch.empty((int(t.shape[0]), (d + 3) // 4 * 4), dtype=torch.float32,
+                                                   device=t.device)[:, :d]
+        if fill:
+            tab.copy_(t)
+        return tab
+
+    def _attn_refuse(self, x):
+        if self.bf16 or x.dtype != torch.float32:
+            raise ValueError("attention has no bfloat16-operand form")
+        if self.edge is not None:
+            raise ValueError("attention has no edge-masked form")
+
+    def attn_product(self, x, scale, out=None, want_lse=True):
+        """(out, lse) of ops.spattn over this matrix's PATTERN with the queries x[:M]: out[i] = the rows of ``x`` that row i
+        stores an entry for, weighed by softmax_j(scale * <x[i], x[j]>); lse the rows' log-sum-exp for ``attn_backward``
+        (None with ``want_lse=False``).  Reads the row kernel's CSR -- pattern and segment plan -- only.  The kernel holds
+        d <= 256 * VW columns: an operand whose alignment would push d over that (602-wide features on a pitch of 602
+        floats: VW = 2) is staged once into an aligned scratch table, an ``out`` view of that kind is computed aligned and
+        copied."""
+        self._attn_refuse(x)
+        d = int(x.shape[1])
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out):
+            if ops.attn_vw(d, x) < 4:
+                x = self._attn_staged('x', x, d)
+            if out is not None and ops.attn_vw(d, out) < 4:
+                res, lse = ops.spattn(self.rows_csr, x, scale=scale, want_lse=want_lse,
+                                      out=self._attn_staged('out', out, d, fill=False))
+                out.copy_(res)
+                return out, lse
+        return ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse)
+
+    def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0):
+        """Called on the matrix whose ``attn_product(x, scale)`` gave ``out_fwd`` and ``lse``: the gradient with respect to
+        ``x`` (as keys / values AND as queries) for g = dL/dout, + add on the first ``add_rows`` rows -- ops.spattn_bwd, a
+        gather over this matrix's pattern and one over its transpose's.  Operands are staged as in ``attn_product``."""
+        self._attn_refuse(x)
+        d = int(x.shape[1])
+        ops_ = dict(x=x, g=g, out_fwd=out_fwd, add=add)
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, add):
+            for role, t in list(ops_.items()):
+                if t is not None and ops.attn_vw(d, t) < 4:
+                    ops_[role] = self._attn_staged(role, t, d)
+        return ops.spattn_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], None, ops_['g'], ops_['out_fwd'], lse, scale,
+                              add=ops_['add'], add_rows=add_rows)[1]
+
     def describe(self, d):
         """What train.pp_products records of a product of width d: where the plan came from, the sweep clock (the column
         sweep only), the kernel variant, the product count the kernel was chosen for."""
@@ -460,8 +549,9 @@ def model_matrix(adj, device, model, products, cache_path=None, kernel=None, bf1
     # (the keyword is passed only when set: with the flag off the call is the one the matrix classes -- the recording
     # stand-ins of the CPU tests among them -- have always taken)
     edge = dict(edge_dropout=edge_dropout) if edge_dropout else {}
-    if kernel is None and getattr(FLAGS, 'aggregator', 'sum') == 'max':
-        # every aggregation of the model is a maximum over the pattern (max_product reads rows_csr and its segment plan):
+    if kernel is None and getattr(FLAGS, 'aggregator', 'sum') in ('max', 'attn'):
+        # every aggregation of the model is a maximum / an attention over the pattern (max_product and attn_product read
+        # rows_csr and its segment plan):
         # no column-sweep or LDS plan, tune or cache file is made for products that never run
         kernel = 'rows'
     return StaticMatrix(adj, device, FLAGS.full_batch_kernel if kernel is None else kernel, products,

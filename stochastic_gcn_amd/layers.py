@@ -414,6 +414,23 @@ class PlainAggregator(Layer):
             out[:, :d] = x[:n1]
             _, self._arg = A.max_product(x, out=out[:, d:], want_arg=want)
             return out
+        # --aggregator attn: softmax dot-product attention over the same pattern, the queries the layer's own input rows; a
+        # training model keeps the input, the output and the rows' log-sum-exp for the backward, an evaluation model no lse
+        self._attn = FLAGS.aggregator == 'attn'
+        if self._attn:
+            if not hasattr(A, 'attn_product'):
+                raise RuntimeError("--aggregator attn runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
+                                   "minibatch adjacency has no attention kernel")
+            want = bool(getattr(self.model, 'is_training', True))
+            scale = float(FLAGS.attn_scale) if float(FLAGS.attn_scale) > 0 else float(d) ** -0.5
+            self._x, self._scale = (x if want else None), scale
+            if not concat:
+                self._out, self._lse = A.attn_product(x, scale, want_lse=want)
+                return self._out
+            out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
+            out[:, :d] = x[:n1]
+            self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want)
+            return out
         if not concat:
             return A.product(x)
         out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
@@ -437,6 +454,11 @@ class PlainAggregator(Layer):
             if not self._concat:
                 return A.transpose.max_backward(g, self._arg)
             return A.transpose.max_backward(g[:, d:], self._arg, add=g[:, :d], add_rows=A.shape[0])
+        if self._attn:
+            # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
+            if not self._concat:
+                return A.attn_backward(self._x, g, self._out, self._lse, self._scale)
+            return A.attn_backward(self._x, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d], add_rows=A.shape[0])
         if not self._concat:
             return A.transpose.product(g)
         # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep

@@ -16,6 +16,8 @@ Reference seams replaced:
                   gcn/train.py:241-276 (running fp64 statistics on the device, stats.DeviceStat)
   spmax / spmax_bwd   the element-wise neighbour maximum over a CSR pattern and its backward (--aggregator max: GraphSAGE's pooling
                   aggregator without its MLP; no reference counterpart)
+  spattn / spattn_bwd   softmax dot-product attention over a CSR pattern and its backward (--aggregator attn: every vertex weighs
+                  its neighbours by a softmax over pairwise scores; no reference counterpart)
   history_error   how far a stored history is from the exact activations (no reference counterpart; exact_history.py)
 """
 import ctypes as C
@@ -320,6 +322,115 @@ def spmax_bwd(At, g, arg, out=None, add=None, add_rows=0):
                                      aptr, ldadd, int(add_rows) if add is not None else 0,
                                      C.byref(plan) if plan is not None else None, _stream()))
     return out
+
+
+ATTN_MAX_VECTORS = 256       # sgcn_spattn.hip: one lane group holds a whole row, 64 lanes x 4 vectors of VW elements
+
+
+def attn_vw(d, *tensors):
+    """The vector width sgcn_spattn_* would pick for width ``d`` and these 2-D operands (include/sgcn.h: the row kernels'
+    rule): 4 with 16-byte aligned bases and pitches that are multiples of 4, 2 with 8-byte / multiples of 2, else 1.  The
+    kernels hold d <= ATTN_MAX_VECTORS * VW columns."""
+    for vw in (4, 2):
+        span = (d + vw - 1) // vw * vw
+        ok = True
+        for t in tensors:
+            if t is None:
+                continue
+            ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+            if ld % vw or ld < span or t.data_ptr() % (4 * vw):
+                ok = False
+                break
+        if ok:
+            return vw
+    return 1
+
+
+def _attn_out(rows, d, device):
+    """A fresh (rows, d) fp32 result of the attention kernels: contiguous, unless that pitch alone would narrow the vectors
+    so far that d no longer fits one lane group -- then on a 16-byte pitch."""
+    if d > ATTN_MAX_VECTORS * (4 if d % 4 == 0 else 2 if d % 2 == 0 else 1):
+        return _pitched_out(rows, d, device)
+    return torch.empty((rows, d), dtype=torch.float32, device=device)
+
+
+def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True):
+    """(out, lse): softmax dot-product attention over the stored pattern of the DeviceCSR ``A`` (M x K, unique column ids
+    per row; stored values are not read) -- sgcn_spattn_csr_f32.  With s_ij = scale * <q[i], x[j]> over the entries j of
+    row i: lse[i] = log sum_j exp(s_ij), out[i] = sum_j exp(s_ij - lse[i]) x[j]; an empty row gives +0.0 and -inf.
+    ``q=None`` means x[:M].  ``out`` may be a pitched (M, >= d) view.  ``want_lse=False`` (an evaluation): lse is None,
+    nothing is allocated for it."""
+    check_unique_cols(A)
+    M, K = A.shape
+    bptr, ldb = _rows2d(x, "x")
+    d = int(x.shape[1])
+    if x.shape[0] < K:
+        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
+    if q is None:
+        if x.shape[0] < M:
+            raise ValueError("q=None takes x[:%d] as the queries, x has %d rows" % (M, x.shape[0]))
+        qptr, ldq = bptr, ldb
+    else:
+        qptr, ldq = _rows2d(q, "q")
+        if q.shape[0] < M or q.shape[1] != d:
+            raise ValueError("q has shape %s, need (>=%d, %d)" % (tuple(q.shape), M, d))
+    if out is None:
+        out = _attn_out(M, d, x.device)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != M or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
+    lse = torch.empty((M,), dtype=torch.float32, device=x.device) if want_lse else None
+    plan = A.plan.struct(d + 4) if A.plan is not None else None          # (a forward slot: the row + one vector for (m, l))
+    check(lib.sgcn_spattn_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, qptr, ldq, bptr, ldb, float(scale), cptr, ldc,
+                                  _ptr(lse), C.byref(plan) if plan is not None else None, _stream()))
+    return out, lse
+
+
+def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0):
+    """(dq, dx), the gradient of ``spattn(A, x, q, scale)`` for g = dL/dout, from the forward's ``out_fwd`` and ``lse`` --
+    sgcn_spattn_csr_bwd_q_f32 over ``A``, then sgcn_spattn_csr_bwd_kv_f32 over ``At``, the DeviceCSR of the TRANSPOSED
+    pattern (ops.transpose_host: source rows ascending).  Nothing nnz-sized is stored, no atomics: bitwise reproducible.
+    With an explicit ``q``: dq (M x d, + add on its first ``add_rows`` rows) and dx = dB (K x d) separately.  With
+    ``q=None`` (the queries are x[:M]): (None, dx) with dx = dB + [dQ + add ; 0] -- the first launch's result is the second
+    one's addend, so the sum costs no extra pass."""
+    M, K = A.shape
+    if tuple(At.shape) != (K, M):
+        raise ValueError("At has shape %s, the transpose of %s is needed" % (tuple(At.shape), tuple(A.shape)))
+    bptr, ldb = _rows2d(x, "x")
+    d = int(x.shape[1])
+    if x.shape[0] < K:
+        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
+    if q is None:
+        if x.shape[0] < M or K < M:
+            raise ValueError("q=None takes x[:%d] as the queries, x has %d rows and A %d columns" % (M, x.shape[0], K))
+        qptr, ldq = bptr, ldb
+    else:
+        qptr, ldq = _rows2d(q, "q")
+        if q.shape[0] < M or q.shape[1] != d:
+            raise ValueError("q has shape %s, need (>=%d, %d)" % (tuple(q.shape), M, d))
+    gptr, ldg = _rows2d(g, "g")
+    cptr, ldc = _rows2d(out_fwd, "out_fwd")
+    if tuple(g.shape) != (M, d) or out_fwd.shape[0] != M or out_fwd.shape[1] < d:
+        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (M, d, tuple(g.shape), tuple(out_fwd.shape)))
+    _dev(lse, torch.float32, "lse")
+    if lse.dim() != 1 or lse.shape[0] != M or not lse.is_contiguous():
+        raise ValueError("lse must be a contiguous vector of %d floats" % M)
+    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
+    add_rows = int(add_rows) if add is not None else 0
+    delta = torch.empty((M,), dtype=torch.float32, device=x.device)
+    dq = _attn_out(M, d, x.device)
+    dx = _attn_out(K, d, x.device)
+    plan = A.plan.struct(d) if A.plan is not None else None
+    check(lib.sgcn_spattn_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, qptr, ldq, bptr, ldb, float(scale),
+                                        gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), _rows2d(dq, "dq")[1],
+                                        aptr, ldadd, add_rows, C.byref(plan) if plan is not None else None, _stream()))
+    tplan = At.plan.struct(d) if At.plan is not None else None
+    fused = q is None
+    check(lib.sgcn_spattn_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, qptr, ldq, bptr, ldb, float(scale),
+                                         gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(), _rows2d(dx, "dx")[1],
+                                         dq.data_ptr() if fused else None, _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0,
+                                         C.byref(tplan) if tplan is not None else None, _stream()))
+    return (None if fused else dq), dx
 
 
 def vr_aggregate(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_self, out_h=None, out_mu=None):
