@@ -949,7 +949,8 @@ int64_t sgcn_sched_packed_meta_len(int32_t L);
  * sampler handle must not be used by anyone else until sgcn_prefetch_stop.
  * sgcn_prefetch_next blocks (holding no interpreter lock) for the next batch: 0 = filled *slot, sizes,
  * meta[sgcn_sched_packed_meta_len(L)] (*spill != NULL: the batch outgrew the slot and lives in that
- * heap buffer instead); 1 = epoch exhausted; < 0 = sampler error.  sgcn_prefetch_release hands a slot
+ * heap buffer instead); 1 = epoch exhausted; < 0 = sampler error, returned by the call that asks for the batch that
+ * failed: the batches in front of it are delivered first, whatever the producers' timing.  sgcn_prefetch_release hands a slot
  * back once the consumer's copy out of it has completed (`lag` = how many handed-out slots the
  * consumer keeps besides the current one; it bounds the producers' look-ahead).  Replaces the synchronous
  * `feed_dict = sch.minibatch(batch_size)` of gcn/train.py:189-191. */

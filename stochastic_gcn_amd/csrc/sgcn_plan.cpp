@@ -57,12 +57,16 @@ int sgcn_plan_fill(const int32_t* rowptr, int32_t M, int32_t T, sgcn_seg_t* seg,
     if (M < 0 || (M > 0 && (!rowptr || !seg)))
         return sgcn::fail(SGCN_ERR_INVALID, "plan_fill: bad argument");
     T = pick_t(T);
+    for (int32_t r = 0; r < M; r++) {               // refused as sgcn_plan_count refuses it, before anything is written
+        const int64_t n = (int64_t)rowptr[r + 1] - rowptr[r];
+        if (n < 0) return sgcn::fail(SGCN_ERR_INVALID, "plan_fill: rowptr not monotone at %d", r);
+        if (n > T && !fix) return sgcn::fail(SGCN_ERR_INVALID, "plan_fill: split rows but no fix array");
+    }
     int64_t s = 0, f = 0;
     int32_t slot = 0;
     for (int32_t r = 0; r < M; r++) {
         const int32_t b = rowptr[r], e = rowptr[r + 1];
         if (e - b <= T) { seg[s++] = sgcn_seg_t{r, b, e, -1}; continue; }
-        if (!fix) return sgcn::fail(SGCN_ERR_INVALID, "plan_fill: split rows but no fix array");
         const int32_t first = slot;
         // equal-sized pieces (not T,T,..,rest) so no wavefront gets a tiny tail piece
         const int32_t c = (int32_t)(((int64_t)e - b + T - 1) / T);

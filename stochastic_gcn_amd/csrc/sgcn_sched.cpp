@@ -669,6 +669,8 @@ struct sgcn_prefetch {
     int32_t next_batch = 0;                                      // the batch the consumer takes next
     std::vector<std::unique_ptr<std::vector<int32_t>>> spills;   // batches that outgrew their slot
     bool stop = false; int32_t running = 0; int error = 0; std::string error_msg;
+    int32_t error_batch = INT32_MAX;                             // the first batch that failed: the batches in front of it are still
+                                                                 // built and delivered, the error is the answer to a request for IT
     std::unique_ptr<std::atomic<char>[]> ready_flag;             // is_ready mirrored for the consumer's short spin before it blocks
     std::atomic<int32_t> taken_raw{0};
     std::atomic<int32_t> raw_count{0};                           // hops handed over by the core so far (same, for the packers)
@@ -701,8 +703,8 @@ struct sgcn_prefetch {
     bool take_slot(int32_t b, int32_t* slot) {
         std::unique_lock<std::mutex> lk(mu);
         const int32_t w = window();
-        cv_free.wait(lk, [&] { return stop || error || (b < next_batch + w && !free_slots.empty()); });
-        if (stop || error) return false;
+        cv_free.wait(lk, [&] { return stop || b > error_batch || (b < next_batch + w && !free_slots.empty()); });
+        if (stop || b > error_batch) return false;
         *slot = free_slots.front(); free_slots.pop_front();
         return true;
     }
@@ -722,9 +724,9 @@ struct sgcn_prefetch {
         ready_flag[(size_t)b].store(1, std::memory_order_release);
         cv_ready.notify_all();
     }
-    void set_error(int rc) {
+    void set_error(int rc, int32_t b) {
         std::lock_guard<std::mutex> lk(mu);
-        if (!error) { error = rc; error_msg = sgcn::error_slot(); }
+        if (!error || b < error_batch) { error = rc; error_msg = sgcn::error_slot(); error_batch = b; }
     }
     void producer_exit() {
         std::lock_guard<std::mutex> lk(mu);
@@ -746,7 +748,7 @@ struct sgcn_prefetch {
             const int rc = ss[(size_t)k]->impl.pack_batch((int32_t)(off[b + 1] - off[b]), ids.data() + off[b], L,
                                                           degrees.data(), labels, n_classes, plan_T, r.meta.data(),
                                                           meta_len, &r.n_i, &r.n_f);
-            if (rc != SGCN_OK) { set_error(rc); break; }
+            if (rc != SGCN_OK) { set_error(rc, b); break; }
             const int64_t ni = std::max<int64_t>(r.n_i, 1), nf = std::max<int64_t>(r.n_f, 1);
             int32_t* dst = dest(r, ni, nf);
             const auto c2 = clk::now();
@@ -794,8 +796,10 @@ struct sgcn_prefetch {
                 spin_for([&] { return raw_count.load(std::memory_order_acquire) > seen; }, 40.0);
                 std::unique_lock<std::mutex> lk(mu);
                 cv_raw.wait(lk, [&] { return stop || error || !raw_ready.empty() || core_done; });
+                // batches arrive in order, the oldest first: after an error every batch in front of the failed one has
+                // been taken already (by the packers that are building them), what is left here lies behind it
                 if (stop || error || raw_ready.empty()) break;
-                raw = raw_ready.front(); raw_ready.pop_front();       // batches arrive in order: the oldest first
+                raw = raw_ready.front(); raw_ready.pop_front();
                 taken_raw.fetch_add(1, std::memory_order_relaxed);
             }
             const int32_t b = raw->batch;
@@ -812,7 +816,7 @@ struct sgcn_prefetch {
                 raw_free.push_back(raw);
             }
             cv_raw.notify_all();
-            if (rc != SGCN_OK) { set_error(rc); break; }
+            if (rc != SGCN_OK) { set_error(rc, b); break; }
             const int64_t ni = std::max<int64_t>(r.n_i, 1), nf = std::max<int64_t>(r.n_f, 1);
             int32_t* dst = dest(r, ni, nf);
             const auto c2 = clk::now();
@@ -959,7 +963,7 @@ int sgcn_prefetch_next(sgcn_prefetch_t* p, int32_t* slot, int64_t* meta, int64_t
         std::unique_lock<std::mutex> lk(p->mu);
         const int32_t b = p->next_batch;
         if (b >= (int32_t)p->ready.size()) return 1;
-        p->cv_ready.wait(lk, [&] { return p->is_ready[(size_t)b] || p->error || p->running == 0; });
+        p->cv_ready.wait(lk, [&] { return p->is_ready[(size_t)b] || b >= p->error_batch || p->running == 0; });
         if (!p->is_ready[(size_t)b]) {
             if (p->error) return sgcn::fail(p->error, "%s", p->error_msg.c_str());
             return sgcn::fail(SGCN_ERR_INVALID, "prefetch_next: producers exited before batch %d", (int)b);
