@@ -56,7 +56,8 @@ const char* sgcn_last_error(void);
  *       of a history -- sgcn_hist_error_f32 / _h16 / _ws_doubles; the value array of a static plan re-drawn under an
  *       edge mask -- sgcn_edge_revalue_f32; the element-wise neighbour maximum over a CSR pattern and its backward --
  *       sgcn_spmax_csr_f32 / sgcn_spmax_csr_bwd_f32; softmax dot-product attention over a CSR pattern and its backward --
- *       sgcn_spattn_csr_f32 / sgcn_spattn_csr_bwd_q_f32 / sgcn_spattn_csr_bwd_kv_f32) */
+ *       sgcn_spattn_csr_f32 / sgcn_spattn_csr_bwd_q_f32 / sgcn_spattn_csr_bwd_kv_f32; their multi-head forms --
+ *       sgcn_spattn_mh_csr_f32 / sgcn_spattn_mh_csr_bwd_q_f32 / sgcn_spattn_mh_csr_bwd_kv_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -541,6 +542,53 @@ int sgcn_spattn_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t
                                float* dev_dB, int64_t lddb,
                                const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
                                const sgcn_plan_t* t_plan /* nullable */, void* stream);
+
+/* ---- multi-head attention (--attn_heads; additive, still v16) ---------------------------------------------------------------
+ * The three calls above with `int32_t heads` inserted directly after d.  heads = H in {1, 2, 4, 8}, d % H == 0, dh = d / H.
+ * Head h is the columns [h*dh, (h+1)*dh) of Q, B, G, C, dQ, dB and the addends, and every head is an attention of its own
+ * over the same pattern -- for every head h independently, with X^h the head's column slice of X:
+ *     s_ij^h     = scale * <Q_i^h, B_j^h>
+ *     lse[i,h]   = log sum_j exp(s_ij^h)            (m + log l, the logarithm in fp64 once per row and head)
+ *     p_ij^h     = exp(s_ij^h - lse[i,h])
+ *     C_i^h      = sum_j p_ij^h B_j^h               (true division acc / l; an empty row: +0.0 and lse = -inf in every head)
+ *     delta[i,h] = <G_i^h, C_i^h>,   e_ij^h = p_ij^h (<G_i^h, B_j^h> - delta[i,h])
+ *     dQ_i^h     = scale sum_j e_ij^h B_j^h (+ add)
+ *     dB_j^h     = sum_i ( p_ij^h G_i^h + scale e_ij^h Q_i^h ) (+ add)
+ * dev_lse and dev_delta are contiguous row-major M x heads fp32 tables, element [i*heads + h].  heads = 1 is the
+ * single-head definition exactly: the sgcn_spattn_csr_* calls are the heads = 1 calls of the same host bodies, and run the
+ * same kernels as before.
+ *
+ * Lanes.  A row segment's group of G lanes is cut into H aligned sub-groups of G / H lanes; sub-group h owns head h, its
+ * lane r the head's vectors r, r + G/H, .. (at most 4).  The dot products reduce over the sub-group only (none at all when
+ * a head is one vector wide), the online softmax's (m, l, acc) are per head.  No atomics, nothing nnz-sized written.
+ *
+ * Width.  A vector never straddles two heads: for heads > 1, VW is the widest of {4, 2, 1} that the operands' pointers and
+ * pitches allow (the rule above) AND that divides dh; nothing is ragged then.  The limit stays d <= 256 * VW with that VW
+ * (520 columns in 8 heads: dh = 65, VW = 1, refused), the message naming the limit and that VW must divide d / heads.
+ *
+ * Slots.  SLOT GEOMETRY OF THE FORWARD: ldw = 4*ceil(d/4) + 4*heads floats per slot -- acc on floats [0, d), head h's m at
+ * float 4*ceil(d/4) + 4*h and its l at 4*ceil(d/4) + 4*h + 1 -- so ws_elems >= nslots * (4*ceil(d/4) + 4*heads); heads = 1
+ * is the slot above.  The ordered fix-up takes, per head, the largest m of the row's slots, adds in slot order and
+ * divides.  The backward slots stay 4*ceil(d/4).
+ *
+ * Validation, before any HIP call and with nothing written (SGCN_ERR_INVALID): everything the single-head calls refuse,
+ * and heads outside {1, 2, 4, 8} or d % heads != 0. */
+int sgcn_spattn_mh_csr_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                           const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb, float scale,
+                           float* dev_C, int64_t ldc, float* dev_lse /* nullable; M x heads */,
+                           const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spattn_mh_csr_bwd_q_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d,
+                                 int32_t heads, const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb, float scale,
+                                 const float* dev_G, int64_t ldg, const float* dev_C, int64_t ldc, const float* dev_lse,
+                                 float* dev_delta, float* dev_dQ, int64_t lddq,
+                                 const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                                 const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spattn_mh_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t_row, int32_t K, int32_t M, int32_t d,
+                                  int32_t heads, const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb, float scale,
+                                  const float* dev_G, int64_t ldg, const float* dev_lse, const float* dev_delta,
+                                  float* dev_dB, int64_t lddb,
+                                  const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                                  const sgcn_plan_t* t_plan /* nullable */, void* stream);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-

@@ -9,6 +9,9 @@
         the README full-batch recipe with --aggregator sum and with attn: the times of `epochs` epochs behind one warm epoch
     python profiles/attn_aggregator_probe.py all
         both on one copy of the data
+    python profiles/attn_aggregator_probe.py heads [--heads 2 4 8] [--d 128] [--rounds 7] [--reps 10]
+        --attn_heads: attention's forward and its two-launch backward at heads = 1 and at every H given, on the same matrix,
+        width and plan, in ONE process in interleaved rounds (each head count at its own default scale 1 / sqrt(d / H))
 
 Records go to stdout as JSON lines (everything else to stderr)."""
 import argparse
@@ -93,6 +96,46 @@ def kernels(args, data):
     print(json.dumps(rec), flush=True)
 
 
+def heads(args, data):
+    import torch
+    from stochastic_gcn_amd import ops
+    dev = torch.device('cuda:0')
+    a = data[1].tocsr()
+    n, d = a.shape[0], args.d
+    A = ops.DeviceCSR.from_scipy(a, dev, with_transpose=True)
+    rng = np.random.RandomState(0)
+    x = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+    g = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+    out = torch.empty_like(x)
+    calls = {}
+    for H in [1] + [h for h in args.heads if h != 1]:
+        scale = float(d // H) ** -0.5
+        att = torch.empty_like(x)
+        _, lse = ops.spattn(A, x, scale=scale, out=att, heads=H)
+        calls["fwd_h%d" % H] = lambda H=H, scale=scale: ops.spattn(A, x, scale=scale, out=out, heads=H)
+        calls["bwd_h%d" % H] = lambda H=H, scale=scale, att=att, lse=lse: ops.spattn_bwd(A, A.transpose, x, None, g, att, lse,
+                                                                                         scale, heads=H)
+    for f in calls.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in calls}
+    for _ in range(args.rounds):
+        for k, f in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.reps):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / args.reps)
+    rec = {"what": "heads", "matrix": "s-reddit train_adj", "rows": n, "nnz": int(a.nnz), "d": d, "plan_T": "default",
+           "split_rows": A.plan.nfix, "split_rows_T": A.transpose.plan.nfix, "rounds": args.rounds, "reps": args.reps}
+    for k, v in ms.items():
+        rec[k + "_ms_median"], rec[k + "_ms_min"], rec[k + "_ms_max"] = float(np.median(v)), float(min(v)), float(max(v))
+    print(json.dumps(rec), flush=True)
+
+
 def epochs(args, data):
     import torch
     for agg in ("sum", "attn", "sum", "attn"):
@@ -116,7 +159,8 @@ def epochs(args, data):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernels", "epochs", "all"])
+    ap.add_argument("what", choices=["kernels", "epochs", "all", "heads"])
+    ap.add_argument("--heads", type=int, nargs='+', default=[2, 4, 8])
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=10)
@@ -125,7 +169,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     data = _data()
     for what in (["kernels", "epochs"] if args.what == "all" else [args.what]):
-        {"kernels": kernels, "epochs": epochs}[what](args, data)
+        {"kernels": kernels, "epochs": epochs, "heads": heads}[what](args, data)
 
 
 if __name__ == "__main__":

@@ -18,6 +18,16 @@
 //
 // A chunk of U entries is always processed whole: past the end of the column block the last entry is loaded again and
 // its weight forced to exactly 0 (score -inf), which adds +-0 to the sums -- one code path, no remainder loop.
+//
+// Multi-head (heads = H in {2, 4, 8}, the MH = true instantiations; H = 1 runs the MH = false ones, which are the single-head
+// kernels unchanged): head h is the columns [h dh, (h + 1) dh), dh = d / H, and every formula above holds per head, lse and
+// delta being M x H tables.  The group's G lanes are cut into H aligned sub-groups of Gh = G / H lanes (Gh a wave-uniform
+// run-time value, not a template parameter: the instantiations double, they do not quadruple); sub-group h owns head h,
+// its lane r the head's vectors r, r + Gh, .. (NV <= 4 of them).  VW divides dh, so no vector straddles two heads and
+// nothing is ragged.  The gathers are the single-head ones; the dot products reduce over the sub-group only (xor offsets
+// below Gh stay inside an aligned sub-group; Gh = 1 moves nothing), and the running (m, l, acc) -- per lane already --
+// is simply each head's own: lanes of different heads may take the `maximum rises` branch differently, which is plain
+// divergence, since nothing inside it crosses lanes.
 #include <cmath>
 #include "sgcn_dev.h"
 
@@ -57,6 +67,9 @@ struct AttnArgs {
     const float* add;        // backward: out[row] += add[row] for row < add_rows
     int64_t ldadd;
     int32_t add_rows;
+    int32_t heads;           // H; the MH kernels only read the three below
+    int32_t gh;              // lanes per head, G / H (a power of two)
+    int32_t nvh;             // vectors per head, dh / VW
 };
 
 template <int G>
@@ -133,19 +146,66 @@ __device__ __forceinline__ void group_sum2(float (&s)[U], float (&t)[U], int lig
     }
 }
 
+// the multi-head forms: the same sums over the aligned sub-group of `gh` lanes (wave-uniform, a power of two <= G) that the
+// lane's head owns; gh == 1: every lane already holds its head's totals
+template <int G, int U>
+__device__ __forceinline__ void head_sum(float (&s)[U], int gh) {
+    for (int o = gh >> 1; o > 0; o >>= 1)
+#pragma unroll
+        for (int u = 0; u < U; u++) s[u] += __shfl_xor(s[u], o, G);
+}
+template <int G, int U>
+__device__ __forceinline__ void head_sum2(float (&s)[U], float (&t)[U], int lig, int gh) {
+    if (gh == 1) return;
+    const bool odd = lig & 1;
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const float keep = odd ? t[u] : s[u], send = odd ? s[u] : t[u];
+        v[u] = keep + __shfl_xor(send, 1, G);
+    }
+    for (int o = 2; o < gh; o <<= 1)
+#pragma unroll
+        for (int u = 0; u < U; u++) v[u] += __shfl_xor(v[u], o, G);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        s[u] = __shfl(v[u], lig & ~1, G);
+        t[u] = __shfl(v[u], lig | 1, G);
+    }
+}
+
 // what a lane owns of a row: NV vectors, their byte offsets (lanes past the row width re-read the last valid vector
 // instead of branching around the load) and how many of their elements exist
-template <int G, int NV, int VW>
+// MH: the lane's head is lig / gh, and its vectors are r, r + gh, .. (r = lig % gh) of that head's nvh whole ones
+template <int G, int NV, int VW, bool MH = false>
 struct Lane {
     uint32_t off[NV];
     int cnt[NV];     // 0: no such vector; VW: whole; between: the ragged last one
     int vi[NV];
+    int head;        // MH: the head this lane works for (0 otherwise)
+    bool first;      // MH: the lane that stores its head's scalars (lane 0 of the group otherwise)
     __device__ __forceinline__ Lane(const AttnArgs& a, int lig) {
+        if constexpr (MH) {
+            const int r = lig & (a.gh - 1);
+            head = lig >> (31 - __builtin_clz(a.gh));
+            first = r == 0;
+            const int base = head * a.nvh;
 #pragma unroll
-        for (int k = 0; k < NV; k++) {
-            vi[k] = lig + k * G;
-            cnt[k] = vi[k] < a.nvec ? min(VW, a.d - vi[k] * VW) : 0;
-            off[k] = (uint32_t)min(vi[k], a.nvec - 1) * (uint32_t)(VW * sizeof(float));
+            for (int k = 0; k < NV; k++) {
+                const int v = r + k * a.gh;
+                vi[k] = base + v;
+                cnt[k] = v < a.nvh ? VW : 0;
+                off[k] = (uint32_t)(base + min(v, a.nvh - 1)) * (uint32_t)(VW * sizeof(float));
+            }
+        } else {
+            head = 0;
+            first = lig == 0;
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+                vi[k] = lig + k * G;
+                cnt[k] = vi[k] < a.nvec ? min(VW, a.d - vi[k] * VW) : 0;
+                off[k] = (uint32_t)min(vi[k], a.nvec - 1) * (uint32_t)(VW * sizeof(float));
+            }
         }
     }
     // a row of the segment's own: loaded once, pads and absent vectors zeroed -- a zero there keeps the (finite)
@@ -164,14 +224,14 @@ template <int NV>
 struct Unroll { static constexpr int fwd = 4, bwd_q = NV >= 3 ? 2 : 4, bwd_kv = NV >= 2 ? 2 : 4; };
 
 // ---- forward ------------------------------------------------------------------------------------------------------------
-template <int G, int NV, int VW>
+template <int G, int NV, int VW, bool MH>
 __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
     typedef typename Vec<VW>::type VT;
     constexpr int U = Unroll<NV>::fwd;
     const int lig = threadIdx.x & (G - 1);
     int row, start, end, slot;
     if (!my_segment<G>(a, row, start, end, slot)) return;
-    const Lane<G, NV, VW> L(a, lig);
+    const Lane<G, NV, VW, MH> L(a, lig);
 
     VT q[NV], acc[NV];
     L.own_row(a.own, a.ldown, row, q);
@@ -195,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
 #pragma unroll
                 for (int k = 0; k < NV; k++) b[u][k] = vload<VW>(reinterpret_cast<const float*>(src + L.off[k]));
             }
-            if (a.ragged) {
+            if (!MH && a.ragged) {
 #pragma unroll
                 for (int u = 0; u < U; u++)
 #pragma unroll
@@ -207,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
 #pragma unroll
                 for (int k = 0; k < NV; k++) s[u] = vdot<VW>(q[k], b[u][k], s[u]);
             }
-            group_sum<G, U>(s);
+            if constexpr (MH) head_sum<G, U>(s, a.gh); else group_sum<G, U>(s);
             float mn = m;
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -240,18 +300,27 @@ __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
                 if (!empty) r = acc[k] / l;
                 vstore_n<VW>(a.out + (int64_t)row * a.ldo + (int64_t)L.vi[k] * VW, r, L.cnt[k]);
             }
-        if (a.lse_out && lig == 0) a.lse_out[row] = empty ? -INFINITY : lse_of(m, l);
+        if constexpr (MH) {
+            if (a.lse_out && L.first) a.lse_out[(int64_t)row * a.heads + L.head] = empty ? -INFINITY : lse_of(m, l);
+        } else {
+            if (a.lse_out && lig == 0) a.lse_out[row] = empty ? -INFINITY : lse_of(m, l);
+        }
     } else {
         float* w = a.ws + (int64_t)slot * a.ldw;
 #pragma unroll
         for (int k = 0; k < NV; k++)
             if (L.cnt[k]) vstore<VW>(w + (int64_t)L.vi[k] * VW, acc[k]);
-        if (lig == 0) { w[a.ldw - 4] = m; w[a.ldw - 3] = l; }
+        if constexpr (MH) {                    // head h's (m, l): the vector h after the accumulator
+            if (L.first) { float* ml = w + (a.ldw - 4 * a.heads) + 4 * L.head; ml[0] = m; ml[1] = l; }
+        } else {
+            if (lig == 0) { w[a.ldw - 4] = m; w[a.ldw - 3] = l; }
+        }
     }
 }
 
 // A split row's slots: the largest m first, then l and acc added in slot order, each slot scaled by exp(m_q - m).
-template <int VW>
+// MH: the thread's vector belongs to head vi / nvh, whose (m, l) sit 4 * head floats further on; per head the same sum.
+template <int VW, bool MH>
 __global__ __launch_bounds__(kBlock) void spattn_fix_kernel(AttnArgs a, const sgcn_fix_t* fix, int64_t nfix) {
     typedef typename Vec<VW>::type VT;
     const int64_t f = blockIdx.x;
@@ -260,15 +329,18 @@ __global__ __launch_bounds__(kBlock) void spattn_fix_kernel(AttnArgs a, const sg
     const int vi = threadIdx.x;
     if (vi >= a.nvec) return;
     const float* w = a.ws + (int64_t)fx.first_slot * a.ldw;
+    int head = 0;
+    int64_t mo = a.ldw - 4;                    // where the slot keeps this thread's m; l follows it
+    if constexpr (MH) { head = vi / a.nvh; mo = a.ldw - 4 * a.heads + 4 * head; }
     float m = -INFINITY;
-    for (int q = 0; q < fx.nslots; q++) m = fmaxf(m, w[(int64_t)q * a.ldw + a.ldw - 4]);
+    for (int q = 0; q < fx.nslots; q++) m = fmaxf(m, w[(int64_t)q * a.ldw + mo]);
     float l = 0.f;
     VT acc = vzero<VW>();
     for (int q = 0; q < fx.nslots; q++) {
         const float* wq = w + (int64_t)q * a.ldw;
-        const float lq = wq[a.ldw - 3];
+        const float lq = wq[mo + 1];
         if (lq > 0.f) {                        // (a segment always holds an entry; the guard keeps -inf - -inf out)
-            const float sc = expf(wq[a.ldw - 4] - m);
+            const float sc = expf(wq[mo] - m);
             l = __builtin_fmaf(lq, sc, l);
             acc = vfma<VW>(sc, vload<VW>(wq + (int64_t)vi * VW), acc);
         }
@@ -276,7 +348,11 @@ __global__ __launch_bounds__(kBlock) void spattn_fix_kernel(AttnArgs a, const sg
     VT r = vzero<VW>();
     if (l > 0.f) r = acc / l;
     vstore_n<VW>(a.out + (int64_t)fx.row * a.ldo + (int64_t)vi * VW, r, min(VW, a.d - vi * VW));
-    if (a.lse_out && vi == 0) a.lse_out[fx.row] = l > 0.f ? lse_of(m, l) : -INFINITY;
+    if constexpr (MH) {
+        if (a.lse_out && vi == head * a.nvh) a.lse_out[(int64_t)fx.row * a.heads + head] = l > 0.f ? lse_of(m, l) : -INFINITY;
+    } else {
+        if (a.lse_out && vi == 0) a.lse_out[fx.row] = l > 0.f ? lse_of(m, l) : -INFINITY;
+    }
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------
@@ -300,14 +376,14 @@ __device__ __forceinline__ void bwd_store(const AttnArgs& a, int row, int vi, ty
 }
 
 // over P: delta_i and dQ[i] = scale * sum_j e_ij B[j]
-template <int G, int NV, int VW>
+template <int G, int NV, int VW, bool MH>
 __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
     typedef typename Vec<VW>::type VT;
     constexpr int U = Unroll<NV>::bwd_q;
     const int lig = threadIdx.x & (G - 1);
     int row, start, end, slot;
     if (!my_segment<G>(a, row, start, end, slot)) return;
-    const Lane<G, NV, VW> L(a, lig);
+    const Lane<G, NV, VW, MH> L(a, lig);
 
     VT q[NV], g[NV], acc[NV];
     L.own_row(a.own, a.ldown, row, q);
@@ -321,11 +397,18 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
         float dd[1] = {0.f}, none[1] = {0.f};
 #pragma unroll
         for (int k = 0; k < NV; k++) dd[0] = vdot<VW>(g[k], c[k], dd[0]);
-        group_sum2<G, 1>(none, dd, lig);
+        if constexpr (MH) head_sum2<G, 1>(none, dd, lig, a.gh); else group_sum2<G, 1>(none, dd, lig);
         delta = dd[0];
     }
-    if (lig == 0 && start == a.rowptr[row]) a.delta_out[row] = delta;   // the row's first segment
-    const float lse = a.lse[row];
+    float lse;
+    if constexpr (MH) {                        // per head: element [row, head] of the M x H tables
+        const int64_t rh = (int64_t)row * a.heads + L.head;
+        if (L.first && start == a.rowptr[row]) a.delta_out[rh] = delta;
+        lse = a.lse[rh];
+    } else {
+        if (lig == 0 && start == a.rowptr[row]) a.delta_out[row] = delta;   // the row's first segment
+        lse = a.lse[row];
+    }
 #pragma unroll
     for (int k = 0; k < NV; k++) acc[k] = vzero<VW>();
     const char* Bb = reinterpret_cast<const char*>(a.gat);
@@ -345,7 +428,7 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
 #pragma unroll
                 for (int k = 0; k < NV; k++) b[u][k] = vload<VW>(reinterpret_cast<const float*>(src + L.off[k]));
             }
-            if (a.ragged) {
+            if (!MH && a.ragged) {
 #pragma unroll
                 for (int u = 0; u < U; u++)
 #pragma unroll
@@ -360,7 +443,7 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
                     t[u] = vdot<VW>(g[k], b[u][k], t[u]);
                 }
             }
-            group_sum2<G, U>(s, t, lig);
+            if constexpr (MH) head_sum2<G, U>(s, t, lig, a.gh); else group_sum2<G, U>(s, t, lig);
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const float p = j + u < n ? expf(s[u] * a.scale - lse) : 0.f;
@@ -384,14 +467,14 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
 }
 
 // over P^T: dB[j] = sum_i ( p_ij G[i] + scale e_ij Q[i] ), two gathered rows per entry
-template <int G, int NV, int VW>
+template <int G, int NV, int VW, bool MH>
 __global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
     typedef typename Vec<VW>::type VT;
     constexpr int U = Unroll<NV>::bwd_kv;
     const int lig = threadIdx.x & (G - 1);
     int row, start, end, slot;
     if (!my_segment<G>(a, row, start, end, slot)) return;
-    const Lane<G, NV, VW> L(a, lig);
+    const Lane<G, NV, VW, MH> L(a, lig);
 
     VT b[NV], acc[NV];
     L.own_row(a.own, a.ldown, row, b);
@@ -413,15 +496,20 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
                 const int i = bcast_i<G>(myrow, min(j + u, n - 1));
                 const char* qs = Qb + (int64_t)i * ldq_bytes;        // G == 64: scalar bases
                 const char* gs = Gb + (int64_t)i * ldg_bytes;
-                lse[u] = a.lse[i];
-                delta[u] = a.delta[i];
+                if constexpr (MH) {
+                    lse[u] = a.lse[(int64_t)i * a.heads + L.head];
+                    delta[u] = a.delta[(int64_t)i * a.heads + L.head];
+                } else {
+                    lse[u] = a.lse[i];
+                    delta[u] = a.delta[i];
+                }
 #pragma unroll
                 for (int k = 0; k < NV; k++) {
                     qi[u][k] = vload<VW>(reinterpret_cast<const float*>(qs + L.off[k]));
                     gi[u][k] = vload<VW>(reinterpret_cast<const float*>(gs + L.off[k]));
                 }
             }
-            if (a.ragged) {
+            if (!MH && a.ragged) {
 #pragma unroll
                 for (int u = 0; u < U; u++)
 #pragma unroll
@@ -439,7 +527,7 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
                     t[u] = vdot<VW>(gi[u][k], b[k], t[u]);
                 }
             }
-            group_sum2<G, U>(s, t, lig);
+            if constexpr (MH) head_sum2<G, U>(s, t, lig, a.gh); else group_sum2<G, U>(s, t, lig);
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const float p = j + u < n ? expf(s[u] * a.scale - lse[u]) : 0.f;
@@ -482,53 +570,98 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_fix_kernel(AttnArgs a, cons
 
 enum Kind { FWD, BWD_Q, BWD_KV };
 
-template <int KIND, int G, int NV, int VW>
+template <int KIND, int G, int NV, int VW, bool MH>
 void launch_seg(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
-    if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-    else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+    if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW, MH>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+    else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW, MH>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW, MH>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
 }
 
-template <int KIND, int VW>
+template <int KIND, int VW, bool MH>
 bool dispatch_gnv(int G, int NV, const AttnArgs& a, int64_t nblocks, hipStream_t st) {
     switch (G) {
-        case 8: launch_seg<KIND, 8, 1, VW>(a, nblocks, st); return true;
-        case 16: launch_seg<KIND, 16, 1, VW>(a, nblocks, st); return true;
-        case 32: launch_seg<KIND, 32, 1, VW>(a, nblocks, st); return true;
+        case 8: launch_seg<KIND, 8, 1, VW, MH>(a, nblocks, st); return true;
+        case 16: launch_seg<KIND, 16, 1, VW, MH>(a, nblocks, st); return true;
+        case 32: launch_seg<KIND, 32, 1, VW, MH>(a, nblocks, st); return true;
         case 64:
             switch (NV) {
-                case 1: launch_seg<KIND, 64, 1, VW>(a, nblocks, st); return true;
-                case 2: launch_seg<KIND, 64, 2, VW>(a, nblocks, st); return true;
-                case 3: launch_seg<KIND, 64, 3, VW>(a, nblocks, st); return true;
-                case 4: launch_seg<KIND, 64, 4, VW>(a, nblocks, st); return true;
+                case 1: launch_seg<KIND, 64, 1, VW, MH>(a, nblocks, st); return true;
+                case 2: launch_seg<KIND, 64, 2, VW, MH>(a, nblocks, st); return true;
+                case 3: launch_seg<KIND, 64, 3, VW, MH>(a, nblocks, st); return true;
+                case 4: launch_seg<KIND, 64, 4, VW, MH>(a, nblocks, st); return true;
             }
     }
     return false;
 }
 
 // the width one group can hold at vector width vw; SGCN_ERR_INVALID beyond it, before any HIP call
-int width_ok(const char* who, int32_t d, int vw) {
+int width_ok(const char* who, int32_t d, int vw, int32_t heads) {
+    if (heads > 1) {
+        SGCN_REQUIRE(((int64_t)d + vw - 1) / vw <= kMaxVec,
+                     "%s: d = %d is over the limit of %d columns at vector width %d (d <= 256 * VW; VW = 4 needs 16-byte aligned "
+                     "rows of every operand, VW = 2 8-byte aligned ones; with heads = %d VW must also divide d / heads = %d)",
+                     who, d, kMaxVec * vw, vw, heads, d / heads);
+        return SGCN_OK;
+    }
     SGCN_REQUIRE(((int64_t)d + vw - 1) / vw <= kMaxVec,
                  "%s: d = %d is over the limit of %d columns at vector width %d (d <= 256 * VW; VW = 4 needs 16-byte aligned "
                  "rows of every operand, VW = 2 8-byte aligned ones)", who, d, kMaxVec * vw, vw);
     return SGCN_OK;
 }
 
+int heads_ok(const char* who, int32_t d, int32_t heads) {
+    SGCN_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be one of 1/2/4/8 (got %d)", who, heads);
+    SGCN_REQUIRE(d % heads == 0, "%s: d = %d is not a multiple of heads = %d", who, d, heads);
+    return SGCN_OK;
+}
+
+// heads > 1: no vector may straddle two heads -- the widest of what the operands allow that divides d / heads
+int head_vw(int vw, int32_t d, int32_t heads) {
+    if (heads > 1)
+        while ((d / heads) % vw) vw >>= 1;
+    return vw;
+}
+
+template <int KIND, bool MH>
+bool dispatch_vw(int vw, int G, int NV, const AttnArgs& a, int64_t nblocks, hipStream_t st) {
+    if (vw == 4) return dispatch_gnv<KIND, 4, MH>(G, NV, a, nblocks, st);
+    if (vw == 2) return dispatch_gnv<KIND, 2, MH>(G, NV, a, nblocks, st);
+    return dispatch_gnv<KIND, 1, MH>(G, NV, a, nblocks, st);
+}
+
+template <bool MH>
+void launch_fix(int vw, dim3 grid, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
+    if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+    else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+    else hipLaunchKernelGGL((spattn_fix_kernel<1, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+}
+
 template <int KIND>
-int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, hipStream_t st) {
+int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, int32_t heads, hipStream_t st) {
     a.nseg = nrows;
     if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
     a.nvec = (a.d + vw - 1) / vw;
     a.ragged = a.d % vw != 0;
-    const int G = group_lanes(a.nvec);
-    const int NV = G == 64 ? (a.nvec + 63) / 64 : 1;
+    a.heads = heads;
+    int G, NV;
+    if (heads == 1) {
+        G = group_lanes(a.nvec);
+        NV = G == 64 ? (a.nvec + 63) / 64 : 1;
+        a.gh = G; a.nvh = a.nvec;
+    } else {
+        // the smallest group whose sub-groups of G / heads lanes hold a head's nvh vectors one per lane; past 64 lanes the
+        // sub-group is 64 / heads and a lane takes NV = ceil(nvh / Gh) <= 4 of them (heads * nvh <= 256, width_ok)
+        a.nvh = a.d / heads / vw;
+        int p = 1;
+        while (p < a.nvh) p <<= 1;
+        if (p * heads <= 64) { G = p * heads < 8 ? 8 : p * heads; NV = 1; }
+        else { G = 64; NV = (a.nvh + 64 / heads - 1) / (64 / heads); }
+        a.gh = G / heads;
+    }
     const int64_t nblocks = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
 
-    bool ok = false;
-    if (vw == 4) ok = dispatch_gnv<KIND, 4>(G, NV, a, nblocks, st);
-    else if (vw == 2) ok = dispatch_gnv<KIND, 2>(G, NV, a, nblocks, st);
-    else ok = dispatch_gnv<KIND, 1>(G, NV, a, nblocks, st);
+    const bool ok = heads == 1 ? dispatch_vw<KIND, false>(vw, G, NV, a, nblocks, st) : dispatch_vw<KIND, true>(vw, G, NV, a, nblocks, st);
     SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
     SGCN_HIP_TRY(hipGetLastError());
 
@@ -536,9 +669,8 @@ int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, in
         SGCN_REQUIRE(plan->nfix < (1ll << 31), "%s: too many split rows", who);
         dim3 grid((unsigned)plan->nfix);      // one workgroup per split row: nvec <= 256 = kBlock threads
         if constexpr (KIND == FWD) {
-            if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-            else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-            else hipLaunchKernelGGL((spattn_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+            if (heads == 1) launch_fix<false>(vw, grid, a, plan, st);
+            else launch_fix<true>(vw, grid, a, plan, st);
         } else {
             const float mul = KIND == BWD_Q ? a.scale : 1.f;
             if (vw == 4) hipLaunchKernelGGL((spattn_bwd_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
@@ -567,35 +699,40 @@ inline int64_t ceil4(int64_t d) { return (d + 3) / 4 * 4; }
 
 using namespace sgcn;
 
-extern "C" int sgcn_spattn_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
-                                   const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
-                                   float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
+
+// The three host bodies: the single-head exports call them with heads = 1, the _mh_ exports pass theirs on.
+static int spattn_fwd(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                      const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                      float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
     SGCN_REQUIRE(M >= 0 && K >= 0, "spattn: negative size");
     SGCN_REQUIRE(d > 0, "spattn: d must be positive (got %d)", d);
+    { const int rc = heads_ok("spattn", d, heads); if (rc) return rc; }
     SGCN_REQUIRE(rowptr && C && (Q || M == 0) && (B || K == 0), "spattn: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldc >= d, "spattn: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn: scale must be finite");
-    const int64_t ldw = ceil4(d) + 4;            // a slot: the accumulator on a 16-byte pitch, then one vector (m, l, -, -)
+    // a slot: the accumulator on a 16-byte pitch, then one vector (m, l, -, -) per head
+    const int64_t ldw = ceil4(d) + 4 * (int64_t)heads;
     if (plan) { const int rc = plan_ok("spattn", plan, M, ldw); if (rc) return rc; }
     const bool split = plan && plan->nfix > 0;
-    const int vw = pick_vw(d, {Q, B, C, split ? (const void*)plan->dev_ws : nullptr}, {ldq, ldb, ldc});
-    { const int rc = width_ok("spattn", d, vw); if (rc) return rc; }
+    const int vw = head_vw(pick_vw(d, {Q, B, C, split ? (const void*)plan->dev_ws : nullptr}, {ldq, ldb, ldc}), d, heads);
+    { const int rc = width_ok("spattn", d, vw, heads); if (rc) return rc; }
     if (M == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = rowptr; a.col = col; a.own = Q; a.ldown = ldq; a.gat = B; a.ldgat = ldb; a.out = C; a.ldo = ldc;
     a.lse_out = lse; a.scale = scale; a.d = d;
     if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
-    return run<FWD>(a, "spattn", M, plan, vw, (hipStream_t)stream);
+    return run<FWD>(a, "spattn", M, plan, vw, heads, (hipStream_t)stream);
 }
 
-extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
-                                         const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
-                                         const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
-                                         float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
-                                         int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
+static int spattn_bwd_q(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                        const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                        const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
+                        float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
+                        int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
     SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_q: negative size");
     SGCN_REQUIRE(d > 0, "spattn_bwd_q: d must be positive (got %d)", d);
+    { const int rc = heads_ok("spattn_bwd_q", d, heads); if (rc) return rc; }
     SGCN_REQUIRE(rowptr && dQ && ((Q && G && C && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_q: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && ldc >= d && lddq >= d, "spattn_bwd_q: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_q: scale must be finite");
@@ -604,9 +741,9 @@ extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* c
     const int64_t ldw = ceil4(d);
     if (plan) { const int rc = plan_ok("spattn_bwd_q", plan, M, ldw); if (rc) return rc; }
     const bool split = plan && plan->nfix > 0;
-    const int vw = pick_vw(d, {Q, B, G, C, dQ, with_add ? add : nullptr, split ? (const void*)plan->dev_ws : nullptr},
-                           {ldq, ldb, ldg, ldc, lddq, with_add ? ldadd : lddq});
-    { const int rc = width_ok("spattn_bwd_q", d, vw); if (rc) return rc; }
+    const int vw = head_vw(pick_vw(d, {Q, B, G, C, dQ, with_add ? add : nullptr, split ? (const void*)plan->dev_ws : nullptr},
+                                   {ldq, ldb, ldg, ldc, lddq, with_add ? ldadd : lddq}), d, heads);
+    { const int rc = width_ok("spattn_bwd_q", d, vw, heads); if (rc) return rc; }
     if (M == 0) return SGCN_OK;
 
     AttnArgs a{};
@@ -614,16 +751,17 @@ extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* c
     a.Cf = C; a.ldcf = ldc; a.lse = lse; a.delta_out = delta; a.out = dQ; a.ldo = lddq; a.scale = scale; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
     if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
-    return run<BWD_Q>(a, "spattn_bwd_q", M, plan, vw, (hipStream_t)stream);
+    return run<BWD_Q>(a, "spattn_bwd_q", M, plan, vw, heads, (hipStream_t)stream);
 }
 
-extern "C" int sgcn_spattn_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d,
-                                          const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
-                                          const float* G, int64_t ldg, const float* lse, const float* delta,
-                                          float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
-                                          const sgcn_plan_t* t_plan, void* stream) {
+static int spattn_bwd_kv(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d, int32_t heads,
+                         const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                         const float* G, int64_t ldg, const float* lse, const float* delta,
+                         float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
+                         const sgcn_plan_t* t_plan, void* stream) {
     SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_kv: negative size");
     SGCN_REQUIRE(d > 0, "spattn_bwd_kv: d must be positive (got %d)", d);
+    { const int rc = heads_ok("spattn_bwd_kv", d, heads); if (rc) return rc; }
     SGCN_REQUIRE(t_rowptr && dB && ((Q && G && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_kv: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && lddb >= d, "spattn_bwd_kv: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_kv: scale must be finite");
@@ -632,9 +770,9 @@ extern "C" int sgcn_spattn_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t
     const int64_t ldw = ceil4(d);
     if (t_plan) { const int rc = plan_ok("spattn_bwd_kv", t_plan, K, ldw); if (rc) return rc; }
     const bool split = t_plan && t_plan->nfix > 0;
-    const int vw = pick_vw(d, {Q, B, G, dB, with_add ? add : nullptr, split ? (const void*)t_plan->dev_ws : nullptr},
-                           {ldq, ldb, ldg, lddb, with_add ? ldadd : lddb});
-    { const int rc = width_ok("spattn_bwd_kv", d, vw); if (rc) return rc; }
+    const int vw = head_vw(pick_vw(d, {Q, B, G, dB, with_add ? add : nullptr, split ? (const void*)t_plan->dev_ws : nullptr},
+                                   {ldq, ldb, ldg, lddb, with_add ? ldadd : lddb}), d, heads);
+    { const int rc = width_ok("spattn_bwd_kv", d, vw, heads); if (rc) return rc; }
     if (K == 0) return SGCN_OK;
 
     AttnArgs a{};
@@ -642,5 +780,53 @@ extern "C" int sgcn_spattn_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t
     a.lse = lse; a.delta = delta; a.out = dB; a.ldo = lddb; a.scale = scale; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
     if (split) { a.ws = t_plan->dev_ws; a.ldw = ldw; }
-    return run<BWD_KV>(a, "spattn_bwd_kv", K, t_plan, vw, (hipStream_t)stream);
+    return run<BWD_KV>(a, "spattn_bwd_kv", K, t_plan, vw, heads, (hipStream_t)stream);
+}
+
+extern "C" int sgcn_spattn_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
+                                   const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                   float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
+    return spattn_fwd(rowptr, col, M, K, d, 1, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
+}
+
+extern "C" int sgcn_spattn_mh_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                                      const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                      float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
+    return spattn_fwd(rowptr, col, M, K, d, heads, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
+}
+
+extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
+                                         const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                         const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
+                                         float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
+                                         int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
+    return spattn_bwd_q(rowptr, col, M, K, d, 1, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd,
+                        add_rows, plan, stream);
+}
+
+extern "C" int sgcn_spattn_mh_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
+                                            int32_t heads, const float* Q, int64_t ldq, const float* B, int64_t ldb,
+                                            float scale, const float* G, int64_t ldg, const float* C, int64_t ldc,
+                                            const float* lse, float* delta, float* dQ, int64_t lddq, const float* add,
+                                            int64_t ldadd, int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
+    return spattn_bwd_q(rowptr, col, M, K, d, heads, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd,
+                        add_rows, plan, stream);
+}
+
+extern "C" int sgcn_spattn_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d,
+                                          const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                                          const float* G, int64_t ldg, const float* lse, const float* delta,
+                                          float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
+                                          const sgcn_plan_t* t_plan, void* stream) {
+    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, 1, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add, ldadd,
+                         add_rows, t_plan, stream);
+}
+
+extern "C" int sgcn_spattn_mh_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d,
+                                             int32_t heads, const float* Q, int64_t ldq, const float* B, int64_t ldb,
+                                             float scale, const float* G, int64_t ldg, const float* lse, const float* delta,
+                                             float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
+                                             const sgcn_plan_t* t_plan, void* stream) {
+    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, heads, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add, ldadd,
+                         add_rows, t_plan, stream);
 }

@@ -184,6 +184,30 @@ def check_attention(flags=None):
     return True, scale
 
 
+ATTN_HEADS = (1, 2, 4, 8)
+
+
+def check_attn_heads(flags=None):
+    """--attn_heads as an int, refused where the kernels have no such form (a head is an aligned power-of-two share of a
+    lane group: 1/2/4/8) or where nothing would read it.  Needs no device; called right after check_attention.  Whether
+    the heads divide a layer's width is known once the widths are (train.Trainer, layers.PlainAggregator)."""
+    f = FLAGS if flags is None else flags
+    heads = getattr(f, 'attn_heads', 1)
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads not in ATTN_HEADS:
+        raise ValueError("--attn_heads must be one of 1/2/4/8, got %r" % (heads,))
+    if heads != 1 and getattr(f, 'aggregator', 'sum') != 'attn':
+        raise ValueError("--attn_heads needs --aggregator attn: it is the number of attention heads, and no other aggregator "
+                         "has any")
+    return heads
+
+
+def attn_heads_divide(heads, width, what):
+    """ValueError naming the layer and its width unless the heads cut it evenly."""
+    if width % heads:
+        raise ValueError("--attn_heads %d does not divide the input width of %s (%d columns): every head is an equal "
+                         "slice of the columns" % (heads, what, width))
+
+
 def full_batch_bf16(flags=None):
     """--full_batch_dtype as a bool (bfloat16 operand?)."""
     return getattr(FLAGS if flags is None else flags, 'full_batch_dtype', 'fp32') == 'bf16'
@@ -497,38 +521,41 @@ class StaticMatrix(object):
         if self.edge is not None:
             raise ValueError("attention has no edge-masked form")
 
-    def attn_product(self, x, scale, out=None, want_lse=True):
+    def attn_product(self, x, scale, out=None, want_lse=True, heads=1):
         """(out, lse) of ops.spattn over this matrix's PATTERN with the queries x[:M]: out[i] = the rows of ``x`` that row i
         stores an entry for, weighed by softmax_j(scale * <x[i], x[j]>); lse the rows' log-sum-exp for ``attn_backward``
         (None with ``want_lse=False``).  Reads the row kernel's CSR -- pattern and segment plan -- only.  The kernel holds
         d <= 256 * VW columns: an operand whose alignment would push d over that (602-wide features on a pitch of 602
         floats: VW = 2) is staged once into an aligned scratch table, an ``out`` view of that kind is computed aligned and
-        copied."""
+        copied.  ``heads``: ops.spattn's; lse is then (M, heads), and an operand is staged where ITS alignment, not the head
+        width, is what narrows the vectors (staging cannot widen what d / heads caps)."""
         self._attn_refuse(x)
         d = int(x.shape[1])
-        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out):
-            if ops.attn_vw(d, x) < 4:
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out, heads=heads):
+            best = ops.attn_vw(d, heads=heads)            # what aligned operands would get
+            if ops.attn_vw(d, x, heads=heads) < best:
                 x = self._attn_staged('x', x, d)
-            if out is not None and ops.attn_vw(d, out) < 4:
-                res, lse = ops.spattn(self.rows_csr, x, scale=scale, want_lse=want_lse,
+            if out is not None and ops.attn_vw(d, out, heads=heads) < best:
+                res, lse = ops.spattn(self.rows_csr, x, scale=scale, want_lse=want_lse, heads=heads,
                                       out=self._attn_staged('out', out, d, fill=False))
                 out.copy_(res)
                 return out, lse
-        return ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse)
+        return ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse, heads=heads)
 
-    def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0):
+    def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1):
         """Called on the matrix whose ``attn_product(x, scale)`` gave ``out_fwd`` and ``lse``: the gradient with respect to
         ``x`` (as keys / values AND as queries) for g = dL/dout, + add on the first ``add_rows`` rows -- ops.spattn_bwd, a
         gather over this matrix's pattern and one over its transpose's.  Operands are staged as in ``attn_product``."""
         self._attn_refuse(x)
         d = int(x.shape[1])
         ops_ = dict(x=x, g=g, out_fwd=out_fwd, add=add)
-        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, add):
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, add, heads=heads):
+            best = ops.attn_vw(d, heads=heads)
             for role, t in list(ops_.items()):
-                if t is not None and ops.attn_vw(d, t) < 4:
+                if t is not None and ops.attn_vw(d, t, heads=heads) < best:
                     ops_[role] = self._attn_staged(role, t, d)
         return ops.spattn_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], None, ops_['g'], ops_['out_fwd'], lse, scale,
-                              add=ops_['add'], add_rows=add_rows)[1]
+                              add=ops_['add'], add_rows=add_rows, heads=heads)[1]
 
     def describe(self, d):
         """What train.pp_products records of a product of width d: where the plan came from, the sweep clock (the column

@@ -422,14 +422,18 @@ class PlainAggregator(Layer):
                 raise RuntimeError("--aggregator attn runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
                                    "minibatch adjacency has no attention kernel")
             want = bool(getattr(self.model, 'is_training', True))
-            scale = float(FLAGS.attn_scale) if float(FLAGS.attn_scale) > 0 else float(d) ** -0.5
+            # --attn_heads H: every head an attention over its own d / H columns, the default scale 1 / sqrt(d / H)
+            heads = self._heads = int(getattr(FLAGS, 'attn_heads', 1))
+            from .full_batch import attn_heads_divide
+            attn_heads_divide(heads, d, self.name)
+            scale = float(FLAGS.attn_scale) if float(FLAGS.attn_scale) > 0 else float(d // heads) ** -0.5
             self._x, self._scale = (x if want else None), scale
             if not concat:
-                self._out, self._lse = A.attn_product(x, scale, want_lse=want)
+                self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads)
                 return self._out
             out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
             out[:, :d] = x[:n1]
-            self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want)
+            self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads)
             return out
         if not concat:
             return A.product(x)
@@ -457,8 +461,9 @@ class PlainAggregator(Layer):
         if self._attn:
             # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
             if not self._concat:
-                return A.attn_backward(self._x, g, self._out, self._lse, self._scale)
-            return A.attn_backward(self._x, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d], add_rows=A.shape[0])
+                return A.attn_backward(self._x, g, self._out, self._lse, self._scale, heads=self._heads)
+            return A.attn_backward(self._x, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d], add_rows=A.shape[0],
+                                   heads=self._heads)
         if not self._concat:
             return A.transpose.product(g)
         # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep

@@ -327,13 +327,17 @@ def spmax_bwd(At, g, arg, out=None, add=None, add_rows=0):
 ATTN_MAX_VECTORS = 256       # sgcn_spattn.hip: one lane group holds a whole row, 64 lanes x 4 vectors of VW elements
 
 
-def attn_vw(d, *tensors):
+ATTN_HEADS = (1, 2, 4, 8)    # sgcn_spattn_mh_*: a head is an aligned power-of-two range of a group's lanes, the smallest group 8
+
+
+def attn_vw(d, *tensors, heads=1):
     """The vector width sgcn_spattn_* would pick for width ``d`` and these 2-D operands (include/sgcn.h: the row kernels'
     rule): 4 with 16-byte aligned bases and pitches that are multiples of 4, 2 with 8-byte / multiples of 2, else 1.  The
-    kernels hold d <= ATTN_MAX_VECTORS * VW columns."""
+    kernels hold d <= ATTN_MAX_VECTORS * VW columns.  ``heads`` > 1: a vector never straddles two heads, so the width
+    must divide d / heads as well."""
     for vw in (4, 2):
         span = (d + vw - 1) // vw * vw
-        ok = True
+        ok = heads == 1 or (d // heads) % vw == 0
         for t in tensors:
             if t is None:
                 continue
@@ -346,24 +350,38 @@ def attn_vw(d, *tensors):
     return 1
 
 
-def _attn_out(rows, d, device):
+def _attn_out(rows, d, device, heads=1):
     """A fresh (rows, d) fp32 result of the attention kernels: contiguous, unless that pitch alone would narrow the vectors
-    so far that d no longer fits one lane group -- then on a 16-byte pitch."""
-    if d > ATTN_MAX_VECTORS * (4 if d % 4 == 0 else 2 if d % 2 == 0 else 1):
+    so far that d no longer fits one lane group -- then on a 16-byte pitch.  (With ``heads`` > 1 the head width d / heads
+    caps the vectors as well, whatever the pitch.)"""
+    dh = d // heads
+    cap = 4 if heads == 1 or dh % 4 == 0 else 2 if dh % 2 == 0 else 1
+    if d > ATTN_MAX_VECTORS * min(cap, 4 if d % 4 == 0 else 2 if d % 2 == 0 else 1):
         return _pitched_out(rows, d, device)
     return torch.empty((rows, d), dtype=torch.float32, device=device)
 
 
-def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True):
+def _attn_heads(d, heads):
+    heads = int(heads)
+    if heads not in ATTN_HEADS:
+        raise ValueError("heads must be one of %s, got %r" % ('/'.join(map(str, ATTN_HEADS)), heads))
+    if d % heads:
+        raise ValueError("the width %d is not a multiple of heads = %d" % (d, heads))
+    return heads
+
+
+def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True, heads=1):
     """(out, lse): softmax dot-product attention over the stored pattern of the DeviceCSR ``A`` (M x K, unique column ids
     per row; stored values are not read) -- sgcn_spattn_csr_f32.  With s_ij = scale * <q[i], x[j]> over the entries j of
     row i: lse[i] = log sum_j exp(s_ij), out[i] = sum_j exp(s_ij - lse[i]) x[j]; an empty row gives +0.0 and -inf.
     ``q=None`` means x[:M].  ``out`` may be a pitched (M, >= d) view.  ``want_lse=False`` (an evaluation): lse is None,
-    nothing is allocated for it."""
+    nothing is allocated for it.  ``heads`` = H in 1/2/4/8 (sgcn_spattn_mh_csr_f32): head h is the columns
+    [h d/H, (h+1) d/H), every head an attention of its own over the same pattern, and lse is (M, H) for H > 1."""
     check_unique_cols(A)
     M, K = A.shape
     bptr, ldb = _rows2d(x, "x")
     d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
     if x.shape[0] < K:
         raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
     if q is None:
@@ -375,29 +393,31 @@ def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True):
         if q.shape[0] < M or q.shape[1] != d:
             raise ValueError("q has shape %s, need (>=%d, %d)" % (tuple(q.shape), M, d))
     if out is None:
-        out = _attn_out(M, d, x.device)
+        out = _attn_out(M, d, x.device, heads)
     cptr, ldc = _rows2d(out, "out")
     if out.shape[0] != M or out.shape[1] < d:
         raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
-    lse = torch.empty((M,), dtype=torch.float32, device=x.device) if want_lse else None
-    plan = A.plan.struct(d + 4) if A.plan is not None else None          # (a forward slot: the row + one vector for (m, l))
-    check(lib.sgcn_spattn_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, qptr, ldq, bptr, ldb, float(scale), cptr, ldc,
-                                  _ptr(lse), C.byref(plan) if plan is not None else None, _stream()))
+    lse = torch.empty((M,) if heads == 1 else (M, heads), dtype=torch.float32, device=x.device) if want_lse else None
+    # (a forward slot: the row + one vector for (m, l) per head)
+    plan = A.plan.struct((d + 3) // 4 * 4 + 4 * heads) if A.plan is not None else None
+    check(lib.sgcn_spattn_mh_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, qptr, ldq, bptr, ldb, float(scale),
+                                     cptr, ldc, _ptr(lse), C.byref(plan) if plan is not None else None, _stream()))
     return out, lse
 
 
-def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0):
+def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1):
     """(dq, dx), the gradient of ``spattn(A, x, q, scale)`` for g = dL/dout, from the forward's ``out_fwd`` and ``lse`` --
     sgcn_spattn_csr_bwd_q_f32 over ``A``, then sgcn_spattn_csr_bwd_kv_f32 over ``At``, the DeviceCSR of the TRANSPOSED
     pattern (ops.transpose_host: source rows ascending).  Nothing nnz-sized is stored, no atomics: bitwise reproducible.
     With an explicit ``q``: dq (M x d, + add on its first ``add_rows`` rows) and dx = dB (K x d) separately.  With
     ``q=None`` (the queries are x[:M]): (None, dx) with dx = dB + [dQ + add ; 0] -- the first launch's result is the second
-    one's addend, so the sum costs no extra pass."""
+    one's addend, so the sum costs no extra pass.  ``heads`` as in ``spattn``, ``lse`` of the shape it returned."""
     M, K = A.shape
     if tuple(At.shape) != (K, M):
         raise ValueError("At has shape %s, the transpose of %s is needed" % (tuple(At.shape), tuple(A.shape)))
     bptr, ldb = _rows2d(x, "x")
     d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
     if x.shape[0] < K:
         raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
     if q is None:
@@ -413,23 +433,28 @@ def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0):
     if tuple(g.shape) != (M, d) or out_fwd.shape[0] != M or out_fwd.shape[1] < d:
         raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (M, d, tuple(g.shape), tuple(out_fwd.shape)))
     _dev(lse, torch.float32, "lse")
-    if lse.dim() != 1 or lse.shape[0] != M or not lse.is_contiguous():
-        raise ValueError("lse must be a contiguous vector of %d floats" % M)
+    if heads == 1:
+        if lse.dim() != 1 or lse.shape[0] != M or not lse.is_contiguous():
+            raise ValueError("lse must be a contiguous vector of %d floats" % M)
+    elif tuple(lse.shape) != (M, heads) or not lse.is_contiguous():
+        raise ValueError("lse must be a contiguous (%d, %d) table of floats" % (M, heads))
     aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
     add_rows = int(add_rows) if add is not None else 0
-    delta = torch.empty((M,), dtype=torch.float32, device=x.device)
-    dq = _attn_out(M, d, x.device)
-    dx = _attn_out(K, d, x.device)
+    delta = torch.empty((M * heads,), dtype=torch.float32, device=x.device)
+    dq = _attn_out(M, d, x.device, heads)
+    dx = _attn_out(K, d, x.device, heads)
     plan = A.plan.struct(d) if A.plan is not None else None
-    check(lib.sgcn_spattn_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, qptr, ldq, bptr, ldb, float(scale),
-                                        gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), _rows2d(dq, "dq")[1],
-                                        aptr, ldadd, add_rows, C.byref(plan) if plan is not None else None, _stream()))
+    check(lib.sgcn_spattn_mh_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, qptr, ldq, bptr, ldb, float(scale),
+                                           gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
+                                           _rows2d(dq, "dq")[1], aptr, ldadd, add_rows,
+                                           C.byref(plan) if plan is not None else None, _stream()))
     tplan = At.plan.struct(d) if At.plan is not None else None
     fused = q is None
-    check(lib.sgcn_spattn_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, qptr, ldq, bptr, ldb, float(scale),
-                                         gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(), _rows2d(dx, "dx")[1],
-                                         dq.data_ptr() if fused else None, _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0,
-                                         C.byref(tplan) if tplan is not None else None, _stream()))
+    check(lib.sgcn_spattn_mh_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, qptr, ldq, bptr, ldb,
+                                            float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
+                                            _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
+                                            _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0,
+                                            C.byref(tplan) if tplan is not None else None, _stream()))
     return (None if fused else dq), dx
 
 

@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
-from .full_batch import (StaticBatch, StaticMatrix, check_aggregator, check_attention, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
+from .full_batch import (StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_heads,check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
@@ -237,6 +237,8 @@ class Trainer(object):
         self.max_aggregator = check_aggregator()
         # (--aggregator attn likewise; --attn_scale negative, non-finite, or set without attn: too)
         self.attn_aggregator, self.attn_scale = check_attention()
+        # (--attn_heads outside 1/2/4/8, or set without attn: too; whether it divides the widths is checked once they are known)
+        self.attn_heads = check_attn_heads()
         # (--feature_dtype bf16 without the bf16 GEMMs or without a full-graph mode: too; which model's table it selects)
         self.feature_bf16 = check_feature_dtype()
         # (--history_init exact / --history_refresh / --history_error without a history, with two of them, on several ranks: too)
@@ -279,6 +281,13 @@ class Trainer(object):
         self.multitask = multitask = FLAGS.dataset == 'ppi'
         L = FLAGS.num_layers - 1 if FLAGS.preprocess else FLAGS.num_layers
         test_L = FLAGS.num_layers - 1 if FLAGS.test_preprocess else FLAGS.num_layers
+        if self.attn_heads > 1:
+            # every head is an equal slice of an aggregation layer's input: the feature width where a model aggregates the
+            # features itself (--nopreprocess / --notest_preprocess), hidden1 for every later aggregation layer
+            if not (FLAGS.preprocess and FLAGS.test_preprocess):
+                attn_heads_divide(self.attn_heads, int(features.shape[1]), "the first aggregation layer (the feature width)")
+            if FLAGS.num_layers > 1:
+                attn_heads_divide(self.attn_heads, int(FLAGS.hidden1), "the aggregation layers behind a dense layer (--hidden1)")
         self.placeholders = placeholders = make_placeholders(max(L, test_L), labels.shape[1])
 
         t = time()
