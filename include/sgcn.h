@@ -57,7 +57,8 @@ const char* sgcn_last_error(void);
  *       edge mask -- sgcn_edge_revalue_f32; the element-wise neighbour maximum over a CSR pattern and its backward --
  *       sgcn_spmax_csr_f32 / sgcn_spmax_csr_bwd_f32; softmax dot-product attention over a CSR pattern and its backward --
  *       sgcn_spattn_csr_f32 / sgcn_spattn_csr_bwd_q_f32 / sgcn_spattn_csr_bwd_kv_f32; their multi-head forms --
- *       sgcn_spattn_mh_csr_f32 / sgcn_spattn_mh_csr_bwd_q_f32 / sgcn_spattn_mh_csr_bwd_kv_f32) */
+ *       sgcn_spattn_mh_csr_f32 / sgcn_spattn_mh_csr_bwd_q_f32 / sgcn_spattn_mh_csr_bwd_kv_f32; their forms with dropout on
+ *       the coefficients -- sgcn_spattn_drop_csr_f32 / sgcn_spattn_drop_csr_bwd_q_f32 / sgcn_spattn_drop_csr_bwd_kv_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -589,6 +590,49 @@ int sgcn_spattn_mh_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* de
                                   float* dev_dB, int64_t lddb,
                                   const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
                                   const sgcn_plan_t* t_plan /* nullable */, void* stream);
+
+/* ---- dropout on the attention coefficients (--attn_dropout; additive, still v16) -------------------------------------------
+ * The three multi-head calls with `float keep, uint32_t key` inserted directly after heads: every vertex attends to a random
+ * subset of its neighbours, as in GAT and Transformer attention.  The mask is a counter-based hash, a pure function of
+ * (row of P, column of P, head, key), so it is never stored: all three launches recompute it per entry.  With fmix32 the
+ * murmur3 finaliser of sgcn_dropout_t, all arithmetic mod 2^32, i the ROW and j the COLUMN of the pattern P in every
+ * launch (the _bwd_kv launch walks P^T: there its own row is j and the gathered id is i), h the head (0 for heads = 1):
+ *     pair(i, j)    = fmix32(fmix32(i * 0x9E3779B1 + key) + j * 0x85EBCA77)
+ *     kept(i, j, h) iff fmix32(pair(i, j) + h * 0x27D4EB2F) < thr          thr from keep exactly as for sgcn_dropout_t
+ *     mk_ijh        = kept ? 1.0f / keep : 0                               (the fp32 quotient, computed once on the host)
+ * pair(i, j) is NOT symmetric, the diagonal entry is not exempt, and the heads of one entry are masked independently.
+ *   forward   s, m, l, lse and p_ij are those of the calls above: the softmax runs over ALL stored entries and the mask comes
+ *             after it (l += p for every entry), so lse under dropout is bit for bit the lse without it.
+ *             C[i]    = sum_j (p_ij * mk_ij) B[j]         (acc += (p * mk) * b; a row whose entries are all dropped: C = 0)
+ *   backward  delta_i = <G[i], C[i]>                      (C the MASKED output; equal to sum_j p_ij mk_ij t_ij, t_ij = <G[i], B[j]>)
+ *             e_ij    = p_ij (mk_ij * t_ij - delta_i)
+ *             dQ[i]   = scale * sum_j e_ij B[j]
+ *             dB[j]   = sum_i ( (p_ij * mk_ij) G[i] + scale e_ij Q[i] )
+ * (the identity behind delta: dL/ds_ij = p_ij (mk_ij t_ij - sum_k p_ik mk_ik t_ik), and the sum is <G[i], C[i]>.)  The
+ * pads of a chunk keep weight exactly 0 whatever their mask says; the fix-up launches are unchanged, the slots already
+ * holding masked partial sums.  key = the dropout key of (seed, SGCN_ATTN_SITE + layer index, step) with the step counter
+ * that keys the activation dropout of the same step.
+ *
+ * keep must be finite and in (0, 1] -- SGCN_ERR_INVALID otherwise, before any HIP call, beside everything the multi-head
+ * calls refuse.  keep == 1 runs the kernels of the calls above (the same instantiations, the same bits); keep < 1 runs their
+ * dropout instantiations. */
+#define SGCN_ATTN_SITE 0x4154544E
+int sgcn_spattn_drop_csr_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                             float keep, uint32_t key, const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb,
+                             float scale, float* dev_C, int64_t ldc, float* dev_lse /* nullable; M x heads */,
+                             const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spattn_drop_csr_bwd_q_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d,
+                                   int32_t heads, float keep, uint32_t key, const float* dev_Q, int64_t ldq,
+                                   const float* dev_B, int64_t ldb, float scale, const float* dev_G, int64_t ldg,
+                                   const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dQ,
+                                   int64_t lddq, const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                                   const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spattn_drop_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t_row, int32_t K, int32_t M, int32_t d,
+                                    int32_t heads, float keep, uint32_t key, const float* dev_Q, int64_t ldq,
+                                    const float* dev_B, int64_t ldb, float scale, const float* dev_G, int64_t ldg,
+                                    const float* dev_lse, const float* dev_delta, float* dev_dB, int64_t lddb,
+                                    const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                                    const sgcn_plan_t* t_plan /* nullable */, void* stream);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-

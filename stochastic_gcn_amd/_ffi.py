@@ -176,6 +176,15 @@ SIGNATURES = {
     "sgcn_spattn_mh_csr_bwd_kv_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
                                                 C.c_float, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int32,
                                                 C.POINTER(Plan), P]),
+    # their forms with dropout on the coefficients (--attn_dropout): `keep`, `key` directly after heads
+    "sgcn_spattn_drop_csr_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P,
+                                           C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, C.POINTER(Plan), P]),
+    "sgcn_spattn_drop_csr_bwd_q_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P,
+                                                 C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, C.c_int64, P, P, P,
+                                                 C.c_int64, P, C.c_int64, C.c_int32, C.POINTER(Plan), P]),
+    "sgcn_spattn_drop_csr_bwd_kv_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P,
+                                                  C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, P, P, C.c_int64, P,
+                                                  C.c_int64, C.c_int32, C.POINTER(Plan), P]),
     "sgcn_coll_available": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgcn_coll_retain": (C.c_int, []),
     "sgcn_coll_abort": (C.c_int, []),

@@ -28,6 +28,16 @@
 // below Gh stay inside an aligned sub-group; Gh = 1 moves nothing), and the running (m, l, acc) -- per lane already --
 // is simply each head's own: lanes of different heads may take the `maximum rises` branch differently, which is plain
 // divergence, since nothing inside it crosses lanes.
+//
+// Dropout on the coefficients (--attn_dropout, the DR = true instantiations; keep == 1 runs the DR = false ones, which are the
+// kernels above unchanged): entry (i, j) of head h is kept iff fmix32(pair(i, j) + h * 0x27D4EB2F) < thr, with
+// pair(i, j) = fmix32(fmix32(i * 0x9E3779B1 + key) + j * 0x85EBCA77), i the row of P and j its column in all three launches
+// (bwd_kv walks P^T: its own row is j, the gathered id i).  A kept coefficient is scaled by mk = 1 / keep AFTER the softmax:
+// m, l and lse never see the mask; the forward adds (p * mk) * B[j], the backward uses mk * t_ij in e_ij and p * mk on
+// G[i].  The mask is a pure function of (i, j, h, key), recomputed in each launch (drop_bits: by the lane that fetched the
+// entry's id, once for all heads): nothing is stored for it.  DR is
+// a template parameter, not a run-time branch, and the mask travels in a second kernel argument that the DR = false
+// kernels never read: their device code is, instruction for instruction, the code they had before DR existed.
 #include <cmath>
 #include "sgcn_dev.h"
 
@@ -71,6 +81,27 @@ struct AttnArgs {
     int32_t gh;              // lanes per head, G / H (a power of two)
     int32_t nvh;             // vectors per head, dh / VW
 };
+
+// the coefficient mask (include/sgcn.h, attention dropout), a second kernel argument: AttnArgs keeps its layout, and the
+// kernels without dropout do not read this one
+struct AttnDrop {
+    uint32_t key, thr;       // kept iff hash < thr
+    float mk;                // 1 / keep
+};
+// The kept bits of entry (i, j) of P: bit h is set iff head h keeps it.  A lane hashes the ONE entry whose id it fetched for the
+// chunk of G entries -- all heads of it, 1 + H finalisers per G entries and lane -- and the bits travel with the id's
+// broadcast: per entry a lane adds one move and one bit test, not two finalisers.
+template <bool MH>
+__device__ __forceinline__ int drop_bits(const AttnDrop& a, int i, int j, int heads) {
+    const uint32_t pair = fmix32(fmix32((uint32_t)i * 0x9E3779B1u + a.key) + (uint32_t)j * 0x85EBCA77u);
+    if constexpr (!MH) return fmix32(pair) < a.thr;
+    else {
+        int bits = 0;
+        for (int h = 0; h < heads; h++) bits |= (int)(fmix32(pair + (uint32_t)h * 0x27D4EB2Fu) < a.thr) << h;
+        return bits;
+    }
+}
+__device__ __forceinline__ float drop_mk(const AttnDrop& a, int bits, int head) { return (bits >> head) & 1 ? a.mk : 0.f; }
 
 template <int G>
 __device__ __forceinline__ bool my_segment(const AttnArgs& a, int& row, int& start, int& end, int& slot) {
@@ -224,8 +255,8 @@ template <int NV>
 struct Unroll { static constexpr int fwd = 4, bwd_q = NV >= 3 ? 2 : 4, bwd_kv = NV >= 2 ? 2 : 4; };
 
 // ---- forward ------------------------------------------------------------------------------------------------------------
-template <int G, int NV, int VW, bool MH>
-__global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
+template <int G, int NV, int VW, bool MH, bool DR>
+__global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a, AttnDrop dm) {
     typedef typename Vec<VW>::type VT;
     constexpr int U = Unroll<NV>::fwd;
     const int lig = threadIdx.x & (G - 1);
@@ -245,13 +276,17 @@ __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
         const int n = min(G, end - p0);
         int mycol = 0;
         if (lig < n) mycol = a.col[p0 + lig];
+        [[maybe_unused]] int mybits = 0;
+        if constexpr (DR) mybits = drop_bits<MH>(dm, row, mycol, a.heads);
         for (int j = 0; j < n; j += U) {
             VT b[U][NV];
             float s[U];
+            [[maybe_unused]] float mk[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int c = bcast_i<G>(mycol, min(j + u, n - 1));
                 const char* src = Bb + (int64_t)c * ldb_bytes;   // G == 64: scalar base
+                if constexpr (DR) mk[u] = drop_mk(dm, bcast_i<G>(mybits, min(j + u, n - 1)), L.head);
 #pragma unroll
                 for (int k = 0; k < NV; k++) b[u][k] = vload<VW>(reinterpret_cast<const float*>(src + L.off[k]));
             }
@@ -285,8 +320,10 @@ __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a) {
             for (int u = 0; u < U; u++) {
                 const float p = expf(s[u] - m);
                 l += p;
+                float w = p;                   // (a chunk pad: p = exp(-inf) = 0, so its weight is 0 whatever its mask)
+                if constexpr (DR) w = p * mk[u];
 #pragma unroll
-                for (int k = 0; k < NV; k++) acc[k] = vfma<VW>(p, b[u][k], acc[k]);
+                for (int k = 0; k < NV; k++) acc[k] = vfma<VW>(w, b[u][k], acc[k]);
             }
         }
     }
@@ -376,8 +413,8 @@ __device__ __forceinline__ void bwd_store(const AttnArgs& a, int row, int vi, ty
 }
 
 // over P: delta_i and dQ[i] = scale * sum_j e_ij B[j]
-template <int G, int NV, int VW, bool MH>
-__global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
+template <int G, int NV, int VW, bool MH, bool DR>
+__global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a, AttnDrop dm) {
     typedef typename Vec<VW>::type VT;
     constexpr int U = Unroll<NV>::bwd_q;
     const int lig = threadIdx.x & (G - 1);
@@ -418,13 +455,17 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
         const int n = min(G, end - p0);
         int mycol = 0;
         if (lig < n) mycol = a.col[p0 + lig];
+        [[maybe_unused]] int mybits = 0;
+        if constexpr (DR) mybits = drop_bits<MH>(dm, row, mycol, a.heads);
         for (int j = 0; j < n; j += U) {
             VT b[U][NV];
             float s[U], t[U];
+            [[maybe_unused]] float mk[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int c = bcast_i<G>(mycol, min(j + u, n - 1));
                 const char* src = Bb + (int64_t)c * ldb_bytes;
+                if constexpr (DR) mk[u] = drop_mk(dm, bcast_i<G>(mybits, min(j + u, n - 1)), L.head);
 #pragma unroll
                 for (int k = 0; k < NV; k++) b[u][k] = vload<VW>(reinterpret_cast<const float*>(src + L.off[k]));
             }
@@ -447,7 +488,9 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const float p = j + u < n ? expf(s[u] * a.scale - lse) : 0.f;
-                const float e = p * (t[u] - delta);
+                float tm = t[u];
+                if constexpr (DR) tm = mk[u] * t[u];
+                const float e = p * (tm - delta);
 #pragma unroll
                 for (int k = 0; k < NV; k++) acc[k] = vfma<VW>(e, b[u][k], acc[k]);
             }
@@ -467,8 +510,8 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a) {
 }
 
 // over P^T: dB[j] = sum_i ( p_ij G[i] + scale e_ij Q[i] ), two gathered rows per entry
-template <int G, int NV, int VW, bool MH>
-__global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
+template <int G, int NV, int VW, bool MH, bool DR>
+__global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a, AttnDrop dm) {
     typedef typename Vec<VW>::type VT;
     constexpr int U = Unroll<NV>::bwd_kv;
     const int lig = threadIdx.x & (G - 1);
@@ -488,12 +531,16 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
         const int n = min(G, end - p0);
         int myrow = 0;
         if (lig < n) myrow = a.col[p0 + lig];
+        [[maybe_unused]] int mybits = 0;
+        if constexpr (DR) mybits = drop_bits<MH>(dm, myrow, row, a.heads);     // pair(i, j): the own row is the COLUMN j
         for (int j = 0; j < n; j += U) {
             VT qi[U][NV], gi[U][NV];
             float s[U], t[U], lse[U], delta[U];
+            [[maybe_unused]] float mk[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int i = bcast_i<G>(myrow, min(j + u, n - 1));
+                if constexpr (DR) mk[u] = drop_mk(dm, bcast_i<G>(mybits, min(j + u, n - 1)), L.head);
                 const char* qs = Qb + (int64_t)i * ldq_bytes;        // G == 64: scalar bases
                 const char* gs = Gb + (int64_t)i * ldg_bytes;
                 if constexpr (MH) {
@@ -531,10 +578,12 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_kv_kernel(AttnArgs a) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const float p = j + u < n ? expf(s[u] * a.scale - lse[u]) : 0.f;
-                const float es = a.scale * (p * (t[u] - delta[u]));
+                float tm = t[u], pg = p;
+                if constexpr (DR) { tm = mk[u] * t[u]; pg = p * mk[u]; }
+                const float es = a.scale * (p * (tm - delta[u]));
 #pragma unroll
                 for (int k = 0; k < NV; k++) {
-                    acc[k] = vfma<VW>(p, gi[u][k], acc[k]);
+                    acc[k] = vfma<VW>(pg, gi[u][k], acc[k]);
                     acc[k] = vfma<VW>(es, qi[u][k], acc[k]);
                 }
             }
@@ -570,25 +619,26 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_fix_kernel(AttnArgs a, cons
 
 enum Kind { FWD, BWD_Q, BWD_KV };
 
-template <int KIND, int G, int NV, int VW, bool MH>
-void launch_seg(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
-    if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW, MH>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-    else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW, MH>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW, MH>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
+template <int KIND, int G, int NV, int VW, bool MH, bool DR>
+void launch_seg(const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
+    const dim3 grid((unsigned)nblocks), block(kBlock);
+    if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
+    else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
+    else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
 }
 
-template <int KIND, int VW, bool MH>
-bool dispatch_gnv(int G, int NV, const AttnArgs& a, int64_t nblocks, hipStream_t st) {
+template <int KIND, int VW, bool MH, bool DR>
+bool dispatch_gnv(int G, int NV, const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
     switch (G) {
-        case 8: launch_seg<KIND, 8, 1, VW, MH>(a, nblocks, st); return true;
-        case 16: launch_seg<KIND, 16, 1, VW, MH>(a, nblocks, st); return true;
-        case 32: launch_seg<KIND, 32, 1, VW, MH>(a, nblocks, st); return true;
+        case 8: launch_seg<KIND, 8, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
+        case 16: launch_seg<KIND, 16, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
+        case 32: launch_seg<KIND, 32, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
         case 64:
             switch (NV) {
-                case 1: launch_seg<KIND, 64, 1, VW, MH>(a, nblocks, st); return true;
-                case 2: launch_seg<KIND, 64, 2, VW, MH>(a, nblocks, st); return true;
-                case 3: launch_seg<KIND, 64, 3, VW, MH>(a, nblocks, st); return true;
-                case 4: launch_seg<KIND, 64, 4, VW, MH>(a, nblocks, st); return true;
+                case 1: launch_seg<KIND, 64, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
+                case 2: launch_seg<KIND, 64, 2, VW, MH, DR>(a, dm, nblocks, st); return true;
+                case 3: launch_seg<KIND, 64, 3, VW, MH, DR>(a, dm, nblocks, st); return true;
+                case 4: launch_seg<KIND, 64, 4, VW, MH, DR>(a, dm, nblocks, st); return true;
             }
     }
     return false;
@@ -622,11 +672,28 @@ int head_vw(int vw, int32_t d, int32_t heads) {
     return vw;
 }
 
-template <int KIND, bool MH>
-bool dispatch_vw(int vw, int G, int NV, const AttnArgs& a, int64_t nblocks, hipStream_t st) {
-    if (vw == 4) return dispatch_gnv<KIND, 4, MH>(G, NV, a, nblocks, st);
-    if (vw == 2) return dispatch_gnv<KIND, 2, MH>(G, NV, a, nblocks, st);
-    return dispatch_gnv<KIND, 1, MH>(G, NV, a, nblocks, st);
+template <int KIND, bool MH, bool DR>
+bool dispatch_vw(int vw, int G, int NV, const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
+    if (vw == 4) return dispatch_gnv<KIND, 4, MH, DR>(G, NV, a, dm, nblocks, st);
+    if (vw == 2) return dispatch_gnv<KIND, 2, MH, DR>(G, NV, a, dm, nblocks, st);
+    return dispatch_gnv<KIND, 1, MH, DR>(G, NV, a, dm, nblocks, st);
+}
+
+// keep as the callers of the _drop_ exports give it: finite and in (0, 1]; SGCN_ERR_INVALID otherwise, before any HIP call
+int keep_ok(const char* who, float keep) {
+    SGCN_REQUIRE(std::isfinite(keep) && keep > 0.f && keep <= 1.f, "%s: keep must be finite and in (0, 1] (got %g)", who, (double)keep);
+    return SGCN_OK;
+}
+
+// the mask of a call; keep == 1: mk = 0, which `run` reads as `the kernels without dropout`
+AttnDrop drop_of(float keep, uint32_t key) {
+    AttnDrop dm{};
+    if (keep >= 1.0f) return dm;
+    sgcn_dropout_t d{};
+    d.key = key; d.keep = keep; d.rows = -1; d.width = 0;
+    const DropArgs da = drop_args(&d);       // the threshold exactly as for sgcn_dropout_t
+    dm.key = da.key; dm.thr = da.thr; dm.mk = da.scale;
+    return dm;
 }
 
 template <bool MH>
@@ -637,7 +704,7 @@ void launch_fix(int vw, dim3 grid, const AttnArgs& a, const sgcn_plan_t* plan, h
 }
 
 template <int KIND>
-int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, int32_t heads, hipStream_t st) {
+int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, int32_t heads, const AttnDrop& dm, hipStream_t st) {
     a.nseg = nrows;
     if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
     a.nvec = (a.d + vw - 1) / vw;
@@ -661,7 +728,11 @@ int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, in
     const int64_t nblocks = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
 
-    const bool ok = heads == 1 ? dispatch_vw<KIND, false>(vw, G, NV, a, nblocks, st) : dispatch_vw<KIND, true>(vw, G, NV, a, nblocks, st);
+    const bool drop = dm.mk > 0.f;
+    const bool ok = drop ? (heads == 1 ? dispatch_vw<KIND, false, true>(vw, G, NV, a, dm, nblocks, st)
+                                       : dispatch_vw<KIND, true, true>(vw, G, NV, a, dm, nblocks, st))
+                         : (heads == 1 ? dispatch_vw<KIND, false, false>(vw, G, NV, a, dm, nblocks, st)
+                                       : dispatch_vw<KIND, true, false>(vw, G, NV, a, dm, nblocks, st));
     SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
     SGCN_HIP_TRY(hipGetLastError());
 
@@ -700,13 +771,15 @@ inline int64_t ceil4(int64_t d) { return (d + 3) / 4 * 4; }
 using namespace sgcn;
 
 
-// The three host bodies: the single-head exports call them with heads = 1, the _mh_ exports pass theirs on.
+// The three host bodies: the single-head exports call them with heads = 1, the _mh_ exports pass theirs on, both with
+// keep = 1 (no dropout: the DR = false kernels); the _drop_ exports pass keep and key on as well.
 static int spattn_fwd(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
-                      const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                      float keep, uint32_t key, const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
                       float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
     SGCN_REQUIRE(M >= 0 && K >= 0, "spattn: negative size");
     SGCN_REQUIRE(d > 0, "spattn: d must be positive (got %d)", d);
     { const int rc = heads_ok("spattn", d, heads); if (rc) return rc; }
+    { const int rc = keep_ok("spattn", keep); if (rc) return rc; }
     SGCN_REQUIRE(rowptr && C && (Q || M == 0) && (B || K == 0), "spattn: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldc >= d, "spattn: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn: scale must be finite");
@@ -722,17 +795,18 @@ static int spattn_fwd(const int32_t* rowptr, const int32_t* col, int32_t M, int3
     a.rowptr = rowptr; a.col = col; a.own = Q; a.ldown = ldq; a.gat = B; a.ldgat = ldb; a.out = C; a.ldo = ldc;
     a.lse_out = lse; a.scale = scale; a.d = d;
     if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
-    return run<FWD>(a, "spattn", M, plan, vw, heads, (hipStream_t)stream);
+    return run<FWD>(a, "spattn", M, plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
 }
 
 static int spattn_bwd_q(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
-                        const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                        float keep, uint32_t key, const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
                         const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
                         float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
                         int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
     SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_q: negative size");
     SGCN_REQUIRE(d > 0, "spattn_bwd_q: d must be positive (got %d)", d);
     { const int rc = heads_ok("spattn_bwd_q", d, heads); if (rc) return rc; }
+    { const int rc = keep_ok("spattn_bwd_q", keep); if (rc) return rc; }
     SGCN_REQUIRE(rowptr && dQ && ((Q && G && C && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_q: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && ldc >= d && lddq >= d, "spattn_bwd_q: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_q: scale must be finite");
@@ -751,17 +825,18 @@ static int spattn_bwd_q(const int32_t* rowptr, const int32_t* col, int32_t M, in
     a.Cf = C; a.ldcf = ldc; a.lse = lse; a.delta_out = delta; a.out = dQ; a.ldo = lddq; a.scale = scale; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
     if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
-    return run<BWD_Q>(a, "spattn_bwd_q", M, plan, vw, heads, (hipStream_t)stream);
+    return run<BWD_Q>(a, "spattn_bwd_q", M, plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
 }
 
 static int spattn_bwd_kv(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d, int32_t heads,
-                         const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
+                         float keep, uint32_t key, const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
                          const float* G, int64_t ldg, const float* lse, const float* delta,
                          float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
                          const sgcn_plan_t* t_plan, void* stream) {
     SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_kv: negative size");
     SGCN_REQUIRE(d > 0, "spattn_bwd_kv: d must be positive (got %d)", d);
     { const int rc = heads_ok("spattn_bwd_kv", d, heads); if (rc) return rc; }
+    { const int rc = keep_ok("spattn_bwd_kv", keep); if (rc) return rc; }
     SGCN_REQUIRE(t_rowptr && dB && ((Q && G && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_kv: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && lddb >= d, "spattn_bwd_kv: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_kv: scale must be finite");
@@ -780,19 +855,19 @@ static int spattn_bwd_kv(const int32_t* t_rowptr, const int32_t* t_row, int32_t 
     a.lse = lse; a.delta = delta; a.out = dB; a.ldo = lddb; a.scale = scale; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
     if (split) { a.ws = t_plan->dev_ws; a.ldw = ldw; }
-    return run<BWD_KV>(a, "spattn_bwd_kv", K, t_plan, vw, heads, (hipStream_t)stream);
+    return run<BWD_KV>(a, "spattn_bwd_kv", K, t_plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
 }
 
 extern "C" int sgcn_spattn_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
                                    const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
                                    float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
-    return spattn_fwd(rowptr, col, M, K, d, 1, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
+    return spattn_fwd(rowptr, col, M, K, d, 1, 1.0f, 0u, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
 }
 
 extern "C" int sgcn_spattn_mh_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
                                       const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
                                       float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
-    return spattn_fwd(rowptr, col, M, K, d, heads, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
+    return spattn_fwd(rowptr, col, M, K, d, heads, 1.0f, 0u, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
 }
 
 extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
@@ -800,7 +875,7 @@ extern "C" int sgcn_spattn_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* c
                                          const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
                                          float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
                                          int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
-    return spattn_bwd_q(rowptr, col, M, K, d, 1, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd,
+    return spattn_bwd_q(rowptr, col, M, K, d, 1, 1.0f, 0u, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd,
                         add_rows, plan, stream);
 }
 
@@ -809,7 +884,7 @@ extern "C" int sgcn_spattn_mh_csr_bwd_q_f32(const int32_t* rowptr, const int32_t
                                             float scale, const float* G, int64_t ldg, const float* C, int64_t ldc,
                                             const float* lse, float* delta, float* dQ, int64_t lddq, const float* add,
                                             int64_t ldadd, int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
-    return spattn_bwd_q(rowptr, col, M, K, d, heads, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd,
+    return spattn_bwd_q(rowptr, col, M, K, d, heads, 1.0f, 0u, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd,
                         add_rows, plan, stream);
 }
 
@@ -818,7 +893,7 @@ extern "C" int sgcn_spattn_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t
                                           const float* G, int64_t ldg, const float* lse, const float* delta,
                                           float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
                                           const sgcn_plan_t* t_plan, void* stream) {
-    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, 1, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add, ldadd,
+    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, 1, 1.0f, 0u, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add, ldadd,
                          add_rows, t_plan, stream);
 }
 
@@ -827,6 +902,32 @@ extern "C" int sgcn_spattn_mh_csr_bwd_kv_f32(const int32_t* t_rowptr, const int3
                                              float scale, const float* G, int64_t ldg, const float* lse, const float* delta,
                                              float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
                                              const sgcn_plan_t* t_plan, void* stream) {
-    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, heads, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add, ldadd,
+    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, heads, 1.0f, 0u, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add, ldadd,
                          add_rows, t_plan, stream);
+}
+
+// The coefficient-dropout forms (--attn_dropout): heads, keep and key directly after d; keep == 1 is the call without them.
+extern "C" int sgcn_spattn_drop_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                                        float keep, uint32_t key, const float* Q, int64_t ldq, const float* B, int64_t ldb,
+                                        float scale, float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
+    return spattn_fwd(rowptr, col, M, K, d, heads, keep, key, Q, ldq, B, ldb, scale, C, ldc, lse, plan, stream);
+}
+
+extern "C" int sgcn_spattn_drop_csr_bwd_q_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
+                                              int32_t heads, float keep, uint32_t key, const float* Q, int64_t ldq,
+                                              const float* B, int64_t ldb, float scale, const float* G, int64_t ldg,
+                                              const float* C, int64_t ldc, const float* lse, float* delta, float* dQ,
+                                              int64_t lddq, const float* add, int64_t ldadd, int32_t add_rows,
+                                              const sgcn_plan_t* plan, void* stream) {
+    return spattn_bwd_q(rowptr, col, M, K, d, heads, keep, key, Q, ldq, B, ldb, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add,
+                        ldadd, add_rows, plan, stream);
+}
+
+extern "C" int sgcn_spattn_drop_csr_bwd_kv_f32(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d,
+                                               int32_t heads, float keep, uint32_t key, const float* Q, int64_t ldq,
+                                               const float* B, int64_t ldb, float scale, const float* G, int64_t ldg,
+                                               const float* lse, const float* delta, float* dB, int64_t lddb, const float* add,
+                                               int64_t ldadd, int32_t add_rows, const sgcn_plan_t* t_plan, void* stream) {
+    return spattn_bwd_kv(t_rowptr, t_row, K, M, d, heads, keep, key, Q, ldq, B, ldb, scale, G, ldg, lse, delta, dB, lddb, add,
+                         ldadd, add_rows, t_plan, stream);
 }

@@ -201,6 +201,19 @@ def check_attn_heads(flags=None):
     return heads
 
 
+def check_attn_dropout(flags=None):
+    """--attn_dropout as a float (0.0 = off), refused outside [0, 1) or where nothing would read it.  Needs no device; called
+    right after check_attn_heads.  (check_attention has refused what attention itself cannot run with.)"""
+    f = FLAGS if flags is None else flags
+    p = float(getattr(f, 'attn_dropout', 0.0))
+    if not (0.0 <= p < 1.0):                  # (NaN too; 1 - p is then at least 2^-53, which fp32 holds)
+        raise ValueError("--attn_dropout must lie in [0, 1) (0 = off), got %r" % (getattr(f, 'attn_dropout', 0.0),))
+    if p > 0 and getattr(f, 'aggregator', 'sum') != 'attn':
+        raise ValueError("--attn_dropout needs --aggregator attn: it drops attention coefficients, and no other aggregator "
+                         "has any")
+    return p
+
+
 def attn_heads_divide(heads, width, what):
     """ValueError naming the layer and its width unless the heads cut it evenly."""
     if width % heads:
@@ -521,31 +534,35 @@ class StaticMatrix(object):
         if self.edge is not None:
             raise ValueError("attention has no edge-masked form")
 
-    def attn_product(self, x, scale, out=None, want_lse=True, heads=1):
+    def attn_product(self, x, scale, out=None, want_lse=True, heads=1, keep=1.0, key=0):
         """(out, lse) of ops.spattn over this matrix's PATTERN with the queries x[:M]: out[i] = the rows of ``x`` that row i
         stores an entry for, weighed by softmax_j(scale * <x[i], x[j]>); lse the rows' log-sum-exp for ``attn_backward``
         (None with ``want_lse=False``).  Reads the row kernel's CSR -- pattern and segment plan -- only.  The kernel holds
         d <= 256 * VW columns: an operand whose alignment would push d over that (602-wide features on a pitch of 602
         floats: VW = 2) is staged once into an aligned scratch table, an ``out`` view of that kind is computed aligned and
         copied.  ``heads``: ops.spattn's; lse is then (M, heads), and an operand is staged where ITS alignment, not the head
-        width, is what narrows the vectors (staging cannot widen what d / heads caps)."""
+        width, is what narrows the vectors (staging cannot widen what d / heads caps).  ``keep``, ``key``: ops.spattn's
+        dropout on the coefficients, passed through (keep = 1: none)."""
         self._attn_refuse(x)
         d = int(x.shape[1])
+        # (the keywords are passed only when set: without dropout the call is the one ops.spattn has always taken)
+        drop = dict(keep=keep, key=key) if keep != 1.0 else {}
         if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out, heads=heads):
             best = ops.attn_vw(d, heads=heads)            # what aligned operands would get
             if ops.attn_vw(d, x, heads=heads) < best:
                 x = self._attn_staged('x', x, d)
             if out is not None and ops.attn_vw(d, out, heads=heads) < best:
                 res, lse = ops.spattn(self.rows_csr, x, scale=scale, want_lse=want_lse, heads=heads,
-                                      out=self._attn_staged('out', out, d, fill=False))
+                                      out=self._attn_staged('out', out, d, fill=False), **drop)
                 out.copy_(res)
                 return out, lse
-        return ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse, heads=heads)
+        return ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse, heads=heads, **drop)
 
-    def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1):
+    def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1, keep=1.0, key=0):
         """Called on the matrix whose ``attn_product(x, scale)`` gave ``out_fwd`` and ``lse``: the gradient with respect to
         ``x`` (as keys / values AND as queries) for g = dL/dout, + add on the first ``add_rows`` rows -- ops.spattn_bwd, a
-        gather over this matrix's pattern and one over its transpose's.  Operands are staged as in ``attn_product``."""
+        gather over this matrix's pattern and one over its transpose's.  Operands are staged as in ``attn_product``.
+        ``keep``, ``key``: those of the forward."""
         self._attn_refuse(x)
         d = int(x.shape[1])
         ops_ = dict(x=x, g=g, out_fwd=out_fwd, add=add)
@@ -555,7 +572,8 @@ class StaticMatrix(object):
                 if t is not None and ops.attn_vw(d, t, heads=heads) < best:
                     ops_[role] = self._attn_staged(role, t, d)
         return ops.spattn_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], None, ops_['g'], ops_['out_fwd'], lse, scale,
-                              add=ops_['add'], add_rows=add_rows, heads=heads)[1]
+                              add=ops_['add'], add_rows=add_rows, heads=heads,
+                              **(dict(keep=keep, key=key) if keep != 1.0 else {}))[1]
 
     def describe(self, d):
         """What train.pp_products records of a product of width d: where the plan came from, the sweep clock (the column

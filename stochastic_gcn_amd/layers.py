@@ -428,12 +428,20 @@ class PlainAggregator(Layer):
             attn_heads_divide(heads, d, self.name)
             scale = float(FLAGS.attn_scale) if float(FLAGS.attn_scale) > 0 else float(d // heads) ** -0.5
             self._x, self._scale = (x if want else None), scale
+            # --attn_dropout P: a training step drops coefficients under a mask keyed by (seed, this layer's index, step); the
+            # key is drawn here, once, and kept for the backward.  An evaluation model never masks.
+            self._drop = {}
+            p_drop = float(getattr(FLAGS, 'attn_dropout', 0.0))
+            if want and p_drop > 0:
+                m = self.model
+                self._drop = dict(keep=1.0 - p_drop, key=ops.attn_key(getattr(m, 'dropout_seed', FLAGS.seed), self.index,
+                                                                      getattr(m, 'dropout_step', 0)))
             if not concat:
-                self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads)
+                self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads, **self._drop)
                 return self._out
             out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
             out[:, :d] = x[:n1]
-            self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads)
+            self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads, **self._drop)
             return out
         if not concat:
             return A.product(x)
@@ -461,9 +469,9 @@ class PlainAggregator(Layer):
         if self._attn:
             # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
             if not self._concat:
-                return A.attn_backward(self._x, g, self._out, self._lse, self._scale, heads=self._heads)
+                return A.attn_backward(self._x, g, self._out, self._lse, self._scale, heads=self._heads, **self._drop)
             return A.attn_backward(self._x, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d], add_rows=A.shape[0],
-                                   heads=self._heads)
+                                   heads=self._heads, **self._drop)
         if not self._concat:
             return A.transpose.product(g)
         # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep

@@ -17,7 +17,8 @@ Reference seams replaced:
   spmax / spmax_bwd   the element-wise neighbour maximum over a CSR pattern and its backward (--aggregator max: GraphSAGE's pooling
                   aggregator without its MLP; no reference counterpart)
   spattn / spattn_bwd   softmax dot-product attention over a CSR pattern and its backward (--aggregator attn: every vertex weighs
-                  its neighbours by a softmax over pairwise scores; no reference counterpart)
+                  its neighbours by a softmax over pairwise scores; no reference counterpart); ``keep`` < 1: dropout on the
+                  coefficients (--attn_dropout) under the hash mask of attn_key / attn_kept
   history_error   how far a stored history is from the exact activations (no reference counterpart; exact_history.py)
 """
 import ctypes as C
@@ -370,14 +371,25 @@ def _attn_heads(d, heads):
     return heads
 
 
-def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True, heads=1):
+def _attn_keep(keep):
+    """``keep`` as a float in (0, 1] (1.0: no dropout on the coefficients)."""
+    keep = float(keep)
+    if not (0.0 < keep <= 1.0):               # (NaN too)
+        raise ValueError("keep must be finite and in (0, 1], got %r" % (keep,))
+    return keep
+
+
+def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True, heads=1, keep=1.0, key=0):
     """(out, lse): softmax dot-product attention over the stored pattern of the DeviceCSR ``A`` (M x K, unique column ids
     per row; stored values are not read) -- sgcn_spattn_csr_f32.  With s_ij = scale * <q[i], x[j]> over the entries j of
     row i: lse[i] = log sum_j exp(s_ij), out[i] = sum_j exp(s_ij - lse[i]) x[j]; an empty row gives +0.0 and -inf.
     ``q=None`` means x[:M].  ``out`` may be a pitched (M, >= d) view.  ``want_lse=False`` (an evaluation): lse is None,
     nothing is allocated for it.  ``heads`` = H in 1/2/4/8 (sgcn_spattn_mh_csr_f32): head h is the columns
-    [h d/H, (h+1) d/H), every head an attention of its own over the same pattern, and lse is (M, H) for H > 1."""
+    [h d/H, (h+1) d/H), every head an attention of its own over the same pattern, and lse is (M, H) for H > 1.
+    ``keep`` < 1 (sgcn_spattn_drop_csr_f32): dropout on the coefficients -- entry (i, j) of head h stays, scaled by 1 / keep,
+    where ``attn_kept(i, j, h, key, keep)``; the softmax and lse are those of keep = 1, and keep = 1 is the call without it."""
     check_unique_cols(A)
+    keep = _attn_keep(keep)
     M, K = A.shape
     bptr, ldb = _rows2d(x, "x")
     d = int(x.shape[1])
@@ -400,18 +412,25 @@ def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True, heads=1):
     lse = torch.empty((M,) if heads == 1 else (M, heads), dtype=torch.float32, device=x.device) if want_lse else None
     # (a forward slot: the row + one vector for (m, l) per head)
     plan = A.plan.struct((d + 3) // 4 * 4 + 4 * heads) if A.plan is not None else None
+    if keep < 1.0:
+        check(lib.sgcn_spattn_drop_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, int(key) & 0xFFFFFFFF, qptr, ldq,
+                                           bptr, ldb, float(scale), cptr, ldc, _ptr(lse),
+                                           C.byref(plan) if plan is not None else None, _stream()))
+        return out, lse
     check(lib.sgcn_spattn_mh_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, qptr, ldq, bptr, ldb, float(scale),
                                      cptr, ldc, _ptr(lse), C.byref(plan) if plan is not None else None, _stream()))
     return out, lse
 
 
-def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1):
+def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1, keep=1.0, key=0):
     """(dq, dx), the gradient of ``spattn(A, x, q, scale)`` for g = dL/dout, from the forward's ``out_fwd`` and ``lse`` --
     sgcn_spattn_csr_bwd_q_f32 over ``A``, then sgcn_spattn_csr_bwd_kv_f32 over ``At``, the DeviceCSR of the TRANSPOSED
     pattern (ops.transpose_host: source rows ascending).  Nothing nnz-sized is stored, no atomics: bitwise reproducible.
     With an explicit ``q``: dq (M x d, + add on its first ``add_rows`` rows) and dx = dB (K x d) separately.  With
     ``q=None`` (the queries are x[:M]): (None, dx) with dx = dB + [dQ + add ; 0] -- the first launch's result is the second
-    one's addend, so the sum costs no extra pass.  ``heads`` as in ``spattn``, ``lse`` of the shape it returned."""
+    one's addend, so the sum costs no extra pass.  ``heads`` as in ``spattn``, ``lse`` of the shape it returned.  ``keep`` and
+    ``key``: the forward's (sgcn_spattn_drop_csr_bwd_q_f32 / _bwd_kv_f32 recompute its mask; ``out_fwd`` is the masked output)."""
+    keep = _attn_keep(keep)
     M, K = A.shape
     if tuple(At.shape) != (K, M):
         raise ValueError("At has shape %s, the transpose of %s is needed" % (tuple(At.shape), tuple(A.shape)))
@@ -444,12 +463,24 @@ def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=
     dq = _attn_out(M, d, x.device, heads)
     dx = _attn_out(K, d, x.device, heads)
     plan = A.plan.struct(d) if A.plan is not None else None
+    tplan = At.plan.struct(d) if At.plan is not None else None
+    fused = q is None
+    if keep < 1.0:
+        key = int(key) & 0xFFFFFFFF
+        check(lib.sgcn_spattn_drop_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, key, qptr, ldq, bptr, ldb,
+                                                 float(scale), gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(),
+                                                 dq.data_ptr(), _rows2d(dq, "dq")[1], aptr, ldadd, add_rows,
+                                                 C.byref(plan) if plan is not None else None, _stream()))
+        check(lib.sgcn_spattn_drop_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, qptr, ldq, bptr,
+                                                  ldb, float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
+                                                  _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
+                                                  _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0,
+                                                  C.byref(tplan) if tplan is not None else None, _stream()))
+        return (None if fused else dq), dx
     check(lib.sgcn_spattn_mh_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, qptr, ldq, bptr, ldb, float(scale),
                                            gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
                                            _rows2d(dq, "dq")[1], aptr, ldadd, add_rows,
                                            C.byref(plan) if plan is not None else None, _stream()))
-    tplan = At.plan.struct(d) if At.plan is not None else None
-    fused = q is None
     check(lib.sgcn_spattn_mh_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, qptr, ldq, bptr, ldb,
                                             float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
                                             _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
@@ -1893,6 +1924,29 @@ def _fmix32_np(h):
     h = h ^ (h >> np.uint64(13))
     h = (h * np.uint64(0xC2B2AE35)) & m
     return h ^ (h >> np.uint64(16))
+
+
+ATTN_SITE = 0x4154544E          # include/sgcn.h SGCN_ATTN_SITE: the coefficient mask of aggregation layer i is site ATTN_SITE + i
+
+
+def attn_key(seed, layer_index, step):
+    """The key of the coefficient mask (--attn_dropout) of the aggregation layer at ``layer_index`` of the model's layer list
+    at one training step (the step counter that keys the step's activation dropout)."""
+    return dropout_key(seed, ATTN_SITE + int(layer_index), step)
+
+
+def attn_kept(row, col, head, key, keep):
+    """The coefficient mask of sgcn_spattn_drop_* on the host: a bool array, True where entry (row, col) of the pattern stays
+    in head ``head`` (NumPy arrays or scalars, broadcast together).  Not symmetric in (row, col); no entry is exempt."""
+    m = np.uint64(0xFFFFFFFF)
+    i = np.asarray(row, dtype=np.int64).astype(np.uint64) & m
+    j = np.asarray(col, dtype=np.int64).astype(np.uint64) & m
+    h = np.asarray(head, dtype=np.int64).astype(np.uint64) & m
+    rowh = _fmix32_np(i * np.uint64(0x9E3779B1) + np.uint64(int(key) & 0xFFFFFFFF))
+    pair = _fmix32_np(rowh + ((j * np.uint64(0x85EBCA77)) & m))
+    t = float(np.float32(keep)) * 4294967296.0
+    thr = 0xFFFFFFFF if t >= 4294967295.0 else int(t)
+    return _fmix32_np(pair + ((h * np.uint64(0x27D4EB2F)) & m)) < np.uint64(thr)
 
 
 def edge_key(seed, step):
