@@ -58,7 +58,9 @@ const char* sgcn_last_error(void);
  *       sgcn_spmax_csr_f32 / sgcn_spmax_csr_bwd_f32; softmax dot-product attention over a CSR pattern and its backward --
  *       sgcn_spattn_csr_f32 / sgcn_spattn_csr_bwd_q_f32 / sgcn_spattn_csr_bwd_kv_f32; their multi-head forms --
  *       sgcn_spattn_mh_csr_f32 / sgcn_spattn_mh_csr_bwd_q_f32 / sgcn_spattn_mh_csr_bwd_kv_f32; their forms with dropout on
- *       the coefficients -- sgcn_spattn_drop_csr_f32 / sgcn_spattn_drop_csr_bwd_q_f32 / sgcn_spattn_drop_csr_bwd_kv_f32) */
+ *       the coefficients -- sgcn_spattn_drop_csr_f32 / sgcn_spattn_drop_csr_bwd_q_f32 / sgcn_spattn_drop_csr_bwd_kv_f32;
+ *       learned additive attention scores (GAT) -- sgcn_gat_scores_f32 / sgcn_spgat_csr_f32 / sgcn_spgat_csr_bwd_u_f32 /
+ *       sgcn_spgat_csr_bwd_v_f32 / sgcn_gat_scores_bwd_f32) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -633,6 +635,78 @@ int sgcn_spattn_drop_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* 
                                     const float* dev_lse, const float* dev_delta, float* dev_dB, int64_t lddb,
                                     const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
                                     const sgcn_plan_t* t_plan /* nullable */, void* stream);
+
+/* ---- learned additive attention scores, GAT (--attn_score gat; additive, still v16) ----------------------------------------
+ * The pattern, the heads and the per-head slicing are those of the multi-head calls above (H in {1, 2, 4, 8}, d % H == 0,
+ * dh = d / H, head h the columns [h*dh, (h+1)*dh)); the score is learned.  The parameter of a layer is a (2 x d, contiguous):
+ * a[0] = a_src and a[1] = a_dst, the heads' slices side by side.  For every head h, with x the layer's input:
+ *     u_i^h  = sum_{c in h} x[i,c] * a[0,c]          v_j^h = sum_{c in h} x[j,c] * a[1,c]
+ *     z_ij   = u_i + v_j                             ONE fp32 addition in the kernels
+ *     s_ij   = z_ij > 0 ? z_ij : slope * z_ij        (LeakyReLU; there is no scale)
+ * lse, p_ij = exp(s_ij - lse_i), C_i = sum_j mk_ij p_ij B_j, empty rows (+0.0 and -inf), the true division acc / l and lse in
+ * fp64 once per row and head are exactly as defined above, and so is the coefficient mask mk_ij of the _drop_ calls: the same
+ * hash of (i, j, h, key), applied after the softmax, recomputed in every launch (keep == 1: mk = 1, instantiations that never
+ * read the mask).
+ *   backward  delta_i^h = <G_i, C_i>_h
+ *             e_ij      = p_ij (mk_ij <G_i, B_j>_h - delta_i)
+ *             dz_ij     = e_ij * (z_ij > 0 ? 1 : slope)                 the derivative at z == 0 is `slope`
+ *             dU[i,h]   = sum_j dz_ij            dV[j,h] = sum_i dz_ij
+ *             dB_j      = sum_i mk_ij p_ij G_i (+ add)
+ *   through the scores:  dX[r,c] += dU[r,h(c)] * a[0,c] + dV[r,h(c)] * a[1,c]
+ *             da[0,c]   = sum_r dU[r,h(c)] * x[r,c]                     da[1,c] = sum_r dV[r,h(c)] * x[r,c]
+ * Nothing of the size of the edge list is written, there are no atomics, and two runs give equal bits.
+ *
+ * Five launches.
+ *   sgcn_gat_scores_f32       S (rows x 2H, contiguous): S[r,h] = u_r^h, S[r,H+h] = v_r^h, in one pass over x.  So U = S and
+ *                             V = S + H, both with pitch 2H, serve the calls below.  SUMMATION ORDER within a head: one
+ *                             wavefront per row; lane l of 64 adds the head's columns h*dh + l, h*dh + l + 64, .. in ascending
+ *                             order by fused multiply-add from +0; the 64 lane sums meet in a butterfly, s += s[lane ^ o] for
+ *                             o = 32, 16, 8, 4, 2, 1.
+ *   sgcn_spgat_csr_f32        the forward over the pattern (M rows, K columns, unique column ids per row; values not read),
+ *                             U (M x H, pitch ldu) and V (K x H, pitch ldv) given as tables.  Per entry it reads the H floats of
+ *                             V[j] and gathers row B[j]; the online softmax, the slots (ldw = 4*ceil(d/4) + 4*heads) and the
+ *                             ordered fix-up are those of sgcn_spattn_mh_csr_f32.  dev_lse (M x H) is nullable.
+ *   sgcn_spgat_csr_bwd_u_f32  a gather over the pattern: writes delta (M x H) and dU (M x H, contiguous); one gathered row per
+ *                             entry (B[j], for <G_i, B_j>).  A split row's partial dU go to its slots -- SLOT GEOMETRY: ldw = 8
+ *                             floats, head h's sum at float h, so ws_elems >= 8 * nslots -- and are added in slot order.
+ *   sgcn_spgat_csr_bwd_v_f32  a gather over the TRANSPOSED pattern (K rows over M columns, source rows ascending): writes
+ *                             dB (K x d) with the epilogue addend of the calls above (out[r] += add[r] for r < add_rows) and dV
+ *                             (K x H, contiguous).  Per entry it gathers G[i] and reads the scalars u_i, lse_i and delta_i;
+ *                             B[j] is the group's own row.  SLOT GEOMETRY: ldw = 4*ceil(d/4) + 8 floats -- the partial dB on
+ *                             floats [0, d), head h's partial dV at float 4*ceil(d/4) + h -- added in slot order.
+ *   sgcn_gat_scores_bwd_f32   takes dU (its first rows_u rows; rows r >= rows_u have no dU term) and dV (rows rows) back
+ *                             through the scores: adds the rank-2H term into dev_dX when that is not null -- per element
+ *                             t = fma(dU, a[0,c], dX), then fma(dV, a[1,c], t) -- and writes da (2 x d) by a two-stage
+ *                             reduction: workgroup b sums the rows [64 b, 64 b + 64) in ascending order by fused multiply-add
+ *                             from +0 into dev_ws[b][0 / 1][c] (a partition that depends on `rows` alone), then the partials
+ *                             are added in block order.  ws_elems >= ceil(rows / 64) * 2 * d.
+ *
+ * Width.  The limit of the attention calls stays, d <= 256 * VW with VW chosen by their rule from B, G, C, dB, the addend and
+ * the workspace (the backward's <G_i, B_j> needs the whole head in one group): any other d is SGCN_ERR_INVALID before any HIP
+ * call.  The two score calls have no width limit.
+ *
+ * Validation, before any HIP call and with nothing written (SGCN_ERR_INVALID): everything the _drop_ calls refuse (scale
+ * aside), a slope outside [0, 1] or NaN, a score-table pitch below heads, rows_u outside [0, rows], a workspace too small. */
+int sgcn_gat_scores_f32(const float* dev_x, int64_t ldx, int32_t rows, int32_t d, int32_t heads,
+                        const float* dev_a /* 2 x d */, float* dev_S /* rows x 2*heads */, void* stream);
+int sgcn_spgat_csr_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                       float keep, uint32_t key, const float* dev_U, int64_t ldu, const float* dev_V, int64_t ldv,
+                       const float* dev_B, int64_t ldb, float slope, float* dev_C, int64_t ldc,
+                       float* dev_lse /* nullable; M x heads */, const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spgat_csr_bwd_u_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d, int32_t heads,
+                             float keep, uint32_t key, const float* dev_U, int64_t ldu, const float* dev_V, int64_t ldv,
+                             const float* dev_B, int64_t ldb, float slope, const float* dev_G, int64_t ldg,
+                             const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dU,
+                             const sgcn_plan_t* plan /* nullable */, void* stream);
+int sgcn_spgat_csr_bwd_v_f32(const int32_t* dev_t_rowptr, const int32_t* dev_t_row, int32_t K, int32_t M, int32_t d,
+                             int32_t heads, float keep, uint32_t key, const float* dev_U, int64_t ldu, const float* dev_V,
+                             int64_t ldv, const float* dev_B, int64_t ldb, float slope, const float* dev_G, int64_t ldg,
+                             const float* dev_lse, const float* dev_delta, float* dev_dB, int64_t lddb, float* dev_dV,
+                             const float* dev_add /* nullable */, int64_t ldadd, int32_t add_rows,
+                             const sgcn_plan_t* t_plan /* nullable */, void* stream);
+int sgcn_gat_scores_bwd_f32(const float* dev_x, int64_t ldx, int32_t rows, int32_t rows_u, int32_t d, int32_t heads,
+                            const float* dev_a, const float* dev_dU, const float* dev_dV, float* dev_dX /* nullable */,
+                            int64_t lddx, float* dev_da /* 2 x d */, float* dev_ws, int64_t ws_elems, void* stream);
 
 /* ---- multi-GPU (the reference is single-process, gcn/train.py:130) ---------------------------------------
  * The library's own RCCL communicator (librccl.so by dlopen), so that the data-parallel step's collectives are stream-

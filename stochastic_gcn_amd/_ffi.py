@@ -185,6 +185,19 @@ SIGNATURES = {
     "sgcn_spattn_drop_csr_bwd_kv_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P,
                                                   C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, P, P, C.c_int64, P,
                                                   C.c_int64, C.c_int32, C.POINTER(Plan), P]),
+    # learned additive attention scores (--attn_score gat): the score tables, the three launches over the pattern with the
+    # tables U / V in place of Q and `slope` in place of `scale`, and the way back through the scores
+    "sgcn_gat_scores_f32": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
+    "sgcn_spgat_csr_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P, C.c_int64,
+                                     P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, C.POINTER(Plan), P]),
+    "sgcn_spgat_csr_bwd_u_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P,
+                                           C.c_int64, P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, C.c_int64, P, P,
+                                           P, C.POINTER(Plan), P]),
+    "sgcn_spgat_csr_bwd_v_f32": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, P,
+                                           C.c_int64, P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, P, P, C.c_int64,
+                                           P, P, C.c_int64, C.c_int32, C.POINTER(Plan), P]),
+    "sgcn_gat_scores_bwd_f32": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, P,
+                                          P, C.c_int64, P]),
     "sgcn_coll_available": (C.c_int, [C.POINTER(C.c_int32)]),
     "sgcn_coll_retain": (C.c_int, []),
     "sgcn_coll_abort": (C.c_int, []),

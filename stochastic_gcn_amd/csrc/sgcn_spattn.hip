@@ -38,218 +38,14 @@
 // entry's id, once for all heads): nothing is stored for it.  DR is
 // a template parameter, not a run-time branch, and the mask travels in a second kernel argument that the DR = false
 // kernels never read: their device code is, instruction for instruction, the code they had before DR existed.
+//
+// The arguments, the mask, the lane geometry, the reductions, the forward's fix-up kernel, the backward's epilogue and the host
+// checks live in sgcn_attn_dev.h, which sgcn_spgat.hip (learned additive scores) shares.
 #include <cmath>
-#include "sgcn_dev.h"
+#include "sgcn_attn_dev.h"
 
 namespace sgcn {
-
-int group_lanes(int nvec);   // sgcn_spmm.hip: lanes per row group for `nvec` vectors
-
 namespace {
-
-constexpr int kMaxVec = 256;   // vectors per row: 64 lanes x NV <= 4
-
-struct AttnArgs {
-    const int32_t* rowptr;
-    const int32_t* col;      // forward / bwd_q: column ids; bwd_kv: the source rows of the transposed pattern
-    const sgcn_seg_t* seg;   // nullable: implicit one segment per row
-    int64_t nseg;
-    const float* own;        // the table the segment's own row comes from: Q (forward, bwd_q), B (bwd_kv)
-    int64_t ldown;
-    const float* gat;        // the gathered table: B (forward, bwd_q), Q (bwd_kv)
-    int64_t ldgat;
-    const float* G;          // bwd_q: the own row's gradient; bwd_kv: gathered beside `gat`
-    int64_t ldg;
-    const float* Cf;         // bwd_q: the forward's output
-    int64_t ldcf;
-    const float* lse;        // backward
-    const float* delta;      // bwd_kv
-    float* delta_out;        // bwd_q
-    float* lse_out;          // forward, nullable
-    float* out;              // C / dQ / dB
-    int64_t ldo;
-    float scale;
-    int32_t d;
-    int32_t nvec;            // ceil(d / VW)
-    int32_t ragged;          // d % VW != 0: the last vector over-reads pad elements, which are zeroed after the load
-    float* ws;
-    int64_t ldw;
-    const float* add;        // backward: out[row] += add[row] for row < add_rows
-    int64_t ldadd;
-    int32_t add_rows;
-    int32_t heads;           // H; the MH kernels only read the three below
-    int32_t gh;              // lanes per head, G / H (a power of two)
-    int32_t nvh;             // vectors per head, dh / VW
-};
-
-// the coefficient mask (include/sgcn.h, attention dropout), a second kernel argument: AttnArgs keeps its layout, and the
-// kernels without dropout do not read this one
-struct AttnDrop {
-    uint32_t key, thr;       // kept iff hash < thr
-    float mk;                // 1 / keep
-};
-// The kept bits of entry (i, j) of P: bit h is set iff head h keeps it.  A lane hashes the ONE entry whose id it fetched for the
-// chunk of G entries -- all heads of it, 1 + H finalisers per G entries and lane -- and the bits travel with the id's
-// broadcast: per entry a lane adds one move and one bit test, not two finalisers.
-template <bool MH>
-__device__ __forceinline__ int drop_bits(const AttnDrop& a, int i, int j, int heads) {
-    const uint32_t pair = fmix32(fmix32((uint32_t)i * 0x9E3779B1u + a.key) + (uint32_t)j * 0x85EBCA77u);
-    if constexpr (!MH) return fmix32(pair) < a.thr;
-    else {
-        int bits = 0;
-        for (int h = 0; h < heads; h++) bits |= (int)(fmix32(pair + (uint32_t)h * 0x27D4EB2Fu) < a.thr) << h;
-        return bits;
-    }
-}
-__device__ __forceinline__ float drop_mk(const AttnDrop& a, int bits, int head) { return (bits >> head) & 1 ? a.mk : 0.f; }
-
-template <int G>
-__device__ __forceinline__ bool my_segment(const AttnArgs& a, int& row, int& start, int& end, int& slot) {
-    constexpr int GPB = kBlock / G;
-    const int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / G;
-    if (s >= a.nseg) return false;
-    if (a.seg) {
-        const sgcn_seg_t sg = a.seg[s];
-        row = sg.row; start = sg.start; end = sg.end; slot = sg.slot;
-    } else {
-        row = (int)s; start = a.rowptr[s]; end = a.rowptr[s + 1]; slot = -1;
-    }
-    row = uniform_i<G>(row); start = uniform_i<G>(start);
-    end = uniform_i<G>(end); slot = uniform_i<G>(slot);
-    return true;
-}
-
-// zero the elements e >= cnt: the pad a ragged last vector over-read (cnt < VW), a lane past the row width (cnt == 0)
-template <int VW>
-__device__ __forceinline__ void keep_head(typename Vec<VW>::type& v, int cnt) {
-    if constexpr (VW == 1) v = cnt > 0 ? v : 0.f;
-    else {
-#pragma unroll
-        for (int e = 0; e < VW; e++) v[e] = e < cnt ? v[e] : 0.f;
-    }
-}
-template <int VW>
-__device__ __forceinline__ float vdot(const typename Vec<VW>::type& x, const typename Vec<VW>::type& y, float acc) {
-    if constexpr (VW == 1) return __builtin_fmaf(x, y, acc);
-    else {
-#pragma unroll
-        for (int e = 0; e < VW; e++) acc = __builtin_fmaf(x[e], y[e], acc);
-        return acc;
-    }
-}
-template <int VW>
-__device__ __forceinline__ void vstore_n(float* p, typename Vec<VW>::type v, int cnt) {
-    if (cnt >= VW) vstore<VW>(p, v);
-    else vstore_head<VW>(p, v, cnt);
-}
-
-// lse = m + log l, once per row: the logarithm and the sum in fp64, rounded once (logf alone was measured 2 ulp off at
-// l = 300, and the backward's every weight exp(s - lse) inherits lse's error)
-__device__ __forceinline__ float lse_of(float m, float l) { return (float)((double)m + log((double)l)); }
-
-// the sum of U values over the group's G lanes, every lane getting every total; the U chains are independent
-template <int G, int U>
-__device__ __forceinline__ void group_sum(float (&s)[U]) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1)
-#pragma unroll
-        for (int u = 0; u < U; u++) s[u] += __shfl_xor(s[u], o, G);
-}
-// two sums per entry through ONE tree: after the first exchange even lanes carry s and odd lanes t, the steps 2 .. G/2
-// reduce both at once, and the last two moves hand every lane both totals
-template <int G, int U>
-__device__ __forceinline__ void group_sum2(float (&s)[U], float (&t)[U], int lig) {
-    const bool odd = lig & 1;
-    float v[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const float keep = odd ? t[u] : s[u], send = odd ? s[u] : t[u];
-        v[u] = keep + __shfl_xor(send, 1, G);
-    }
-#pragma unroll
-    for (int o = 2; o < G; o <<= 1)
-#pragma unroll
-        for (int u = 0; u < U; u++) v[u] += __shfl_xor(v[u], o, G);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        s[u] = __shfl(v[u], lig & ~1, G);
-        t[u] = __shfl(v[u], lig | 1, G);
-    }
-}
-
-// the multi-head forms: the same sums over the aligned sub-group of `gh` lanes (wave-uniform, a power of two <= G) that the
-// lane's head owns; gh == 1: every lane already holds its head's totals
-template <int G, int U>
-__device__ __forceinline__ void head_sum(float (&s)[U], int gh) {
-    for (int o = gh >> 1; o > 0; o >>= 1)
-#pragma unroll
-        for (int u = 0; u < U; u++) s[u] += __shfl_xor(s[u], o, G);
-}
-template <int G, int U>
-__device__ __forceinline__ void head_sum2(float (&s)[U], float (&t)[U], int lig, int gh) {
-    if (gh == 1) return;
-    const bool odd = lig & 1;
-    float v[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const float keep = odd ? t[u] : s[u], send = odd ? s[u] : t[u];
-        v[u] = keep + __shfl_xor(send, 1, G);
-    }
-    for (int o = 2; o < gh; o <<= 1)
-#pragma unroll
-        for (int u = 0; u < U; u++) v[u] += __shfl_xor(v[u], o, G);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        s[u] = __shfl(v[u], lig & ~1, G);
-        t[u] = __shfl(v[u], lig | 1, G);
-    }
-}
-
-// what a lane owns of a row: NV vectors, their byte offsets (lanes past the row width re-read the last valid vector
-// instead of branching around the load) and how many of their elements exist
-// MH: the lane's head is lig / gh, and its vectors are r, r + gh, .. (r = lig % gh) of that head's nvh whole ones
-template <int G, int NV, int VW, bool MH = false>
-struct Lane {
-    uint32_t off[NV];
-    int cnt[NV];     // 0: no such vector; VW: whole; between: the ragged last one
-    int vi[NV];
-    int head;        // MH: the head this lane works for (0 otherwise)
-    bool first;      // MH: the lane that stores its head's scalars (lane 0 of the group otherwise)
-    __device__ __forceinline__ Lane(const AttnArgs& a, int lig) {
-        if constexpr (MH) {
-            const int r = lig & (a.gh - 1);
-            head = lig >> (31 - __builtin_clz(a.gh));
-            first = r == 0;
-            const int base = head * a.nvh;
-#pragma unroll
-            for (int k = 0; k < NV; k++) {
-                const int v = r + k * a.gh;
-                vi[k] = base + v;
-                cnt[k] = v < a.nvh ? VW : 0;
-                off[k] = (uint32_t)(base + min(v, a.nvh - 1)) * (uint32_t)(VW * sizeof(float));
-            }
-        } else {
-            head = 0;
-            first = lig == 0;
-#pragma unroll
-            for (int k = 0; k < NV; k++) {
-                vi[k] = lig + k * G;
-                cnt[k] = vi[k] < a.nvec ? min(VW, a.d - vi[k] * VW) : 0;
-                off[k] = (uint32_t)min(vi[k], a.nvec - 1) * (uint32_t)(VW * sizeof(float));
-            }
-        }
-    }
-    // a row of the segment's own: loaded once, pads and absent vectors zeroed -- a zero there keeps the (finite)
-    // gathered element it meets out of every dot product
-    __device__ __forceinline__ void own_row(const float* base, int64_t ld, int row, typename Vec<VW>::type (&v)[NV]) const {
-        const char* src = reinterpret_cast<const char*>(base) + (int64_t)row * ld * (int64_t)sizeof(float);
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            v[k] = vload<VW>(reinterpret_cast<const float*>(src + off[k]));
-            keep_head<VW>(v[k], cnt[k]);
-        }
-    }
-};
 
 template <int NV>
 struct Unroll { static constexpr int fwd = 4, bwd_q = NV >= 3 ? 2 : 4, bwd_kv = NV >= 2 ? 2 : 4; };
@@ -355,63 +151,7 @@ __global__ __launch_bounds__(kBlock) void spattn_seg_kernel(AttnArgs a, AttnDrop
     }
 }
 
-// A split row's slots: the largest m first, then l and acc added in slot order, each slot scaled by exp(m_q - m).
-// MH: the thread's vector belongs to head vi / nvh, whose (m, l) sit 4 * head floats further on; per head the same sum.
-template <int VW, bool MH>
-__global__ __launch_bounds__(kBlock) void spattn_fix_kernel(AttnArgs a, const sgcn_fix_t* fix, int64_t nfix) {
-    typedef typename Vec<VW>::type VT;
-    const int64_t f = blockIdx.x;
-    if (f >= nfix) return;
-    const sgcn_fix_t fx = fix[f];
-    const int vi = threadIdx.x;
-    if (vi >= a.nvec) return;
-    const float* w = a.ws + (int64_t)fx.first_slot * a.ldw;
-    int head = 0;
-    int64_t mo = a.ldw - 4;                    // where the slot keeps this thread's m; l follows it
-    if constexpr (MH) { head = vi / a.nvh; mo = a.ldw - 4 * a.heads + 4 * head; }
-    float m = -INFINITY;
-    for (int q = 0; q < fx.nslots; q++) m = fmaxf(m, w[(int64_t)q * a.ldw + mo]);
-    float l = 0.f;
-    VT acc = vzero<VW>();
-    for (int q = 0; q < fx.nslots; q++) {
-        const float* wq = w + (int64_t)q * a.ldw;
-        const float lq = wq[mo + 1];
-        if (lq > 0.f) {                        // (a segment always holds an entry; the guard keeps -inf - -inf out)
-            const float sc = expf(wq[mo] - m);
-            l = __builtin_fmaf(lq, sc, l);
-            acc = vfma<VW>(sc, vload<VW>(wq + (int64_t)vi * VW), acc);
-        }
-    }
-    VT r = vzero<VW>();
-    if (l > 0.f) r = acc / l;
-    vstore_n<VW>(a.out + (int64_t)fx.row * a.ldo + (int64_t)vi * VW, r, min(VW, a.d - vi * VW));
-    if constexpr (MH) {
-        if (a.lse_out && vi == head * a.nvh) a.lse_out[(int64_t)fx.row * a.heads + head] = l > 0.f ? lse_of(m, l) : -INFINITY;
-    } else {
-        if (a.lse_out && vi == 0) a.lse_out[fx.row] = l > 0.f ? lse_of(m, l) : -INFINITY;
-    }
-}
-
 // ---- backward -----------------------------------------------------------------------------------------------------------
-// r = mul * r (+ add[row] for row < add_rows), the first `cnt` elements stored
-template <int VW>
-__device__ __forceinline__ void bwd_store(const AttnArgs& a, int row, int vi, typename Vec<VW>::type r, float mul) {
-    const int left = a.d - vi * VW;   // > 0 by construction
-    r *= mul;
-    if (a.add && row < a.add_rows) {
-        const float* ad = a.add + (int64_t)row * a.ldadd + (int64_t)vi * VW;
-        if (left >= VW) r += vload<VW>(ad);
-        else {
-#pragma unroll
-            for (int e = 0; e < VW; e++)
-                if (e < left) {
-                    if constexpr (VW == 1) r += ad[0]; else r[e] += ad[e];
-                }
-        }
-    }
-    vstore_n<VW>(a.out + (int64_t)row * a.ldo + (int64_t)vi * VW, r, left);
-}
-
 // over P: delta_i and dQ[i] = scale * sum_j e_ij B[j]
 template <int G, int NV, int VW, bool MH, bool DR>
 __global__ __launch_bounds__(kBlock) void spattn_bwd_q_kernel(AttnArgs a, AttnDrop dm) {
@@ -644,63 +384,11 @@ bool dispatch_gnv(int G, int NV, const AttnArgs& a, const AttnDrop& dm, int64_t 
     return false;
 }
 
-// the width one group can hold at vector width vw; SGCN_ERR_INVALID beyond it, before any HIP call
-int width_ok(const char* who, int32_t d, int vw, int32_t heads) {
-    if (heads > 1) {
-        SGCN_REQUIRE(((int64_t)d + vw - 1) / vw <= kMaxVec,
-                     "%s: d = %d is over the limit of %d columns at vector width %d (d <= 256 * VW; VW = 4 needs 16-byte aligned "
-                     "rows of every operand, VW = 2 8-byte aligned ones; with heads = %d VW must also divide d / heads = %d)",
-                     who, d, kMaxVec * vw, vw, heads, d / heads);
-        return SGCN_OK;
-    }
-    SGCN_REQUIRE(((int64_t)d + vw - 1) / vw <= kMaxVec,
-                 "%s: d = %d is over the limit of %d columns at vector width %d (d <= 256 * VW; VW = 4 needs 16-byte aligned "
-                 "rows of every operand, VW = 2 8-byte aligned ones)", who, d, kMaxVec * vw, vw);
-    return SGCN_OK;
-}
-
-int heads_ok(const char* who, int32_t d, int32_t heads) {
-    SGCN_REQUIRE(heads == 1 || heads == 2 || heads == 4 || heads == 8, "%s: heads must be one of 1/2/4/8 (got %d)", who, heads);
-    SGCN_REQUIRE(d % heads == 0, "%s: d = %d is not a multiple of heads = %d", who, d, heads);
-    return SGCN_OK;
-}
-
-// heads > 1: no vector may straddle two heads -- the widest of what the operands allow that divides d / heads
-int head_vw(int vw, int32_t d, int32_t heads) {
-    if (heads > 1)
-        while ((d / heads) % vw) vw >>= 1;
-    return vw;
-}
-
 template <int KIND, bool MH, bool DR>
 bool dispatch_vw(int vw, int G, int NV, const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
     if (vw == 4) return dispatch_gnv<KIND, 4, MH, DR>(G, NV, a, dm, nblocks, st);
     if (vw == 2) return dispatch_gnv<KIND, 2, MH, DR>(G, NV, a, dm, nblocks, st);
     return dispatch_gnv<KIND, 1, MH, DR>(G, NV, a, dm, nblocks, st);
-}
-
-// keep as the callers of the _drop_ exports give it: finite and in (0, 1]; SGCN_ERR_INVALID otherwise, before any HIP call
-int keep_ok(const char* who, float keep) {
-    SGCN_REQUIRE(std::isfinite(keep) && keep > 0.f && keep <= 1.f, "%s: keep must be finite and in (0, 1] (got %g)", who, (double)keep);
-    return SGCN_OK;
-}
-
-// the mask of a call; keep == 1: mk = 0, which `run` reads as `the kernels without dropout`
-AttnDrop drop_of(float keep, uint32_t key) {
-    AttnDrop dm{};
-    if (keep >= 1.0f) return dm;
-    sgcn_dropout_t d{};
-    d.key = key; d.keep = keep; d.rows = -1; d.width = 0;
-    const DropArgs da = drop_args(&d);       // the threshold exactly as for sgcn_dropout_t
-    dm.key = da.key; dm.thr = da.thr; dm.mk = da.scale;
-    return dm;
-}
-
-template <bool MH>
-void launch_fix(int vw, dim3 grid, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
-    if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-    else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-    else hipLaunchKernelGGL((spattn_fix_kernel<1, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
 }
 
 template <int KIND>
@@ -753,17 +441,6 @@ int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, in
     return SGCN_OK;
 }
 
-int plan_ok(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw) {
-    SGCN_REQUIRE(plan->dev_seg && plan->nseg >= nrows, "%s: malformed plan", who);
-    if (plan->nfix > 0) {
-        SGCN_REQUIRE(plan->dev_fix && plan->dev_ws, "%s: plan with split rows needs dev_fix/dev_ws", who);
-        SGCN_REQUIRE(plan->ws_elems >= plan->nslots * ldw, "%s: workspace too small (%lld < %lld floats)", who,
-                     (long long)plan->ws_elems, (long long)(plan->nslots * ldw));
-    }
-    return SGCN_OK;
-}
-
-inline int64_t ceil4(int64_t d) { return (d + 3) / 4 * 4; }
 
 }  // namespace
 }  // namespace sgcn

@@ -214,6 +214,33 @@ def check_attn_dropout(flags=None):
     return p
 
 
+ATTN_SCORES = _CHOICES['attn_score']
+
+
+def check_attn_score(flags=None):
+    """(--attn_score gat?, --attn_slope) with what the learned scores have no meaning for refused.  Needs no device; called
+    right after check_attn_dropout."""
+    f = FLAGS if flags is None else flags
+    score = getattr(f, 'attn_score', 'dot')
+    if score not in ATTN_SCORES:
+        raise ValueError("--attn_score must be one of %s, got %r" % ('/'.join(ATTN_SCORES), score))
+    slope = float(getattr(f, 'attn_slope', 0.2))
+    if not (0.0 <= slope <= 1.0):             # (NaN too)
+        raise ValueError("--attn_slope must lie in [0, 1], got %r" % (getattr(f, 'attn_slope', 0.2),))
+    if score != 'gat':
+        if slope != 0.2:
+            raise ValueError("--attn_slope needs --attn_score gat: it is the negative slope of the LeakyReLU on the learned "
+                             "scores, and the dot-product scores have none")
+        return False, slope
+    if getattr(f, 'aggregator', 'sum') != 'attn':
+        raise ValueError("--attn_score gat needs --aggregator attn: it is how the attention scores are formed, and no other "
+                         "aggregator computes any")
+    if float(getattr(f, 'attn_scale', 0.0)) != 0.0:
+        raise ValueError("--attn_score gat is not supported with --attn_scale: the learned scores have no scale (the vectors "
+                         "a_src and a_dst carry it)")
+    return True, slope
+
+
 def attn_heads_divide(heads, width, what):
     """ValueError naming the layer and its width unless the heads cut it evenly."""
     if width % heads:
@@ -574,6 +601,50 @@ class StaticMatrix(object):
         return ops.spattn_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], None, ops_['g'], ops_['out_fwd'], lse, scale,
                               add=ops_['add'], add_rows=add_rows, heads=heads,
                               **(dict(keep=keep, key=key) if keep != 1.0 else {}))[1]
+
+    # ---- learned additive scores (--attn_score gat) ------------------------------------------------------------------------
+    def gat_product(self, x, a, slope, out=None, want_lse=True, heads=1, keep=1.0, key=0):
+        """(out, lse, S) of ops.gat_scores + ops.spgat over this matrix's PATTERN: S = the score table of ``x`` under the
+        layer's vectors ``a`` (2, d), out[i] = the rows of ``x`` that row i stores an entry for, weighed by
+        softmax_j(LeakyReLU(S[i, h] + S[j, H + h])) per head h.  lse (M, H) and S are what ``gat_backward`` needs (lse is None
+        with ``want_lse=False``).  Operands are staged as in ``attn_product``, and the same operands are refused."""
+        self._attn_refuse(x)
+        d = int(x.shape[1])
+        H = int(heads)
+        S = ops.gat_scores(x, a, heads=H)
+        M = self.shape[0]
+        kw = dict(slope=slope, want_lse=want_lse, heads=H, keep=keep, key=key)
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out, heads=H):
+            best = ops.attn_vw(d, heads=H)
+            if ops.attn_vw(d, x, heads=H) < best:
+                x = self._attn_staged('x', x, d)
+            if out is not None and ops.attn_vw(d, out, heads=H) < best:
+                res, lse = ops.spgat(self.rows_csr, x, S[:M, :H], S[:, H:], out=self._attn_staged('out', out, d, fill=False), **kw)
+                out.copy_(res)
+                return out, lse, S
+        res, lse = ops.spgat(self.rows_csr, x, S[:M, :H], S[:, H:], out=out, **kw)
+        return res, lse, S
+
+    def gat_backward(self, x, a, S, g, out_fwd, lse, slope, add=None, add_rows=0, heads=1, keep=1.0, key=0, need_dx=True):
+        """Called on the matrix whose ``gat_product(x, a, slope)`` gave ``out_fwd``, ``lse`` and ``S``: (dX or None, da) for
+        g = dL/dout -- ops.spgat_bwd (a gather over this matrix's pattern, one over its transpose's, the addend in the
+        second one's epilogue), then ops.gat_scores_bwd, which adds the scores' share into dX and reduces da (2, d).
+        ``need_dx=False``: dX is not formed (the launch over the transpose still runs, for dV)."""
+        self._attn_refuse(x)
+        d = int(x.shape[1])
+        H = int(heads)
+        M = self.shape[0]
+        ops_ = dict(x=x, g=g, out_fwd=out_fwd, add=add if need_dx else None)
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, ops_['add'], heads=H):
+            best = ops.attn_vw(d, heads=H)
+            for role, t in list(ops_.items()):
+                if t is not None and ops.attn_vw(d, t, heads=H) < best:
+                    ops_[role] = self._attn_staged(role, t, d)
+        dB, dU, dV, _ = ops.spgat_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], S[:M, :H], S[:, H:], ops_['g'],
+                                      ops_['out_fwd'], lse, slope=slope, add=ops_['add'], add_rows=add_rows if need_dx else 0,
+                                      heads=H, keep=keep, key=key)
+        da = ops.gat_scores_bwd(ops_['x'], a, dU, dV, dx=dB if need_dx else None, heads=H)
+        return (dB if need_dx else None), da
 
     def describe(self, d):
         """What train.pp_products records of a product of width d: where the plan came from, the sweep clock (the column

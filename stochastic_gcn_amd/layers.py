@@ -380,6 +380,20 @@ class PlainAggregator(Layer):
         super(PlainAggregator, self).__init__(**kw)
         self.model, self.l = model, l
 
+    def _gat(self):
+        return FLAGS.aggregator == 'attn' and getattr(FLAGS, 'attn_score', 'dot') == 'gat'
+
+    def param_shapes(self):
+        """--attn_score gat: the layer's score vectors (a_src ; a_dst) over its own input width -- the one aggregator that
+        owns a parameter.  Otherwise nothing: the layout and the initial weights are those of a run without the flag."""
+        if not self._gat():
+            return []
+        d = int(self.model.agg0_dim if self.l == 0 else FLAGS.hidden1)
+        return [('attn_vec', (2, d), 'glorot')]
+
+    def wd_vars(self):
+        return []                                       # (weight decay stays with the first dense layer)
+
     def forward(self, x):
         A = self.model.cur.adj[self.l]
         concat = FLAGS.normalization != 'gcn'
@@ -436,6 +450,24 @@ class PlainAggregator(Layer):
                 m = self.model
                 self._drop = dict(keep=1.0 - p_drop, key=ops.attn_key(getattr(m, 'dropout_seed', FLAGS.seed), self.index,
                                                                       getattr(m, 'dropout_step', 0)))
+            # --attn_score gat: the scores are LeakyReLU(u_i + v_j) of the layer's own vectors -- one launch for the score
+            # table, then the product; a training model keeps the table beside the input, the output and lse
+            self._gat_on = self._gat()
+            if self._gat_on:
+                if not hasattr(A, 'gat_product'):
+                    raise RuntimeError("--attn_score gat runs on a full-graph matrix only (full_batch.StaticMatrix)")
+                a, slope = self.vars['attn_vec'], float(getattr(FLAGS, 'attn_slope', 0.2))
+                if tuple(a.shape) != (2, d):
+                    raise ValueError("%s: attn_vec is %s, the input is %d columns wide" % (self.name, tuple(a.shape), d))
+                self._slope = slope
+                out = None
+                if concat:
+                    out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
+                    out[:, :d] = x[:n1]
+                res, lse, S = A.gat_product(x, a, slope, out=out[:, d:] if concat else None, want_lse=want, heads=heads,
+                                            **self._drop)
+                self._out, self._lse, self._S = res, lse, (S if want else None)
+                return out if concat else res
             if not concat:
                 self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads, **self._drop)
                 return self._out
@@ -466,6 +498,18 @@ class PlainAggregator(Layer):
             if not self._concat:
                 return A.transpose.max_backward(g, self._arg)
             return A.transpose.max_backward(g[:, d:], self._arg, add=g[:, :d], add_rows=A.shape[0])
+        if self._attn and self._gat_on:
+            # launches 3, 4, 5: dU over A, dB (+ g_self in the epilogue) and dV over A^T, then back through the scores into dX
+            # and attn_vec's gradient; as the model's first parametrised layer (--nopreprocess) nothing consumes dX
+            a = self.vars['attn_vec']
+            kw = dict(heads=self._heads, need_dx=self.need_dx, **self._drop)
+            if not self._concat:
+                dx, da = A.gat_backward(self._x, a, self._S, g, self._out, self._lse, self._slope, **kw)
+            else:
+                dx, da = A.gat_backward(self._x, a, self._S, g[:, d:], self._out, self._lse, self._slope, add=g[:, :d],
+                                        add_rows=A.shape[0], **kw)
+            self.grads['attn_vec'].copy_(da)
+            return dx
         if self._attn:
             # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
             if not self._concat:

@@ -529,10 +529,12 @@ class GCN(Model):
             self.adam_m = torch.zeros_like(self.theta)
             self.adam_v = torch.zeros_like(self.theta)
         # weight decay: the vars of the first parametrised layer (gcn/models.py:68-75) are one contiguous
-        # range of the flat buffer (a layer's parameters are laid out back to back, wd_vars() first)
+        # range of the flat buffer (a layer's parameters are laid out back to back, wd_vars() first) -- the first layer that
+        # HAS decayed variables: an aggregator that owns score vectors (--attn_score gat) has none, and under --nopreprocess
+        # it comes before the first dense layer
         self._wd_range = (0, 0)
         for layer in self.layers:
-            if layer.param_shapes():
+            if layer.param_shapes() and layer.wd_vars():
                 spans = [(off, off + n) for name, shape, _, off, n in layout
                          if name.rsplit('/', 1)[0] == layer.name and name.rsplit('/', 1)[1] in layer.wd_vars()]
                 lo, hi = min(a for a, _ in spans), max(b for _, b in spans)

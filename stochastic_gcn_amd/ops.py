@@ -489,6 +489,149 @@ def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=
     return (None if fused else dq), dx
 
 
+GAT_RED_ROWS = 64            # sgcn_gat_scores_bwd_f32: rows per partial sum of da
+
+
+def _attn_slope(slope):
+    """``slope`` as a float in [0, 1] (the LeakyReLU of the learned scores)."""
+    slope = float(slope)
+    if not (0.0 <= slope <= 1.0):             # (NaN too)
+        raise ValueError("slope must lie in [0, 1], got %r" % (slope,))
+    return slope
+
+
+def _gat_vec(a, d):
+    _dev(a, torch.float32, "a")
+    if tuple(a.shape) != (2, d) or not a.is_contiguous():
+        raise ValueError("a must be a contiguous (2, %d) table of floats, got %s" % (d, tuple(a.shape)))
+    return a
+
+
+def _gat_table(t, rows, heads, name):
+    """(ptr, pitch) of a score table: at least ``rows`` rows of ``heads`` floats"""
+    ptr, ld = _rows2d(t, name)
+    if t.shape[0] < rows or t.shape[1] != heads:
+        raise ValueError("%s has shape %s, need (>=%d, %d)" % (name, tuple(t.shape), rows, heads))
+    return ptr, ld
+
+
+def gat_scores(x, a, heads=1):
+    """S (rows, 2 H): S[r, h] = u_r^h = sum_{c in head h} x[r, c] a[0, c] and S[r, H + h] = v_r^h with a[1] -- the learned
+    additive scores' two per-vertex scalars (sgcn_gat_scores_f32; one pass over x, a fixed summation order).  ``S[:, :H]`` and
+    ``S[:, H:]`` are the tables U and V of ``spgat``."""
+    xptr, ldx = _rows2d(x, "x")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    _gat_vec(a, d)
+    rows = int(x.shape[0])
+    S = torch.empty((rows, 2 * heads), dtype=torch.float32, device=x.device)
+    check(lib.sgcn_gat_scores_f32(xptr, ldx, rows, d, heads, a.data_ptr(), S.data_ptr(), _stream()))
+    return S
+
+
+def spgat(A, x, u, v, slope=0.2, out=None, want_lse=True, heads=1, keep=1.0, key=0):
+    """(out, lse): attention with learned additive scores over the stored pattern of the DeviceCSR ``A`` (M x K, unique column
+    ids per row) -- sgcn_spgat_csr_f32.  With z_ij = u[i] + v[j] per head and s_ij = z_ij > 0 ? z_ij : slope z_ij:
+    lse[i] = log sum_j exp(s_ij), out[i] = sum_j exp(s_ij - lse[i]) x[j]; an empty row gives +0.0 and -inf.  ``u`` (>= M, H)
+    and ``v`` (>= K, H) are score tables (views of ``gat_scores``' result serve).  lse is always (M, H).  ``out``, ``want_lse``,
+    ``heads``, ``keep`` and ``key`` as in ``spattn``."""
+    check_unique_cols(A)
+    keep = _attn_keep(keep)
+    slope = _attn_slope(slope)
+    M, K = A.shape
+    bptr, ldb = _rows2d(x, "x")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    if x.shape[0] < K:
+        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
+    uptr, ldu = _gat_table(u, M, heads, "u")
+    vptr, ldv = _gat_table(v, K, heads, "v")
+    if out is None:
+        out = _attn_out(M, d, x.device, heads)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != M or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
+    lse = torch.empty((M, heads), dtype=torch.float32, device=x.device) if want_lse else None
+    plan = A.plan.struct((d + 3) // 4 * 4 + 4 * heads) if A.plan is not None else None
+    check(lib.sgcn_spgat_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, int(key) & 0xFFFFFFFF, uptr, ldu, vptr,
+                                 ldv, bptr, ldb, slope, cptr, ldc, _ptr(lse), C.byref(plan) if plan is not None else None,
+                                 _stream()))
+    return out, lse
+
+
+def spgat_bwd(A, At, x, u, v, g, out_fwd, lse, slope=0.2, add=None, add_rows=0, heads=1, keep=1.0, key=0):
+    """(dB, dU, dV, delta), the gradient of ``spgat`` for g = dL/dout from the forward's ``out_fwd`` and ``lse`` --
+    sgcn_spgat_csr_bwd_u_f32 over ``A``, then sgcn_spgat_csr_bwd_v_f32 over ``At`` (the TRANSPOSED pattern, source rows
+    ascending).  dB (K x d, + add on its first ``add_rows`` rows) is the gradient with respect to ``x`` as the VALUES; dU
+    (M, H) and dV (K, H) those of the score tables, which ``gat_scores_bwd`` takes on to x and a.  Nothing nnz-sized is
+    stored, no atomics: bitwise reproducible."""
+    keep = _attn_keep(keep)
+    slope = _attn_slope(slope)
+    M, K = A.shape
+    if tuple(At.shape) != (K, M):
+        raise ValueError("At has shape %s, the transpose of %s is needed" % (tuple(At.shape), tuple(A.shape)))
+    bptr, ldb = _rows2d(x, "x")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    if x.shape[0] < K:
+        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
+    uptr, ldu = _gat_table(u, M, heads, "u")
+    vptr, ldv = _gat_table(v, K, heads, "v")
+    gptr, ldg = _rows2d(g, "g")
+    cptr, ldc = _rows2d(out_fwd, "out_fwd")
+    if tuple(g.shape) != (M, d) or out_fwd.shape[0] != M or out_fwd.shape[1] < d:
+        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (M, d, tuple(g.shape), tuple(out_fwd.shape)))
+    _dev(lse, torch.float32, "lse")
+    if tuple(lse.shape) != (M, heads) or not lse.is_contiguous():
+        raise ValueError("lse must be a contiguous (%d, %d) table of floats" % (M, heads))
+    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
+    add_rows = int(add_rows) if add is not None else 0
+    delta = torch.empty((M, heads), dtype=torch.float32, device=x.device)
+    dU = torch.empty((M, heads), dtype=torch.float32, device=x.device)
+    dV = torch.empty((K, heads), dtype=torch.float32, device=x.device)
+    dB = _attn_out(K, d, x.device, heads)
+    plan = A.plan.struct(8) if A.plan is not None else None
+    key = int(key) & 0xFFFFFFFF
+    check(lib.sgcn_spgat_csr_bwd_u_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, key, uptr, ldu, vptr, ldv, bptr,
+                                       ldb, slope, gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dU.data_ptr(),
+                                       C.byref(plan) if plan is not None else None, _stream()))
+    tplan = At.plan.struct((d + 3) // 4 * 4 + 8) if At.plan is not None else None
+    check(lib.sgcn_spgat_csr_bwd_v_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, uptr, ldu, vptr, ldv, bptr,
+                                       ldb, slope, gptr, ldg, lse.data_ptr(), delta.data_ptr(), dB.data_ptr(),
+                                       _rows2d(dB, "dB")[1], dV.data_ptr(), aptr, ldadd, add_rows,
+                                       C.byref(tplan) if tplan is not None else None, _stream()))
+    return dB, dU, dV, delta
+
+
+def gat_scores_bwd(x, a, dU, dV, dx=None, heads=1):
+    """da (2, d): da[0, c] = sum_r dU[r, h(c)] x[r, c] over the rows of ``dU`` and da[1, c] = sum_r dV[r, h(c)] x[r, c] over
+    those of ``dV`` (= the first rows of ``x``; dU may have fewer) -- sgcn_gat_scores_bwd_f32, a two-stage reduction whose
+    partition depends on the row count alone.  With ``dx`` (rows x d, pitched or not) the launch also ADDS the scores' share of
+    the input gradient into it: dx[r, c] += dU[r, h(c)] a[0, c] + dV[r, h(c)] a[1, c]; ``dx=None`` writes nothing but da."""
+    xptr, ldx = _rows2d(x, "x")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    _gat_vec(a, d)
+    for t, name in ((dU, "dU"), (dV, "dV")):
+        _dev(t, torch.float32, name)
+        if t.dim() != 2 or t.shape[1] != heads or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous (rows, %d) table of floats, got %s" % (name, heads, tuple(t.shape)))
+    rows, rows_u = int(dV.shape[0]), int(dU.shape[0])
+    if rows_u > rows or x.shape[0] < rows:
+        raise ValueError("dU has %d rows, dV %d, x %d: need rows(dU) <= rows(dV) <= rows(x)" % (rows_u, rows, x.shape[0]))
+    dxptr, lddx = (None, 0)
+    if dx is not None:
+        dxptr, lddx = _rows2d(dx, "dx")
+        if dx.shape[0] < rows or dx.shape[1] != d:
+            raise ValueError("dx has shape %s, need (>=%d, %d)" % (tuple(dx.shape), rows, d))
+    da = torch.empty((2, d), dtype=torch.float32, device=x.device)
+    nws = (rows + GAT_RED_ROWS - 1) // GAT_RED_ROWS * 2 * d
+    ws = torch.empty(max(nws, 1), dtype=torch.float32, device=x.device)
+    check(lib.sgcn_gat_scores_bwd_f32(xptr, ldx, rows, rows_u, d, heads, a.data_ptr(), dU.data_ptr(), dV.data_ptr(), dxptr, lddx,
+                                      da.data_ptr(), ws.data_ptr(), nws, _stream()))
+    return da
+
+
 def vr_aggregate(A, P, h, mu, Hbar, ifield, ffield, s, cvd, concat_self, out_h=None, out_mu=None):
     """Fused control-variate aggregator forward (sgcn_vr_aggregate_f32; sgcn_vr_aggregate_h16 on a bfloat16 history)."""
     n1, n0 = A.shape

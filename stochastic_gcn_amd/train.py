@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
-from .full_batch import (StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads,check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
+from .full_batch import (StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
@@ -241,6 +241,8 @@ class Trainer(object):
         self.attn_heads = check_attn_heads()
         # (--attn_dropout outside [0, 1), or set without attn: too)
         self.attn_dropout = check_attn_dropout()
+        # (--attn_score outside dot/gat, gat without attn or with --attn_scale, --attn_slope outside [0, 1] or set without gat: too)
+        self.attn_gat, self.attn_slope = check_attn_score()
         # (--feature_dtype bf16 without the bf16 GEMMs or without a full-graph mode: too; which model's table it selects)
         self.feature_bf16 = check_feature_dtype()
         # (--history_init exact / --history_refresh / --history_error without a history, with two of them, on several ranks: too)
