@@ -617,7 +617,7 @@ int sgcn_spattn_mh_csr_bwd_kv_f32(const int32_t* dev_t_rowptr, const int32_t* de
  *
  * keep must be finite and in (0, 1] -- SGCN_ERR_INVALID otherwise, before any HIP call, beside everything the multi-head
  * calls refuse.  keep == 1 runs the kernels of the calls above (the same instantiations, the same bits); keep < 1 runs their
- * dropout instantiations. */
+ * dropout instantiations.  (The Python package's ops.spattn / spattn_bwd call these three for every heads and keep.) */
 #define SGCN_ATTN_SITE 0x4154544E
 int sgcn_spattn_drop_csr_f32(const int32_t* dev_rowptr, const int32_t* dev_col, int32_t M, int32_t K, int32_t d, int32_t heads,
                              float keep, uint32_t key, const float* dev_Q, int64_t ldq, const float* dev_B, int64_t ldb,

@@ -1,6 +1,8 @@
 // What the attention kernels over a CSR pattern share (sgcn_spattn.hip: dot-product scores; sgcn_spgat.hip: learned additive
-// scores): the kernel arguments, the coefficient mask, the lane geometry, the reductions over a group or a head, the forward
-// slots' ordered fix-up, the backward's epilogue and the host-side checks -- moved here verbatim from sgcn_spattn.hip.
+// scores).  Device: the kernel arguments, the coefficient mask, a lane's share of a row, the reductions over a group or a
+// head, the forward slots' ordered fix-up, the backward's epilogue.  Host: the slot widths, the checks every export opens
+// with, and the one path from checked arguments to a launch -- geometry, dispatch ladder, fix-up -- which each translation
+// unit instantiates with a launcher for its own kernels.
 #pragma once
 #include <cmath>
 #include "sgcn_dev.h"
@@ -316,13 +318,6 @@ AttnDrop drop_of(float keep, uint32_t key) {
     return dm;
 }
 
-template <bool MH>
-void launch_fix(int vw, dim3 grid, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
-    if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-    else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-    else hipLaunchKernelGGL((spattn_fix_kernel<1, MH>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-}
-
 int plan_ok(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw) {
     SGCN_REQUIRE(plan->dev_seg && plan->nseg >= nrows, "%s: malformed plan", who);
     if (plan->nfix > 0) {
@@ -333,7 +328,133 @@ int plan_ok(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw
     return SGCN_OK;
 }
 
+// ---- the slots of a split row (ops.attn_slot mirrors these four) -----------------------------------------------------------
+constexpr int kScalarSlot = 8;   // floats a GAT backward slot keeps for the per-head scalar sums (H <= 8)
 inline int64_t ceil4(int64_t d) { return (d + 3) / 4 * 4; }
+// forward, both score kinds: the accumulator on a 16-byte pitch, then one vector (m, l, -, -) per head
+inline int64_t fwd_slot(int32_t d, int32_t heads) { return ceil4(d) + 4 * (int64_t)heads; }
+inline int64_t bwd_slot(int32_t d) { return ceil4(d); }                         // dot-product bwd_q / bwd_kv: the row
+constexpr int64_t kGatBwdUSlot = kScalarSlot;                                   // GAT bwd_u: the heads' dU alone
+inline int64_t gat_bwd_v_slot(int32_t d) { return ceil4(d) + kScalarSlot; }     // GAT bwd_v: the row, then the heads' dV
+
+// ---- what the six host bodies open with ------------------------------------------------------------------------------------
+// first: the sizes, the width, the heads and the mask's keep
+inline int attn_open(const char* who, int32_t M, int32_t K, int32_t d, int32_t heads, float keep) {
+    SGCN_REQUIRE(M >= 0 && K >= 0, "%s: negative size", who);
+    SGCN_REQUIRE(d > 0, "%s: d must be positive (got %d)", who, d);
+    if (const int rc = heads_ok(who, d, heads)) return rc;
+    return keep_ok(who, keep);
+}
+
+// the workspace of a plan with split rows -- an operand like the others where its slots hold vectors -- else null
+inline const void* split_ws(const sgcn_plan_t* plan) { return plan && plan->nfix > 0 ? plan->dev_ws : nullptr; }
+
+// last, after the body's own operand checks: the plan against its slot width `ldw`, then the call's vector width -- the widest
+// these operands allow that no head straddles -- and the row width it can hold
+inline int attn_plan_width(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw, int32_t d, int32_t heads,
+                           std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds, int& vw) {
+    if (plan)
+        if (const int rc = plan_ok(who, plan, nrows, ldw)) return rc;
+    vw = head_vw(pick_vw(d, ptrs, lds), d, heads);
+    return width_ok(who, d, vw, heads);
+}
+
+// ---- one launch ------------------------------------------------------------------------------------------------------------
+// The lane geometry of a launch: G lanes per row segment and NV vectors per lane from d, vw and heads; fills what the kernels
+// read of it (nvec, ragged, heads, gh, nvh).  One head: the row kernels' group for nvec vectors (group_lanes), past 64 lanes
+// NV = ceil(nvec / 64).  Several: the smallest group whose sub-groups of G / heads lanes hold a head's nvh vectors one per
+// lane, at least 8 lanes; past 64 lanes the sub-group is 64 / heads and a lane takes NV = ceil(nvh / Gh) <= 4 of them
+// (heads * nvh <= 256, width_ok).
+inline void attn_geometry(AttnArgs& a, int vw, int32_t heads, int& G, int& NV) {
+    a.nvec = (a.d + vw - 1) / vw;
+    a.ragged = a.d % vw != 0;
+    a.heads = heads;
+    if (heads == 1) {
+        G = group_lanes(a.nvec);
+        NV = G == 64 ? (a.nvec + 63) / 64 : 1;
+        a.gh = G; a.nvh = a.nvec;
+    } else {
+        a.nvh = a.d / heads / vw;
+        int p = 1;
+        while (p < a.nvh) p <<= 1;
+        if (p * heads <= 64) { G = p * heads < 8 ? 8 : p * heads; NV = 1; }
+        else { G = 64; NV = (a.nvh + 64 / heads - 1) / (64 / heads); }
+        a.gh = G / heads;
+    }
+}
+
+// The ladder over (DR, MH, VW, G, NV).  L is a translation unit's launcher for one kind of launch:
+//   template <int G, int NV, int VW, bool MH, bool DR> static void launch(dim3 grid, hipStream_t, const KA&... the kernel's arguments)
+//   static void fix(int vw, const AttnArgs&, const sgcn_plan_t*, hipStream_t, const X&... what it has beside them)
+//   static constexpr int64_t max_fix: the split rows its fix-up's grid can count
+template <class L, int VW, bool MH, bool DR, class... KA>
+bool dispatch_gnv(int G, int NV, dim3 grid, hipStream_t st, const KA&... ka) {
+    switch (G) {
+        case 8: L::template launch<8, 1, VW, MH, DR>(grid, st, ka...); return true;
+        case 16: L::template launch<16, 1, VW, MH, DR>(grid, st, ka...); return true;
+        case 32: L::template launch<32, 1, VW, MH, DR>(grid, st, ka...); return true;
+        case 64:
+            switch (NV) {
+                case 1: L::template launch<64, 1, VW, MH, DR>(grid, st, ka...); return true;
+                case 2: L::template launch<64, 2, VW, MH, DR>(grid, st, ka...); return true;
+                case 3: L::template launch<64, 3, VW, MH, DR>(grid, st, ka...); return true;
+                case 4: L::template launch<64, 4, VW, MH, DR>(grid, st, ka...); return true;
+            }
+    }
+    return false;
+}
+
+template <class L, bool MH, bool DR, class... KA>
+bool dispatch_vw(int vw, int G, int NV, dim3 grid, hipStream_t st, const KA&... ka) {
+    if (vw == 4) return dispatch_gnv<L, 4, MH, DR>(G, NV, grid, st, ka...);
+    if (vw == 2) return dispatch_gnv<L, 2, MH, DR>(G, NV, grid, st, ka...);
+    return dispatch_gnv<L, 1, MH, DR>(G, NV, grid, st, ka...);
+}
+
+// A launch from its checked arguments: the segments and the slots from the plan, the geometry, the kernel off the ladder (the
+// kernels take a, x..., dm), then L's fix-up where the plan has split rows.  dm.mk == 0 (drop_of: keep == 1) and heads == 1
+// select the DR = false and the MH = false kernels.
+template <class L, class... X>
+int attn_run(const char* who, AttnArgs& a, int32_t nrows, const sgcn_plan_t* plan, int64_t ldw, int vw, int32_t heads,
+             const AttnDrop& dm, hipStream_t st, const X&... x) {
+    a.nseg = nrows;
+    if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
+    const bool split = plan && plan->nfix > 0;
+    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
+    int G, NV;
+    attn_geometry(a, vw, heads, G, NV);
+    const int64_t nblocks = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
+    SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
+
+    const dim3 grid((unsigned)nblocks);
+    const bool drop = dm.mk > 0.f;
+    const bool ok = drop ? (heads == 1 ? dispatch_vw<L, false, true>(vw, G, NV, grid, st, a, x..., dm)
+                                       : dispatch_vw<L, true, true>(vw, G, NV, grid, st, a, x..., dm))
+                         : (heads == 1 ? dispatch_vw<L, false, false>(vw, G, NV, grid, st, a, x..., dm)
+                                       : dispatch_vw<L, true, false>(vw, G, NV, grid, st, a, x..., dm));
+    SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
+    SGCN_HIP_TRY(hipGetLastError());
+
+    if (split) {
+        SGCN_REQUIRE(plan->nfix < L::max_fix, "%s: too many split rows", who);
+        L::fix(vw, a, plan, st, x...);
+        SGCN_HIP_TRY(hipGetLastError());
+    }
+    return SGCN_OK;
+}
+
+// the forward's fix-up of both score kinds, one workgroup per split row: nvec <= 256 = kBlock threads
+template <bool MH>
+void launch_fix(int vw, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
+    const dim3 grid((unsigned)plan->nfix), block(kBlock);
+    if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
+    else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
+    else hipLaunchKernelGGL((spattn_fix_kernel<1, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
+}
+inline void launch_fwd_fix(int vw, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
+    if (a.heads == 1) launch_fix<false>(vw, a, plan, st);
+    else launch_fix<true>(vw, a, plan, st);
+}
 
 }  // namespace
 }  // namespace sgcn

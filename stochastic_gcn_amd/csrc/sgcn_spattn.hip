@@ -39,8 +39,10 @@
 // a template parameter, not a run-time branch, and the mask travels in a second kernel argument that the DR = false
 // kernels never read: their device code is, instruction for instruction, the code they had before DR existed.
 //
-// The arguments, the mask, the lane geometry, the reductions, the forward's fix-up kernel, the backward's epilogue and the host
-// checks live in sgcn_attn_dev.h, which sgcn_spgat.hip (learned additive scores) shares.
+// This file holds the three pattern kernels, the backward's fix-up kernel, the launcher that names them (Dot) and the exports'
+// own operand checks.  The arguments, the mask, a lane's share of a row, the reductions, the forward's fix-up kernel and the
+// backward's epilogue live in sgcn_attn_dev.h, and so does the whole host path from checked arguments to a launch -- slot widths,
+// opening checks, lane geometry, dispatch ladder, fix-up step (attn_run) -- which sgcn_spgat.hip (learned additive scores) shares.
 #include <cmath>
 #include "sgcn_attn_dev.h"
 
@@ -357,90 +359,30 @@ __global__ __launch_bounds__(kBlock) void spattn_bwd_fix_kernel(AttnArgs a, cons
     bwd_store<VW>(a, fx.row, vi, acc, mul);
 }
 
+// the launcher attn_run (sgcn_attn_dev.h) takes: the kernel and the fix-up of one kind of launch
 enum Kind { FWD, BWD_Q, BWD_KV };
 
-template <int KIND, int G, int NV, int VW, bool MH, bool DR>
-void launch_seg(const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
-    const dim3 grid((unsigned)nblocks), block(kBlock);
-    if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
-    else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
-    else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
-}
-
-template <int KIND, int VW, bool MH, bool DR>
-bool dispatch_gnv(int G, int NV, const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
-    switch (G) {
-        case 8: launch_seg<KIND, 8, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
-        case 16: launch_seg<KIND, 16, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
-        case 32: launch_seg<KIND, 32, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
-        case 64:
-            switch (NV) {
-                case 1: launch_seg<KIND, 64, 1, VW, MH, DR>(a, dm, nblocks, st); return true;
-                case 2: launch_seg<KIND, 64, 2, VW, MH, DR>(a, dm, nblocks, st); return true;
-                case 3: launch_seg<KIND, 64, 3, VW, MH, DR>(a, dm, nblocks, st); return true;
-                case 4: launch_seg<KIND, 64, 4, VW, MH, DR>(a, dm, nblocks, st); return true;
-            }
-    }
-    return false;
-}
-
-template <int KIND, bool MH, bool DR>
-bool dispatch_vw(int vw, int G, int NV, const AttnArgs& a, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
-    if (vw == 4) return dispatch_gnv<KIND, 4, MH, DR>(G, NV, a, dm, nblocks, st);
-    if (vw == 2) return dispatch_gnv<KIND, 2, MH, DR>(G, NV, a, dm, nblocks, st);
-    return dispatch_gnv<KIND, 1, MH, DR>(G, NV, a, dm, nblocks, st);
-}
-
 template <int KIND>
-int run(AttnArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, int32_t heads, const AttnDrop& dm, hipStream_t st) {
-    a.nseg = nrows;
-    if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
-    a.nvec = (a.d + vw - 1) / vw;
-    a.ragged = a.d % vw != 0;
-    a.heads = heads;
-    int G, NV;
-    if (heads == 1) {
-        G = group_lanes(a.nvec);
-        NV = G == 64 ? (a.nvec + 63) / 64 : 1;
-        a.gh = G; a.nvh = a.nvec;
-    } else {
-        // the smallest group whose sub-groups of G / heads lanes hold a head's nvh vectors one per lane; past 64 lanes the
-        // sub-group is 64 / heads and a lane takes NV = ceil(nvh / Gh) <= 4 of them (heads * nvh <= 256, width_ok)
-        a.nvh = a.d / heads / vw;
-        int p = 1;
-        while (p < a.nvh) p <<= 1;
-        if (p * heads <= 64) { G = p * heads < 8 ? 8 : p * heads; NV = 1; }
-        else { G = 64; NV = (a.nvh + 64 / heads - 1) / (64 / heads); }
-        a.gh = G / heads;
+struct Dot {
+    static constexpr int64_t max_fix = 1ll << 31;
+    template <int G, int NV, int VW, bool MH, bool DR>
+    static void launch(dim3 grid, hipStream_t st, const AttnArgs& a, const AttnDrop& dm) {
+        const dim3 block(kBlock);
+        if constexpr (KIND == FWD) hipLaunchKernelGGL((spattn_seg_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
+        else if constexpr (KIND == BWD_Q) hipLaunchKernelGGL((spattn_bwd_q_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
+        else hipLaunchKernelGGL((spattn_bwd_kv_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, dm);
     }
-    const int64_t nblocks = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
-    SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
-
-    const bool drop = dm.mk > 0.f;
-    const bool ok = drop ? (heads == 1 ? dispatch_vw<KIND, false, true>(vw, G, NV, a, dm, nblocks, st)
-                                       : dispatch_vw<KIND, true, true>(vw, G, NV, a, dm, nblocks, st))
-                         : (heads == 1 ? dispatch_vw<KIND, false, false>(vw, G, NV, a, dm, nblocks, st)
-                                       : dispatch_vw<KIND, true, false>(vw, G, NV, a, dm, nblocks, st));
-    SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
-    SGCN_HIP_TRY(hipGetLastError());
-
-    if (plan && plan->nfix > 0) {
-        SGCN_REQUIRE(plan->nfix < (1ll << 31), "%s: too many split rows", who);
-        dim3 grid((unsigned)plan->nfix);      // one workgroup per split row: nvec <= 256 = kBlock threads
-        if constexpr (KIND == FWD) {
-            if (heads == 1) launch_fix<false>(vw, grid, a, plan, st);
-            else launch_fix<true>(vw, grid, a, plan, st);
-        } else {
+    static void fix(int vw, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
+        if constexpr (KIND == FWD) launch_fwd_fix(vw, a, plan, st);
+        else {
+            const dim3 grid((unsigned)plan->nfix), block(kBlock);      // one workgroup per split row: nvec <= 256 = kBlock threads
             const float mul = KIND == BWD_Q ? a.scale : 1.f;
-            if (vw == 4) hipLaunchKernelGGL((spattn_bwd_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
-            else if (vw == 2) hipLaunchKernelGGL((spattn_bwd_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
-            else hipLaunchKernelGGL((spattn_bwd_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix, mul);
+            if (vw == 4) hipLaunchKernelGGL((spattn_bwd_fix_kernel<4>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
+            else if (vw == 2) hipLaunchKernelGGL((spattn_bwd_fix_kernel<2>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
+            else hipLaunchKernelGGL((spattn_bwd_fix_kernel<1>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
         }
-        SGCN_HIP_TRY(hipGetLastError());
     }
-    return SGCN_OK;
-}
-
+};
 
 }  // namespace
 }  // namespace sgcn
@@ -453,26 +395,19 @@ using namespace sgcn;
 static int spattn_fwd(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
                       float keep, uint32_t key, const float* Q, int64_t ldq, const float* B, int64_t ldb, float scale,
                       float* C, int64_t ldc, float* lse, const sgcn_plan_t* plan, void* stream) {
-    SGCN_REQUIRE(M >= 0 && K >= 0, "spattn: negative size");
-    SGCN_REQUIRE(d > 0, "spattn: d must be positive (got %d)", d);
-    { const int rc = heads_ok("spattn", d, heads); if (rc) return rc; }
-    { const int rc = keep_ok("spattn", keep); if (rc) return rc; }
+    if (const int rc = attn_open("spattn", M, K, d, heads, keep)) return rc;
     SGCN_REQUIRE(rowptr && C && (Q || M == 0) && (B || K == 0), "spattn: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldc >= d, "spattn: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn: scale must be finite");
-    // a slot: the accumulator on a 16-byte pitch, then one vector (m, l, -, -) per head
-    const int64_t ldw = ceil4(d) + 4 * (int64_t)heads;
-    if (plan) { const int rc = plan_ok("spattn", plan, M, ldw); if (rc) return rc; }
-    const bool split = plan && plan->nfix > 0;
-    const int vw = head_vw(pick_vw(d, {Q, B, C, split ? (const void*)plan->dev_ws : nullptr}, {ldq, ldb, ldc}), d, heads);
-    { const int rc = width_ok("spattn", d, vw, heads); if (rc) return rc; }
+    const int64_t ldw = fwd_slot(d, heads);
+    int vw;
+    if (const int rc = attn_plan_width("spattn", plan, M, ldw, d, heads, {Q, B, C, split_ws(plan)}, {ldq, ldb, ldc}, vw)) return rc;
     if (M == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = rowptr; a.col = col; a.own = Q; a.ldown = ldq; a.gat = B; a.ldgat = ldb; a.out = C; a.ldo = ldc;
     a.lse_out = lse; a.scale = scale; a.d = d;
-    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
-    return run<FWD>(a, "spattn", M, plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
+    return attn_run<Dot<FWD>>("spattn", a, M, plan, ldw, vw, heads, drop_of(keep, key), (hipStream_t)stream);
 }
 
 static int spattn_bwd_q(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d, int32_t heads,
@@ -480,29 +415,23 @@ static int spattn_bwd_q(const int32_t* rowptr, const int32_t* col, int32_t M, in
                         const float* G, int64_t ldg, const float* C, int64_t ldc, const float* lse,
                         float* delta, float* dQ, int64_t lddq, const float* add, int64_t ldadd,
                         int32_t add_rows, const sgcn_plan_t* plan, void* stream) {
-    SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_q: negative size");
-    SGCN_REQUIRE(d > 0, "spattn_bwd_q: d must be positive (got %d)", d);
-    { const int rc = heads_ok("spattn_bwd_q", d, heads); if (rc) return rc; }
-    { const int rc = keep_ok("spattn_bwd_q", keep); if (rc) return rc; }
+    if (const int rc = attn_open("spattn_bwd_q", M, K, d, heads, keep)) return rc;
     SGCN_REQUIRE(rowptr && dQ && ((Q && G && C && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_q: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && ldc >= d && lddq >= d, "spattn_bwd_q: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_q: scale must be finite");
     const bool with_add = add && add_rows > 0;
     if (with_add) SGCN_REQUIRE(ldadd >= d && add_rows <= M, "spattn_bwd_q: bad addend");
-    const int64_t ldw = ceil4(d);
-    if (plan) { const int rc = plan_ok("spattn_bwd_q", plan, M, ldw); if (rc) return rc; }
-    const bool split = plan && plan->nfix > 0;
-    const int vw = head_vw(pick_vw(d, {Q, B, G, C, dQ, with_add ? add : nullptr, split ? (const void*)plan->dev_ws : nullptr},
-                                   {ldq, ldb, ldg, ldc, lddq, with_add ? ldadd : lddq}), d, heads);
-    { const int rc = width_ok("spattn_bwd_q", d, vw, heads); if (rc) return rc; }
+    int vw;
+    if (const int rc = attn_plan_width("spattn_bwd_q", plan, M, bwd_slot(d), d, heads,
+                                       {Q, B, G, C, dQ, with_add ? add : nullptr, split_ws(plan)},
+                                       {ldq, ldb, ldg, ldc, lddq, with_add ? ldadd : lddq}, vw)) return rc;
     if (M == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = rowptr; a.col = col; a.own = Q; a.ldown = ldq; a.gat = B; a.ldgat = ldb; a.G = G; a.ldg = ldg;
     a.Cf = C; a.ldcf = ldc; a.lse = lse; a.delta_out = delta; a.out = dQ; a.ldo = lddq; a.scale = scale; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
-    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
-    return run<BWD_Q>(a, "spattn_bwd_q", M, plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
+    return attn_run<Dot<BWD_Q>>("spattn_bwd_q", a, M, plan, bwd_slot(d), vw, heads, drop_of(keep, key), (hipStream_t)stream);
 }
 
 static int spattn_bwd_kv(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d, int32_t heads,
@@ -510,29 +439,23 @@ static int spattn_bwd_kv(const int32_t* t_rowptr, const int32_t* t_row, int32_t 
                          const float* G, int64_t ldg, const float* lse, const float* delta,
                          float* dB, int64_t lddb, const float* add, int64_t ldadd, int32_t add_rows,
                          const sgcn_plan_t* t_plan, void* stream) {
-    SGCN_REQUIRE(M >= 0 && K >= 0, "spattn_bwd_kv: negative size");
-    SGCN_REQUIRE(d > 0, "spattn_bwd_kv: d must be positive (got %d)", d);
-    { const int rc = heads_ok("spattn_bwd_kv", d, heads); if (rc) return rc; }
-    { const int rc = keep_ok("spattn_bwd_kv", keep); if (rc) return rc; }
+    if (const int rc = attn_open("spattn_bwd_kv", M, K, d, heads, keep)) return rc;
     SGCN_REQUIRE(t_rowptr && dB && ((Q && G && lse && delta) || M == 0) && (B || K == 0), "spattn_bwd_kv: null operand");
     SGCN_REQUIRE(ldq >= d && ldb >= d && ldg >= d && lddb >= d, "spattn_bwd_kv: leading dimension smaller than d");
     SGCN_REQUIRE(std::isfinite(scale), "spattn_bwd_kv: scale must be finite");
     const bool with_add = add && add_rows > 0;
     if (with_add) SGCN_REQUIRE(ldadd >= d && add_rows <= K, "spattn_bwd_kv: bad addend");
-    const int64_t ldw = ceil4(d);
-    if (t_plan) { const int rc = plan_ok("spattn_bwd_kv", t_plan, K, ldw); if (rc) return rc; }
-    const bool split = t_plan && t_plan->nfix > 0;
-    const int vw = head_vw(pick_vw(d, {Q, B, G, dB, with_add ? add : nullptr, split ? (const void*)t_plan->dev_ws : nullptr},
-                                   {ldq, ldb, ldg, lddb, with_add ? ldadd : lddb}), d, heads);
-    { const int rc = width_ok("spattn_bwd_kv", d, vw, heads); if (rc) return rc; }
+    int vw;
+    if (const int rc = attn_plan_width("spattn_bwd_kv", t_plan, K, bwd_slot(d), d, heads,
+                                       {Q, B, G, dB, with_add ? add : nullptr, split_ws(t_plan)},
+                                       {ldq, ldb, ldg, lddb, with_add ? ldadd : lddb}, vw)) return rc;
     if (K == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = t_rowptr; a.col = t_row; a.own = B; a.ldown = ldb; a.gat = Q; a.ldgat = ldq; a.G = G; a.ldg = ldg;
     a.lse = lse; a.delta = delta; a.out = dB; a.ldo = lddb; a.scale = scale; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
-    if (split) { a.ws = t_plan->dev_ws; a.ldw = ldw; }
-    return run<BWD_KV>(a, "spattn_bwd_kv", K, t_plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
+    return attn_run<Dot<BWD_KV>>("spattn_bwd_kv", a, K, t_plan, bwd_slot(d), vw, heads, drop_of(keep, key), (hipStream_t)stream);
 }
 
 extern "C" int sgcn_spattn_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,

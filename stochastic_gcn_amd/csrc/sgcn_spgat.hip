@@ -15,6 +15,8 @@
 // backward launch carries one more per-lane scalar sum (dU, dV), which a split row keeps in its slot beside the row.
 // delta and t go through the SAME reduction tree in the same per-lane order, so where C[i] holds the bits of one B[j] (a
 // saturated softmax) t - delta is exactly 0 for it.  Nothing nnz-sized is written and there are no atomics.
+// The host side is sgcn_attn_dev.h's as well: slot widths, opening checks, lane geometry, dispatch ladder and fix-up step
+// (attn_run); this file adds the launcher that names its kernels (Gat), slope_ok and each export's own operand checks.
 #include <cmath>
 #include "sgcn_attn_dev.h"
 
@@ -31,8 +33,6 @@ struct GatX {
     float* dU;               // bwd_u: M x H, contiguous
     float* dV;               // bwd_v: K x H, contiguous
 };
-
-constexpr int kScalarSlot = 8;   // floats a backward slot keeps for the per-head scalar sums (H <= 8)
 
 __device__ __forceinline__ float leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
 __device__ __forceinline__ float leaky_d(float z, float slope) { return z > 0.f ? 1.f : slope; }
@@ -426,91 +426,32 @@ __global__ __launch_bounds__(kBlock) void gat_da_reduce_kernel(const float* __re
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
+// the launcher attn_run (sgcn_attn_dev.h) takes: the kernel and the fix-up of one kind of launch
 enum GatKind { GAT_FWD, GAT_BWD_U, GAT_BWD_V };
 
-template <int KIND, int G, int NV, int VW, bool MH, bool DR>
-void gat_launch_seg(const AttnArgs& a, const GatX& x, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
-    const dim3 grid((unsigned)nblocks), block(kBlock);
-    if constexpr (KIND == GAT_FWD) hipLaunchKernelGGL((spgat_seg_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, x, dm);
-    else if constexpr (KIND == GAT_BWD_U) hipLaunchKernelGGL((spgat_bwd_u_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, x, dm);
-    else hipLaunchKernelGGL((spgat_bwd_v_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, x, dm);
-}
-
-template <int KIND, int VW, bool MH, bool DR>
-bool gat_dispatch_gnv(int G, int NV, const AttnArgs& a, const GatX& x, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
-    switch (G) {
-        case 8: gat_launch_seg<KIND, 8, 1, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-        case 16: gat_launch_seg<KIND, 16, 1, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-        case 32: gat_launch_seg<KIND, 32, 1, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-        case 64:
-            switch (NV) {
-                case 1: gat_launch_seg<KIND, 64, 1, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-                case 2: gat_launch_seg<KIND, 64, 2, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-                case 3: gat_launch_seg<KIND, 64, 3, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-                case 4: gat_launch_seg<KIND, 64, 4, VW, MH, DR>(a, x, dm, nblocks, st); return true;
-            }
-    }
-    return false;
-}
-
-template <int KIND, bool MH, bool DR>
-bool gat_dispatch_vw(int vw, int G, int NV, const AttnArgs& a, const GatX& x, const AttnDrop& dm, int64_t nblocks, hipStream_t st) {
-    if (vw == 4) return gat_dispatch_gnv<KIND, 4, MH, DR>(G, NV, a, x, dm, nblocks, st);
-    if (vw == 2) return gat_dispatch_gnv<KIND, 2, MH, DR>(G, NV, a, x, dm, nblocks, st);
-    return gat_dispatch_gnv<KIND, 1, MH, DR>(G, NV, a, x, dm, nblocks, st);
-}
-
-// the geometry of sgcn_spattn.hip's `run`, the GAT kernels and their fix-ups
 template <int KIND>
-int gat_run(AttnArgs& a, const GatX& x, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, int32_t heads,
-            const AttnDrop& dm, hipStream_t st) {
-    a.nseg = nrows;
-    if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
-    a.nvec = (a.d + vw - 1) / vw;
-    a.ragged = a.d % vw != 0;
-    a.heads = heads;
-    int G, NV;
-    if (heads == 1) {
-        G = group_lanes(a.nvec);
-        NV = G == 64 ? (a.nvec + 63) / 64 : 1;
-        a.gh = G; a.nvh = a.nvec;
-    } else {
-        a.nvh = a.d / heads / vw;
-        int p = 1;
-        while (p < a.nvh) p <<= 1;
-        if (p * heads <= 64) { G = p * heads < 8 ? 8 : p * heads; NV = 1; }
-        else { G = 64; NV = (a.nvh + 64 / heads - 1) / (64 / heads); }
-        a.gh = G / heads;
+struct Gat {
+    static constexpr int64_t max_fix = (1ll << 31) / 8;      // (bwd_u's fix-up counts nfix * heads threads)
+    template <int G, int NV, int VW, bool MH, bool DR>
+    static void launch(dim3 grid, hipStream_t st, const AttnArgs& a, const GatX& x, const AttnDrop& dm) {
+        const dim3 block(kBlock);
+        if constexpr (KIND == GAT_FWD) hipLaunchKernelGGL((spgat_seg_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, x, dm);
+        else if constexpr (KIND == GAT_BWD_U) hipLaunchKernelGGL((spgat_bwd_u_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, x, dm);
+        else hipLaunchKernelGGL((spgat_bwd_v_kernel<G, NV, VW, MH, DR>), grid, block, 0, st, a, x, dm);
     }
-    const int64_t nblocks = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
-    SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
-
-    const bool drop = dm.mk > 0.f;
-    const bool ok = drop ? (heads == 1 ? gat_dispatch_vw<KIND, false, true>(vw, G, NV, a, x, dm, nblocks, st)
-                                       : gat_dispatch_vw<KIND, true, true>(vw, G, NV, a, x, dm, nblocks, st))
-                         : (heads == 1 ? gat_dispatch_vw<KIND, false, false>(vw, G, NV, a, x, dm, nblocks, st)
-                                       : gat_dispatch_vw<KIND, true, false>(vw, G, NV, a, x, dm, nblocks, st));
-    SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
-    SGCN_HIP_TRY(hipGetLastError());
-
-    if (plan && plan->nfix > 0) {
-        SGCN_REQUIRE(plan->nfix < (1ll << 31) / 8, "%s: too many split rows", who);
-        dim3 grid((unsigned)plan->nfix);      // one workgroup per split row: nvec <= 256 = kBlock threads
-        if constexpr (KIND == GAT_FWD) {
-            if (heads == 1) launch_fix<false>(vw, grid, a, plan, st);
-            else launch_fix<true>(vw, grid, a, plan, st);
-        } else if constexpr (KIND == GAT_BWD_U) {
-            const dim3 g1((unsigned)((plan->nfix * heads + kBlock - 1) / kBlock));
+    static void fix(int vw, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st, const GatX& x) {
+        if constexpr (KIND == GAT_FWD) launch_fwd_fix(vw, a, plan, st);
+        else if constexpr (KIND == GAT_BWD_U) {
+            const dim3 g1((unsigned)((plan->nfix * a.heads + kBlock - 1) / kBlock));
             hipLaunchKernelGGL(spgat_bwd_u_fix_kernel, g1, dim3(kBlock), 0, st, a, x, plan->dev_fix, plan->nfix);
         } else {
-            if (vw == 4) hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, x, plan->dev_fix, plan->nfix);
-            else if (vw == 2) hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, x, plan->dev_fix, plan->nfix);
-            else hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, x, plan->dev_fix, plan->nfix);
+            const dim3 grid((unsigned)plan->nfix), block(kBlock);      // one workgroup per split row: nvec <= 256 = kBlock threads
+            if (vw == 4) hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<4>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
+            else if (vw == 2) hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<2>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
+            else hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<1>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
         }
-        SGCN_HIP_TRY(hipGetLastError());
     }
-    return SGCN_OK;
-}
+};
 
 int slope_ok(const char* who, float slope) {
     SGCN_REQUIRE(std::isfinite(slope) && slope >= 0.f && slope <= 1.f, "%s: slope must lie in [0, 1] (got %g)", who, (double)slope);
@@ -540,27 +481,21 @@ extern "C" int sgcn_spgat_csr_f32(const int32_t* rowptr, const int32_t* col, int
                                   float keep, uint32_t key, const float* U, int64_t ldu, const float* V, int64_t ldv,
                                   const float* B, int64_t ldb, float slope, float* C, int64_t ldc, float* lse,
                                   const sgcn_plan_t* plan, void* stream) {
-    SGCN_REQUIRE(M >= 0 && K >= 0, "spgat: negative size");
-    SGCN_REQUIRE(d > 0, "spgat: d must be positive (got %d)", d);
-    { const int rc = heads_ok("spgat", d, heads); if (rc) return rc; }
-    { const int rc = keep_ok("spgat", keep); if (rc) return rc; }
-    { const int rc = slope_ok("spgat", slope); if (rc) return rc; }
+    if (const int rc = attn_open("spgat", M, K, d, heads, keep)) return rc;
+    if (const int rc = slope_ok("spgat", slope)) return rc;
     SGCN_REQUIRE(rowptr && C && (U || M == 0) && ((B && V) || K == 0), "spgat: null operand");
     SGCN_REQUIRE(ldb >= d && ldc >= d, "spgat: leading dimension smaller than d");
     SGCN_REQUIRE(ldu >= heads && ldv >= heads, "spgat: score table pitch smaller than heads");
-    const int64_t ldw = ceil4(d) + 4 * (int64_t)heads;      // the forward slot of sgcn_spattn_mh_csr_f32
-    if (plan) { const int rc = plan_ok("spgat", plan, M, ldw); if (rc) return rc; }
-    const bool split = plan && plan->nfix > 0;
-    const int vw = head_vw(pick_vw(d, {B, C, split ? (const void*)plan->dev_ws : nullptr}, {ldb, ldc}), d, heads);
-    { const int rc = width_ok("spgat", d, vw, heads); if (rc) return rc; }
+    const int64_t ldw = fwd_slot(d, heads);                  // the forward slot of sgcn_spattn_mh_csr_f32
+    int vw;
+    if (const int rc = attn_plan_width("spgat", plan, M, ldw, d, heads, {B, C, split_ws(plan)}, {ldb, ldc}, vw)) return rc;
     if (M == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = rowptr; a.col = col; a.gat = B; a.ldgat = ldb; a.out = C; a.ldo = ldc; a.lse_out = lse; a.d = d;
-    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
     GatX x{};
     x.U = U; x.ldu = ldu; x.V = V; x.ldv = ldv; x.slope = slope;
-    return gat_run<GAT_FWD>(a, x, "spgat", M, plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
+    return attn_run<Gat<GAT_FWD>>("spgat", a, M, plan, ldw, vw, heads, drop_of(keep, key), (hipStream_t)stream, x);
 }
 
 extern "C" int sgcn_spgat_csr_bwd_u_f32(const int32_t* rowptr, const int32_t* col, int32_t M, int32_t K, int32_t d,
@@ -568,28 +503,21 @@ extern "C" int sgcn_spgat_csr_bwd_u_f32(const int32_t* rowptr, const int32_t* co
                                         int64_t ldv, const float* B, int64_t ldb, float slope, const float* G, int64_t ldg,
                                         const float* C, int64_t ldc, const float* lse, float* delta, float* dU,
                                         const sgcn_plan_t* plan, void* stream) {
-    SGCN_REQUIRE(M >= 0 && K >= 0, "spgat_bwd_u: negative size");
-    SGCN_REQUIRE(d > 0, "spgat_bwd_u: d must be positive (got %d)", d);
-    { const int rc = heads_ok("spgat_bwd_u", d, heads); if (rc) return rc; }
-    { const int rc = keep_ok("spgat_bwd_u", keep); if (rc) return rc; }
-    { const int rc = slope_ok("spgat_bwd_u", slope); if (rc) return rc; }
+    if (const int rc = attn_open("spgat_bwd_u", M, K, d, heads, keep)) return rc;
+    if (const int rc = slope_ok("spgat_bwd_u", slope)) return rc;
     SGCN_REQUIRE(rowptr && ((U && G && C && lse && delta && dU) || M == 0) && ((B && V) || K == 0), "spgat_bwd_u: null operand");
     SGCN_REQUIRE(ldb >= d && ldg >= d && ldc >= d, "spgat_bwd_u: leading dimension smaller than d");
     SGCN_REQUIRE(ldu >= heads && ldv >= heads, "spgat_bwd_u: score table pitch smaller than heads");
-    const int64_t ldw = kScalarSlot;
-    if (plan) { const int rc = plan_ok("spgat_bwd_u", plan, M, ldw); if (rc) return rc; }
-    const bool split = plan && plan->nfix > 0;
-    const int vw = head_vw(pick_vw(d, {B, G, C}, {ldb, ldg, ldc}), d, heads);
-    { const int rc = width_ok("spgat_bwd_u", d, vw, heads); if (rc) return rc; }
+    int vw;      // (the slots hold scalars only: the workspace is no operand of the vector width)
+    if (const int rc = attn_plan_width("spgat_bwd_u", plan, M, kGatBwdUSlot, d, heads, {B, G, C}, {ldb, ldg, ldc}, vw)) return rc;
     if (M == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = rowptr; a.col = col; a.gat = B; a.ldgat = ldb; a.G = G; a.ldg = ldg; a.Cf = C; a.ldcf = ldc; a.lse = lse;
     a.delta_out = delta; a.d = d;
-    if (split) { a.ws = plan->dev_ws; a.ldw = ldw; }
     GatX x{};
     x.U = U; x.ldu = ldu; x.V = V; x.ldv = ldv; x.slope = slope; x.dU = dU;
-    return gat_run<GAT_BWD_U>(a, x, "spgat_bwd_u", M, plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
+    return attn_run<Gat<GAT_BWD_U>>("spgat_bwd_u", a, M, plan, kGatBwdUSlot, vw, heads, drop_of(keep, key), (hipStream_t)stream, x);
 }
 
 extern "C" int sgcn_spgat_csr_bwd_v_f32(const int32_t* t_rowptr, const int32_t* t_row, int32_t K, int32_t M, int32_t d,
@@ -598,32 +526,27 @@ extern "C" int sgcn_spgat_csr_bwd_v_f32(const int32_t* t_rowptr, const int32_t* 
                                         const float* lse, const float* delta, float* dB, int64_t lddb, float* dV,
                                         const float* add, int64_t ldadd, int32_t add_rows, const sgcn_plan_t* t_plan,
                                         void* stream) {
-    SGCN_REQUIRE(M >= 0 && K >= 0, "spgat_bwd_v: negative size");
-    SGCN_REQUIRE(d > 0, "spgat_bwd_v: d must be positive (got %d)", d);
-    { const int rc = heads_ok("spgat_bwd_v", d, heads); if (rc) return rc; }
-    { const int rc = keep_ok("spgat_bwd_v", keep); if (rc) return rc; }
-    { const int rc = slope_ok("spgat_bwd_v", slope); if (rc) return rc; }
+    if (const int rc = attn_open("spgat_bwd_v", M, K, d, heads, keep)) return rc;
+    if (const int rc = slope_ok("spgat_bwd_v", slope)) return rc;
     SGCN_REQUIRE(t_rowptr && ((U && G && lse && delta) || M == 0) && ((B && V && dB && dV) || K == 0), "spgat_bwd_v: null operand");
     SGCN_REQUIRE(ldb >= d && ldg >= d && lddb >= d, "spgat_bwd_v: leading dimension smaller than d");
     SGCN_REQUIRE(ldu >= heads && ldv >= heads, "spgat_bwd_v: score table pitch smaller than heads");
     const bool with_add = add && add_rows > 0;
     if (with_add) SGCN_REQUIRE(ldadd >= d && add_rows <= K, "spgat_bwd_v: bad addend");
-    const int64_t ldw = ceil4(d) + kScalarSlot;
-    if (t_plan) { const int rc = plan_ok("spgat_bwd_v", t_plan, K, ldw); if (rc) return rc; }
-    const bool split = t_plan && t_plan->nfix > 0;
-    const int vw = head_vw(pick_vw(d, {B, G, dB, with_add ? add : nullptr, split ? (const void*)t_plan->dev_ws : nullptr},
-                                   {ldb, ldg, lddb, with_add ? ldadd : lddb}), d, heads);
-    { const int rc = width_ok("spgat_bwd_v", d, vw, heads); if (rc) return rc; }
+    int vw;
+    if (const int rc = attn_plan_width("spgat_bwd_v", t_plan, K, gat_bwd_v_slot(d), d, heads,
+                                       {B, G, dB, with_add ? add : nullptr, split_ws(t_plan)},
+                                       {ldb, ldg, lddb, with_add ? ldadd : lddb}, vw)) return rc;
     if (K == 0) return SGCN_OK;
 
     AttnArgs a{};
     a.rowptr = t_rowptr; a.col = t_row; a.own = B; a.ldown = ldb; a.G = G; a.ldg = ldg; a.lse = lse; a.delta = delta;
     a.out = dB; a.ldo = lddb; a.d = d;
     if (with_add) { a.add = add; a.ldadd = ldadd; a.add_rows = add_rows; }
-    if (split) { a.ws = t_plan->dev_ws; a.ldw = ldw; }
     GatX x{};
     x.U = U; x.ldu = ldu; x.V = V; x.ldv = ldv; x.slope = slope; x.dV = dV;
-    return gat_run<GAT_BWD_V>(a, x, "spgat_bwd_v", K, t_plan, vw, heads, drop_of(keep, key), (hipStream_t)stream);
+    return attn_run<Gat<GAT_BWD_V>>("spgat_bwd_v", a, K, t_plan, gat_bwd_v_slot(d), vw, heads, drop_of(keep, key),
+                                    (hipStream_t)stream, x);
 }
 
 extern "C" int sgcn_gat_scores_bwd_f32(const float* x, int64_t ldx, int32_t rows, int32_t rows_u, int32_t d, int32_t heads,

@@ -561,29 +561,44 @@ class StaticMatrix(object):
         if self.edge is not None:
             raise ValueError("attention has no edge-masked form")
 
-    def attn_product(self, x, scale, out=None, want_lse=True, heads=1, keep=1.0, key=0):
-        """(out, lse) of ops.spattn over this matrix's PATTERN with the queries x[:M]: out[i] = the rows of ``x`` that row i
-        stores an entry for, weighed by softmax_j(scale * <x[i], x[j]>); lse the rows' log-sum-exp for ``attn_backward``
-        (None with ``want_lse=False``).  Reads the row kernel's CSR -- pattern and segment plan -- only.  The kernel holds
-        d <= 256 * VW columns: an operand whose alignment would push d over that (602-wide features on a pitch of 602
-        floats: VW = 2) is staged once into an aligned scratch table, an ``out`` view of that kind is computed aligned and
-        copied.  ``heads``: ops.spattn's; lse is then (M, heads), and an operand is staged where ITS alignment, not the head
-        width, is what narrows the vectors (staging cannot widen what d / heads caps).  ``keep``, ``key``: ops.spattn's
-        dropout on the coefficients, passed through (keep = 1: none)."""
-        self._attn_refuse(x)
+    def _attn_forward(self, launch, x, out, heads):
+        """``launch(x, out)`` -> (res, lse) on operands the kernel can hold: it takes d <= 256 * VW columns, so where an
+        operand's alignment -- not the head width, which staging cannot widen -- narrows the vectors so far that d is over
+        that, ``x`` is staged into an aligned scratch table, and an ``out`` view of that kind is computed aligned and copied."""
         d = int(x.shape[1])
-        # (the keywords are passed only when set: without dropout the call is the one ops.spattn has always taken)
-        drop = dict(keep=keep, key=key) if keep != 1.0 else {}
         if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out, heads=heads):
             best = ops.attn_vw(d, heads=heads)            # what aligned operands would get
             if ops.attn_vw(d, x, heads=heads) < best:
                 x = self._attn_staged('x', x, d)
             if out is not None and ops.attn_vw(d, out, heads=heads) < best:
-                res, lse = ops.spattn(self.rows_csr, x, scale=scale, want_lse=want_lse, heads=heads,
-                                      out=self._attn_staged('out', out, d, fill=False), **drop)
+                res, lse = launch(x, self._attn_staged('out', out, d, fill=False))
                 out.copy_(res)
                 return out, lse
-        return ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse, heads=heads, **drop)
+        return launch(x, out)
+
+    def _attn_backward_operands(self, heads, x, g, out_fwd, add):
+        """The backward's four tables (``add`` may be None), each staged where ``_attn_forward`` would stage it."""
+        d = int(x.shape[1])
+        tabs = dict(x=x, g=g, out_fwd=out_fwd, add=add)
+        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, add, heads=heads):
+            best = ops.attn_vw(d, heads=heads)
+            for role, t in tabs.items():
+                if t is not None and ops.attn_vw(d, t, heads=heads) < best:
+                    tabs[role] = self._attn_staged(role, t, d)
+        return tabs['x'], tabs['g'], tabs['out_fwd'], tabs['add']
+
+    def attn_product(self, x, scale, out=None, want_lse=True, heads=1, keep=1.0, key=0):
+        """(out, lse) of ops.spattn over this matrix's PATTERN with the queries x[:M]: out[i] = the rows of ``x`` that row i
+        stores an entry for, weighed by softmax_j(scale * <x[i], x[j]>); lse the rows' log-sum-exp for ``attn_backward``
+        (None with ``want_lse=False``).  Reads the row kernel's CSR -- pattern and segment plan -- only.  Misaligned operands
+        too wide for the kernel (602-wide features on a pitch of 602 floats: VW = 2) are staged (``_attn_forward``).
+        ``heads``: ops.spattn's; lse is then (M, heads).  ``keep``, ``key``: ops.spattn's dropout on the coefficients,
+        passed through (keep = 1: none)."""
+        self._attn_refuse(x)
+        # (the keywords are passed only when set: without dropout the call is the one ops.spattn has always taken)
+        drop = dict(keep=keep, key=key) if keep != 1.0 else {}
+        return self._attn_forward(lambda x, out: ops.spattn(self.rows_csr, x, scale=scale, out=out, want_lse=want_lse, heads=heads,
+                                                            **drop), x, out, heads)
 
     def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1, keep=1.0, key=0):
         """Called on the matrix whose ``attn_product(x, scale)`` gave ``out_fwd`` and ``lse``: the gradient with respect to
@@ -591,16 +606,9 @@ class StaticMatrix(object):
         gather over this matrix's pattern and one over its transpose's.  Operands are staged as in ``attn_product``.
         ``keep``, ``key``: those of the forward."""
         self._attn_refuse(x)
-        d = int(x.shape[1])
-        ops_ = dict(x=x, g=g, out_fwd=out_fwd, add=add)
-        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, add, heads=heads):
-            best = ops.attn_vw(d, heads=heads)
-            for role, t in list(ops_.items()):
-                if t is not None and ops.attn_vw(d, t, heads=heads) < best:
-                    ops_[role] = self._attn_staged(role, t, d)
-        return ops.spattn_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], None, ops_['g'], ops_['out_fwd'], lse, scale,
-                              add=ops_['add'], add_rows=add_rows, heads=heads,
-                              **(dict(keep=keep, key=key) if keep != 1.0 else {}))[1]
+        x, g, out_fwd, add = self._attn_backward_operands(heads, x, g, out_fwd, add)
+        return ops.spattn_bwd(self.rows_csr, self.transpose.rows_csr, x, None, g, out_fwd, lse, scale, add=add, add_rows=add_rows,
+                              heads=heads, **(dict(keep=keep, key=key) if keep != 1.0 else {}))[1]
 
     # ---- learned additive scores (--attn_score gat) ------------------------------------------------------------------------
     def gat_product(self, x, a, slope, out=None, want_lse=True, heads=1, keep=1.0, key=0):
@@ -609,20 +617,10 @@ class StaticMatrix(object):
         softmax_j(LeakyReLU(S[i, h] + S[j, H + h])) per head h.  lse (M, H) and S are what ``gat_backward`` needs (lse is None
         with ``want_lse=False``).  Operands are staged as in ``attn_product``, and the same operands are refused."""
         self._attn_refuse(x)
-        d = int(x.shape[1])
-        H = int(heads)
+        H, M = int(heads), self.shape[0]
         S = ops.gat_scores(x, a, heads=H)
-        M = self.shape[0]
-        kw = dict(slope=slope, want_lse=want_lse, heads=H, keep=keep, key=key)
-        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, out, heads=H):
-            best = ops.attn_vw(d, heads=H)
-            if ops.attn_vw(d, x, heads=H) < best:
-                x = self._attn_staged('x', x, d)
-            if out is not None and ops.attn_vw(d, out, heads=H) < best:
-                res, lse = ops.spgat(self.rows_csr, x, S[:M, :H], S[:, H:], out=self._attn_staged('out', out, d, fill=False), **kw)
-                out.copy_(res)
-                return out, lse, S
-        res, lse = ops.spgat(self.rows_csr, x, S[:M, :H], S[:, H:], out=out, **kw)
+        res, lse = self._attn_forward(lambda x, out: ops.spgat(self.rows_csr, x, S[:M, :H], S[:, H:], slope=slope, out=out,
+                                                               want_lse=want_lse, heads=H, keep=keep, key=key), x, out, H)
         return res, lse, S
 
     def gat_backward(self, x, a, S, g, out_fwd, lse, slope, add=None, add_rows=0, heads=1, keep=1.0, key=0, need_dx=True):
@@ -631,19 +629,11 @@ class StaticMatrix(object):
         second one's epilogue), then ops.gat_scores_bwd, which adds the scores' share into dX and reduces da (2, d).
         ``need_dx=False``: dX is not formed (the launch over the transpose still runs, for dV)."""
         self._attn_refuse(x)
-        d = int(x.shape[1])
-        H = int(heads)
-        M = self.shape[0]
-        ops_ = dict(x=x, g=g, out_fwd=out_fwd, add=add if need_dx else None)
-        if d > ops.ATTN_MAX_VECTORS * ops.attn_vw(d, x, g, out_fwd, ops_['add'], heads=H):
-            best = ops.attn_vw(d, heads=H)
-            for role, t in list(ops_.items()):
-                if t is not None and ops.attn_vw(d, t, heads=H) < best:
-                    ops_[role] = self._attn_staged(role, t, d)
-        dB, dU, dV, _ = ops.spgat_bwd(self.rows_csr, self.transpose.rows_csr, ops_['x'], S[:M, :H], S[:, H:], ops_['g'],
-                                      ops_['out_fwd'], lse, slope=slope, add=ops_['add'], add_rows=add_rows if need_dx else 0,
-                                      heads=H, keep=keep, key=key)
-        da = ops.gat_scores_bwd(ops_['x'], a, dU, dV, dx=dB if need_dx else None, heads=H)
+        H, M = int(heads), self.shape[0]
+        x, g, out_fwd, add = self._attn_backward_operands(H, x, g, out_fwd, add if need_dx else None)
+        dB, dU, dV, _ = ops.spgat_bwd(self.rows_csr, self.transpose.rows_csr, x, S[:M, :H], S[:, H:], g, out_fwd, lse, slope=slope,
+                                      add=add, add_rows=add_rows if need_dx else 0, heads=H, keep=keep, key=key)
+        da = ops.gat_scores_bwd(x, a, dU, dV, dx=dB if need_dx else None, heads=H)
         return (dB if need_dx else None), da
 
     def describe(self, d):

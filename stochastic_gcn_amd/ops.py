@@ -379,113 +379,124 @@ def _attn_keep(keep):
     return keep
 
 
-def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True, heads=1, keep=1.0, key=0):
-    """(out, lse): softmax dot-product attention over the stored pattern of the DeviceCSR ``A`` (M x K, unique column ids
-    per row; stored values are not read) -- sgcn_spattn_csr_f32.  With s_ij = scale * <q[i], x[j]> over the entries j of
-    row i: lse[i] = log sum_j exp(s_ij), out[i] = sum_j exp(s_ij - lse[i]) x[j]; an empty row gives +0.0 and -inf.
-    ``q=None`` means x[:M].  ``out`` may be a pitched (M, >= d) view.  ``want_lse=False`` (an evaluation): lse is None,
-    nothing is allocated for it.  ``heads`` = H in 1/2/4/8 (sgcn_spattn_mh_csr_f32): head h is the columns
-    [h d/H, (h+1) d/H), every head an attention of its own over the same pattern, and lse is (M, H) for H > 1.
-    ``keep`` < 1 (sgcn_spattn_drop_csr_f32): dropout on the coefficients -- entry (i, j) of head h stays, scaled by 1 / keep,
-    where ``attn_kept(i, j, h, key, keep)``; the softmax and lse are those of keep = 1, and keep = 1 is the call without it."""
-    check_unique_cols(A)
-    keep = _attn_keep(keep)
+def attn_slot(kind, d, heads=1):
+    """Floats per workspace slot of a split row in the attention launches -- the mirror of sgcn_attn_dev.h's fwd_slot, bwd_slot,
+    kGatBwdUSlot and gat_bwd_v_slot, what ``DevicePlan.struct`` is sized with.  'fwd' (both score kinds): the row on a 16-byte
+    pitch + one vector (m, l, -, -) per head; 'bwd' (dot-product bwd_q / bwd_kv): the row; 'gat_bwd_u': the heads' dU alone;
+    'gat_bwd_v': the row + the heads' dV."""
+    c4 = (d + 3) // 4 * 4
+    return {'fwd': c4 + 4 * heads, 'bwd': c4, 'gat_bwd_u': 8, 'gat_bwd_v': c4 + 8}[kind]
+
+
+def _attn_operands(A, x, heads, own, out=None, bwd=None, vector_lse=False):
+    """The operand checks of spattn, spattn_bwd, spgat and spgat_bwd, in the order they have always run: ``x`` against the K
+    columns of ``A`` and ``heads``; ``own(d, heads, (bptr, ldb))``, the caller's own operands (q; the score tables); then the
+    forward's ``out`` (allocated when None) or, with ``bwd = (g, out_fwd, lse, add, add_rows)``, the backward's -- lse a
+    vector of M floats under ``vector_lse`` at one head, else (M, heads).  Returns d, heads, x's (ptr, pitch), own's result
+    and, forward: out, its (ptr, pitch); backward: g's and out_fwd's (ptr, pitch) and (aptr, ldadd, add_rows)."""
     M, K = A.shape
-    bptr, ldb = _rows2d(x, "x")
+    b = _rows2d(x, "x")
     d = int(x.shape[1])
     heads = _attn_heads(d, heads)
     if x.shape[0] < K:
         raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
-    if q is None:
+    mine = own(d, heads, b)
+    if bwd is None:
+        if out is None:
+            out = _attn_out(M, d, x.device, heads)
+        c = _rows2d(out, "out")
+        if out.shape[0] != M or out.shape[1] < d:
+            raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
+        return d, heads, b, mine, out, c
+    g, out_fwd, lse, add, add_rows = bwd
+    gp = _rows2d(g, "g")
+    c = _rows2d(out_fwd, "out_fwd")
+    if tuple(g.shape) != (M, d) or out_fwd.shape[0] != M or out_fwd.shape[1] < d:
+        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (M, d, tuple(g.shape), tuple(out_fwd.shape)))
+    _dev(lse, torch.float32, "lse")
+    if vector_lse and heads == 1:
+        if lse.dim() != 1 or lse.shape[0] != M or not lse.is_contiguous():
+            raise ValueError("lse must be a contiguous vector of %d floats" % M)
+    elif tuple(lse.shape) != (M, heads) or not lse.is_contiguous():
+        raise ValueError("lse must be a contiguous (%d, %d) table of floats" % (M, heads))
+    a = _rows2d(add, "add") if add is not None else (None, 0)
+    return d, heads, b, mine, gp, c, a + (int(add_rows) if add is not None else 0,)
+
+
+def _attn_q(q, M, d):
+    """(ptr, pitch) of an explicit query table: at least M rows of d floats"""
+    qp = _rows2d(q, "q")
+    if q.shape[0] < M or q.shape[1] != d:
+        raise ValueError("q has shape %s, need (>=%d, %d)" % (tuple(q.shape), M, d))
+    return qp
+
+
+def _byref(plan):
+    return C.byref(plan) if plan is not None else None
+
+
+def spattn(A, x, q=None, scale=1.0, out=None, want_lse=True, heads=1, keep=1.0, key=0):
+    """(out, lse): softmax dot-product attention over the stored pattern of the DeviceCSR ``A`` (M x K, unique column ids
+    per row; stored values are not read) -- sgcn_spattn_drop_csr_f32.  With s_ij = scale * <q[i], x[j]> over the entries j of
+    row i: lse[i] = log sum_j exp(s_ij), out[i] = sum_j exp(s_ij - lse[i]) x[j]; an empty row gives +0.0 and -inf.
+    ``q=None`` means x[:M].  ``out`` may be a pitched (M, >= d) view.  ``want_lse=False`` (an evaluation): lse is None,
+    nothing is allocated for it.  ``heads`` = H in 1/2/4/8: head h is the columns [h d/H, (h+1) d/H), every head an attention
+    of its own over the same pattern, and lse is (M, H) for H > 1.  ``keep`` < 1: dropout on the coefficients -- entry (i, j)
+    of head h stays, scaled by 1 / keep, where ``attn_kept(i, j, h, key, keep)``; the softmax and lse are those of keep = 1,
+    and keep = 1 makes the library run the kernels without a mask, whatever ``key``."""
+    check_unique_cols(A)
+    keep = _attn_keep(keep)
+    M, K = A.shape
+
+    def queries(d, heads, b):
+        if q is not None:
+            return _attn_q(q, M, d)
         if x.shape[0] < M:
             raise ValueError("q=None takes x[:%d] as the queries, x has %d rows" % (M, x.shape[0]))
-        qptr, ldq = bptr, ldb
-    else:
-        qptr, ldq = _rows2d(q, "q")
-        if q.shape[0] < M or q.shape[1] != d:
-            raise ValueError("q has shape %s, need (>=%d, %d)" % (tuple(q.shape), M, d))
-    if out is None:
-        out = _attn_out(M, d, x.device, heads)
-    cptr, ldc = _rows2d(out, "out")
-    if out.shape[0] != M or out.shape[1] < d:
-        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
+        return b
+    d, heads, (bptr, ldb), (qptr, ldq), out, (cptr, ldc) = _attn_operands(A, x, heads, queries, out=out)
     lse = torch.empty((M,) if heads == 1 else (M, heads), dtype=torch.float32, device=x.device) if want_lse else None
-    # (a forward slot: the row + one vector for (m, l) per head)
-    plan = A.plan.struct((d + 3) // 4 * 4 + 4 * heads) if A.plan is not None else None
-    if keep < 1.0:
-        check(lib.sgcn_spattn_drop_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, int(key) & 0xFFFFFFFF, qptr, ldq,
-                                           bptr, ldb, float(scale), cptr, ldc, _ptr(lse),
-                                           C.byref(plan) if plan is not None else None, _stream()))
-        return out, lse
-    check(lib.sgcn_spattn_mh_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, qptr, ldq, bptr, ldb, float(scale),
-                                     cptr, ldc, _ptr(lse), C.byref(plan) if plan is not None else None, _stream()))
+    plan = A.plan.struct(attn_slot('fwd', d, heads)) if A.plan is not None else None
+    check(lib.sgcn_spattn_drop_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, int(key) & 0xFFFFFFFF, qptr, ldq,
+                                       bptr, ldb, float(scale), cptr, ldc, _ptr(lse), _byref(plan), _stream()))
     return out, lse
 
 
 def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1, keep=1.0, key=0):
     """(dq, dx), the gradient of ``spattn(A, x, q, scale)`` for g = dL/dout, from the forward's ``out_fwd`` and ``lse`` --
-    sgcn_spattn_csr_bwd_q_f32 over ``A``, then sgcn_spattn_csr_bwd_kv_f32 over ``At``, the DeviceCSR of the TRANSPOSED
+    sgcn_spattn_drop_csr_bwd_q_f32 over ``A``, then sgcn_spattn_drop_csr_bwd_kv_f32 over ``At``, the DeviceCSR of the TRANSPOSED
     pattern (ops.transpose_host: source rows ascending).  Nothing nnz-sized is stored, no atomics: bitwise reproducible.
     With an explicit ``q``: dq (M x d, + add on its first ``add_rows`` rows) and dx = dB (K x d) separately.  With
     ``q=None`` (the queries are x[:M]): (None, dx) with dx = dB + [dQ + add ; 0] -- the first launch's result is the second
     one's addend, so the sum costs no extra pass.  ``heads`` as in ``spattn``, ``lse`` of the shape it returned.  ``keep`` and
-    ``key``: the forward's (sgcn_spattn_drop_csr_bwd_q_f32 / _bwd_kv_f32 recompute its mask; ``out_fwd`` is the masked output)."""
+    ``key``: the forward's (the launches recompute its mask; ``out_fwd`` is the masked output)."""
     keep = _attn_keep(keep)
     M, K = A.shape
     if tuple(At.shape) != (K, M):
         raise ValueError("At has shape %s, the transpose of %s is needed" % (tuple(At.shape), tuple(A.shape)))
-    bptr, ldb = _rows2d(x, "x")
-    d = int(x.shape[1])
-    heads = _attn_heads(d, heads)
-    if x.shape[0] < K:
-        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
-    if q is None:
+
+    def queries(d, heads, b):
+        if q is not None:
+            return _attn_q(q, M, d)
         if x.shape[0] < M or K < M:
             raise ValueError("q=None takes x[:%d] as the queries, x has %d rows and A %d columns" % (M, x.shape[0], K))
-        qptr, ldq = bptr, ldb
-    else:
-        qptr, ldq = _rows2d(q, "q")
-        if q.shape[0] < M or q.shape[1] != d:
-            raise ValueError("q has shape %s, need (>=%d, %d)" % (tuple(q.shape), M, d))
-    gptr, ldg = _rows2d(g, "g")
-    cptr, ldc = _rows2d(out_fwd, "out_fwd")
-    if tuple(g.shape) != (M, d) or out_fwd.shape[0] != M or out_fwd.shape[1] < d:
-        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (M, d, tuple(g.shape), tuple(out_fwd.shape)))
-    _dev(lse, torch.float32, "lse")
-    if heads == 1:
-        if lse.dim() != 1 or lse.shape[0] != M or not lse.is_contiguous():
-            raise ValueError("lse must be a contiguous vector of %d floats" % M)
-    elif tuple(lse.shape) != (M, heads) or not lse.is_contiguous():
-        raise ValueError("lse must be a contiguous (%d, %d) table of floats" % (M, heads))
-    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
-    add_rows = int(add_rows) if add is not None else 0
+        return b
+    d, heads, (bptr, ldb), (qptr, ldq), (gptr, ldg), (cptr, ldc), (aptr, ldadd, add_rows) = _attn_operands(
+        A, x, heads, queries, bwd=(g, out_fwd, lse, add, add_rows), vector_lse=True)
     delta = torch.empty((M * heads,), dtype=torch.float32, device=x.device)
     dq = _attn_out(M, d, x.device, heads)
     dx = _attn_out(K, d, x.device, heads)
-    plan = A.plan.struct(d) if A.plan is not None else None
-    tplan = At.plan.struct(d) if At.plan is not None else None
+    plan = A.plan.struct(attn_slot('bwd', d)) if A.plan is not None else None
+    tplan = At.plan.struct(attn_slot('bwd', d)) if At.plan is not None else None
     fused = q is None
-    if keep < 1.0:
-        key = int(key) & 0xFFFFFFFF
-        check(lib.sgcn_spattn_drop_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, key, qptr, ldq, bptr, ldb,
-                                                 float(scale), gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(),
-                                                 dq.data_ptr(), _rows2d(dq, "dq")[1], aptr, ldadd, add_rows,
-                                                 C.byref(plan) if plan is not None else None, _stream()))
-        check(lib.sgcn_spattn_drop_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, qptr, ldq, bptr,
-                                                  ldb, float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
-                                                  _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
-                                                  _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0,
-                                                  C.byref(tplan) if tplan is not None else None, _stream()))
-        return (None if fused else dq), dx
-    check(lib.sgcn_spattn_mh_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, qptr, ldq, bptr, ldb, float(scale),
-                                           gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
-                                           _rows2d(dq, "dq")[1], aptr, ldadd, add_rows,
-                                           C.byref(plan) if plan is not None else None, _stream()))
-    check(lib.sgcn_spattn_mh_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, qptr, ldq, bptr, ldb,
-                                            float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
-                                            _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
-                                            _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0,
-                                            C.byref(tplan) if tplan is not None else None, _stream()))
+    key = int(key) & 0xFFFFFFFF
+    check(lib.sgcn_spattn_drop_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, key, qptr, ldq, bptr, ldb,
+                                             float(scale), gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(),
+                                             dq.data_ptr(), _rows2d(dq, "dq")[1], aptr, ldadd, add_rows, _byref(plan), _stream()))
+    check(lib.sgcn_spattn_drop_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, qptr, ldq, bptr,
+                                              ldb, float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
+                                              _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
+                                              _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0, _byref(tplan), _stream()))
     return (None if fused else dq), dx
 
 
@@ -539,23 +550,12 @@ def spgat(A, x, u, v, slope=0.2, out=None, want_lse=True, heads=1, keep=1.0, key
     keep = _attn_keep(keep)
     slope = _attn_slope(slope)
     M, K = A.shape
-    bptr, ldb = _rows2d(x, "x")
-    d = int(x.shape[1])
-    heads = _attn_heads(d, heads)
-    if x.shape[0] < K:
-        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
-    uptr, ldu = _gat_table(u, M, heads, "u")
-    vptr, ldv = _gat_table(v, K, heads, "v")
-    if out is None:
-        out = _attn_out(M, d, x.device, heads)
-    cptr, ldc = _rows2d(out, "out")
-    if out.shape[0] != M or out.shape[1] < d:
-        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), M, d))
+    d, heads, (bptr, ldb), (uptr, ldu, vptr, ldv), out, (cptr, ldc) = _attn_operands(
+        A, x, heads, lambda d, heads, b: _gat_table(u, M, heads, "u") + _gat_table(v, K, heads, "v"), out=out)
     lse = torch.empty((M, heads), dtype=torch.float32, device=x.device) if want_lse else None
-    plan = A.plan.struct((d + 3) // 4 * 4 + 4 * heads) if A.plan is not None else None
+    plan = A.plan.struct(attn_slot('fwd', d, heads)) if A.plan is not None else None
     check(lib.sgcn_spgat_csr_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, int(key) & 0xFFFFFFFF, uptr, ldu, vptr,
-                                 ldv, bptr, ldb, slope, cptr, ldc, _ptr(lse), C.byref(plan) if plan is not None else None,
-                                 _stream()))
+                                 ldv, bptr, ldb, slope, cptr, ldc, _ptr(lse), _byref(plan), _stream()))
     return out, lse
 
 
@@ -570,36 +570,22 @@ def spgat_bwd(A, At, x, u, v, g, out_fwd, lse, slope=0.2, add=None, add_rows=0, 
     M, K = A.shape
     if tuple(At.shape) != (K, M):
         raise ValueError("At has shape %s, the transpose of %s is needed" % (tuple(At.shape), tuple(A.shape)))
-    bptr, ldb = _rows2d(x, "x")
-    d = int(x.shape[1])
-    heads = _attn_heads(d, heads)
-    if x.shape[0] < K:
-        raise ValueError("x has %d rows, A has %d columns" % (x.shape[0], K))
-    uptr, ldu = _gat_table(u, M, heads, "u")
-    vptr, ldv = _gat_table(v, K, heads, "v")
-    gptr, ldg = _rows2d(g, "g")
-    cptr, ldc = _rows2d(out_fwd, "out_fwd")
-    if tuple(g.shape) != (M, d) or out_fwd.shape[0] != M or out_fwd.shape[1] < d:
-        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (M, d, tuple(g.shape), tuple(out_fwd.shape)))
-    _dev(lse, torch.float32, "lse")
-    if tuple(lse.shape) != (M, heads) or not lse.is_contiguous():
-        raise ValueError("lse must be a contiguous (%d, %d) table of floats" % (M, heads))
-    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
-    add_rows = int(add_rows) if add is not None else 0
+    d, heads, (bptr, ldb), (uptr, ldu, vptr, ldv), (gptr, ldg), (cptr, ldc), (aptr, ldadd, add_rows) = _attn_operands(
+        A, x, heads, lambda d, heads, b: _gat_table(u, M, heads, "u") + _gat_table(v, K, heads, "v"),
+        bwd=(g, out_fwd, lse, add, add_rows))
     delta = torch.empty((M, heads), dtype=torch.float32, device=x.device)
     dU = torch.empty((M, heads), dtype=torch.float32, device=x.device)
     dV = torch.empty((K, heads), dtype=torch.float32, device=x.device)
     dB = _attn_out(K, d, x.device, heads)
-    plan = A.plan.struct(8) if A.plan is not None else None
+    plan = A.plan.struct(attn_slot('gat_bwd_u', d)) if A.plan is not None else None
     key = int(key) & 0xFFFFFFFF
     check(lib.sgcn_spgat_csr_bwd_u_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, key, uptr, ldu, vptr, ldv, bptr,
                                        ldb, slope, gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dU.data_ptr(),
-                                       C.byref(plan) if plan is not None else None, _stream()))
-    tplan = At.plan.struct((d + 3) // 4 * 4 + 8) if At.plan is not None else None
+                                       _byref(plan), _stream()))
+    tplan = At.plan.struct(attn_slot('gat_bwd_v', d)) if At.plan is not None else None
     check(lib.sgcn_spgat_csr_bwd_v_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, uptr, ldu, vptr, ldv, bptr,
                                        ldb, slope, gptr, ldg, lse.data_ptr(), delta.data_ptr(), dB.data_ptr(),
-                                       _rows2d(dB, "dB")[1], dV.data_ptr(), aptr, ldadd, add_rows,
-                                       C.byref(tplan) if tplan is not None else None, _stream()))
+                                       _rows2d(dB, "dB")[1], dV.data_ptr(), aptr, ldadd, add_rows, _byref(tplan), _stream()))
     return dB, dU, dV, delta
 
 

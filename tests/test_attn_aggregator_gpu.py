@@ -161,6 +161,57 @@ def test_wide_misaligned_operands_are_staged():
     assert all(m._scratch[k] is v for k, v in tables.items())                   # reused, not allocated again
 
 
+@pytest.mark.parametrize("kind", ["attn", "gat"])
+def test_staged_operands_give_the_bits_of_aligned_ones(kind):
+    """d = 258 on a pitch of 259 floats (VW = 1: 258 > 256 columns, the smallest width that is staged at all) against the same
+    values on a pitch of 260 (VW = 4, served as it is): x, out, g, out_fwd and add all go through StaticMatrix's staging
+    helpers, the results of both score kinds are those of the aligned tables to the bit, and a second call allocates nothing"""
+    from stochastic_gcn_amd import full_batch, ops
+    import sparse_cases as sc
+    a = sc.pattern("row_lengths")
+    M, K = a.shape
+    d, slope = 258, 0.2
+    rng = np.random.RandomState(5)
+    host = dict(x=rng.standard_normal((K, d)), g=rng.standard_normal((M, d)), add=rng.standard_normal((M, d)))
+    av = torch.tensor((rng.standard_normal((2, d)) * d ** -0.5).astype(np.float32)).to(DEV)
+
+    def view(v, pitch):
+        t = torch.full((v.shape[0], pitch), float('nan'), device=DEV)
+        t[:, :d] = torch.tensor(v.astype(np.float32)).to(DEV)
+        return t[:, :d]
+
+    def run(pitch):
+        m = full_batch.StaticMatrix(a, DEV, 'rows')
+        x, g, add = (view(host[k], pitch) for k in ('x', 'g', 'add'))
+        buf = torch.full((M, pitch), float('nan'), device=DEV)
+        out = buf[:, :d]
+        got, tables = [], None
+        for _ in range(2):
+            if kind == "attn":
+                res, lse = m.attn_product(x, d ** -0.5, out=out)
+                back = (m.attn_backward(x, g, out, lse, d ** -0.5, add=add, add_rows=M),)
+                fwd = (res, lse)
+            else:
+                res, lse, S = m.gat_product(x, av, slope, out=out)
+                back = m.gat_backward(x, av, S, g, out, lse, slope, add=add, add_rows=M)
+                fwd = (res, lse, S)
+            assert res.data_ptr() == out.data_ptr() and bool(torch.isnan(buf[:, d:]).all().item())
+            got.append([_np(t) for t in fwd + tuple(back)])
+            if tables is None:
+                tables = dict(m._scratch)
+        assert sorted(m._scratch) == sorted(tables) and all(m._scratch[k] is v for k, v in tables.items())
+        assert all(ref.same_bits(p, q) for p, q in zip(*got))
+        return x, got[0], tables
+
+    x259, staged, tables = run(259)
+    x260, aligned, none = run(260)
+    assert ops.attn_vw(d, x259) == 1 and ops.attn_vw(d, x260) == 4
+    assert sorted(k[1] for k in tables) == ['add', 'g', 'out', 'out_fwd', 'x'] and none == {}
+    assert len(staged) == len(aligned) == (3 if kind == "attn" else 5)
+    for i, (p, q) in enumerate(zip(staged, aligned)):
+        assert p.shape == q.shape and ref.same_bits(p, q), (kind, i)
+
+
 def test_train_main_end_to_end(tmp_path, monkeypatch):
     from stochastic_gcn_amd import train
     monkeypatch.chdir(tmp_path)
