@@ -774,6 +774,31 @@ int sgcn_csr_transpose_index(int32_t ncols, int64_t nnz, const int32_t* dev_col,
  * the LDS sweep use its unit plan (ops.LdsSweepCSR). */
 int sgcn_scale_rows_f32(const float* dev_x, int64_t ldx, const float* dev_s, int32_t n, int32_t d, float* dev_out, int64_t ldo,
                         void* stream);
+/* The induced subgraph A[S, S] of a resident CSR, cut on the device (--full_batch_parts: the matrix of a Cluster-GCN step).
+ * ids: the n vertex ids of S in [0, N), ASCENDING and UNIQUE -- the caller checks that on the host, the device trusts it.
+ *   sgcn_induce_map_i32    map[v] = position of v in ids, -1 elsewhere (map: N words)
+ *   sgcn_csr_induce_count  per selected row i the number of stored entries of row ids[i] whose column is in S, scanned
+ *                          (exclusive, on the device) into o_rowptr[n + 1]; with val != NULL also o_full[i] / o_kept[i], the
+ *                          fp32 sums of the row's values over all its entries / over the kept ones, in a fixed lane order
+ *   sgcn_csr_induce_fill   the kept entries of every selected row in STORED order: o_col = map[col], o_val = val (times
+ *                          rscale[i] where rscale != NULL; scale_cols != 0: times rscale[map[col]], the scale of the entry's
+ *                          relabelled column -- the cut of the resident TRANSPOSE, whose rows hold the source rows in ascending
+ *                          order, is the stable transpose of the block and carries the block's own values),
+ *                          o_coo_row (nullable) = i.  cap > 0: the words [o_rowptr[n], cap)
+ *                          of o_col and o_coo_row take the value n, a pad column behind the last one, so that
+ *                          sgcn_csr_transpose_index(n + 1, cap, ...) can be launched before the host has read o_rowptr[n]
+ *                          (stable: the pad sorts behind every real entry); o_col, o_val, o_coo_row then hold cap elements
+ * With rscale == NULL the output holds the rowptr, the column ids and the value bits of SciPy's A[ids][:, ids] for a CSR
+ * with sorted, duplicate-free rows.  Count and fill evaluate one predicate; no atomics.  SGCN_ERR_INVALID, before any HIP
+ * call, for a null operand with n > 0, a negative size, n > N. */
+int sgcn_induce_map_i32(const int32_t* dev_ids, int32_t n, int32_t N, int32_t* dev_map, void* stream);
+int sgcn_csr_induce_count(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, const int32_t* dev_ids,
+                          int32_t n, const int32_t* dev_map, int32_t* dev_o_rowptr, float* dev_o_full, float* dev_o_kept,
+                          void* stream);
+int sgcn_csr_induce_fill(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, const int32_t* dev_ids,
+                         int32_t n, const int32_t* dev_map, const int32_t* dev_o_rowptr, const float* dev_rscale,
+                         int32_t* dev_o_col, float* dev_o_val, int32_t* dev_o_coo_row, int32_t scale_cols, int64_t cap,
+                         void* stream);
 /* out[i] = src[idx[i]] */
 int sgcn_gather_f32(const float* dev_src, const int32_t* dev_idx, int64_t n, float* dev_out, void* stream);
 

@@ -266,6 +266,12 @@ SIGNATURES = {
     "sgcn_csr_transpose_ws_ints": (C.c_int64, [C.c_int32, C.c_int64]),
     "sgcn_csr_transpose_index": (C.c_int, [C.c_int32, C.c_int64, P, P, P, P, P, P, P]),
     "sgcn_gather_f32": (C.c_int, [P, P, C.c_int64, P, P]),
+    # the induced subgraph A[S, S] of a resident CSR (--full_batch_parts): (ids, n, N, map, stream),
+    # (rowptr, col, val, ids, n, map, o_rowptr, o_full, o_kept, stream),
+    # (rowptr, col, val, ids, n, map, o_rowptr, rscale, o_col, o_val, o_coo_row, scale_cols, cap, stream)
+    "sgcn_induce_map_i32": (C.c_int, [P, C.c_int32, C.c_int32, P, P]),
+    "sgcn_csr_induce_count": (C.c_int, [P, P, P, P, C.c_int32, P, P, P, P, P]),
+    "sgcn_csr_induce_fill": (C.c_int, [P, P, P, P, C.c_int32, P, P, P, P, P, P, C.c_int32, C.c_int64, P]),
     "sgcn_step_run": (C.c_int, [C.POINTER(StepOp), C.c_int32, P, C.c_int32, P]),
     "sgcn_step_fill": (C.c_int, [C.POINTER(StepFill), P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                                  P, C.c_int64]),

@@ -23,6 +23,12 @@ two products).
   StaticBatch    what Model.upload / get_data accept in place of a PackedBatch: fields[l] = arange(N), unit scales,
                  the N x C label table, and ``rows`` -- the sorted subset of vertices the loss runs over
                  (ops.softmax_ce / sigmoid_ce ``rows=``); without labels: a batch for forward passes only (exact_history.py)
+
+--full_batch_parts P (Cluster-GCN, Chiang et al., KDD 2019): more than one optimizer step per epoch without an estimator --
+  partition      the vertices cut once into P parts (label-propagation communities, cut to size, packed largest first)
+  PartSchedule   per epoch a seeded permutation of the parts in groups of q; a step runs on the union S of a group
+  InducedMatrix  the StaticMatrix of A[S, S], over the block ops.csr_induce cut out of the resident CSR on the device
+  PartBatch      the StaticBatch of that block: labels[S] and the positions within S of the training vertices
 """
 import numpy as np
 import torch
@@ -716,3 +722,151 @@ class StaticBatch(object):
         c.host_fields = [self.host_field] * (self.L + 1)
         c.fadj, c.ffields, c.inputs, c.sizes = [], [], inputs, self.sizes
         return c
+
+
+# ---- Cluster-GCN steps on device-cut subgraphs (--full_batch_parts) ----------------------------------------------------------
+PART_NORMS = _CHOICES['full_batch_part_norm']
+
+
+def check_full_batch_parts(flags=None, num_vertices=None):
+    """(P, q, norm) of --full_batch_parts / --full_batch_parts_per_step / --full_batch_part_norm (P = 0: off), with what a part
+    batch has no kernel or no meaning for refused.  Needs no device; a sibling of check_full_batch, called beside it -- and
+    once more with ``num_vertices`` when the graph is known."""
+    f = FLAGS if flags is None else flags
+    P, q = getattr(f, 'full_batch_parts', 0), getattr(f, 'full_batch_parts_per_step', 1)
+    norm = getattr(f, 'full_batch_part_norm', 'rows')
+    for name, v in (('full_batch_parts', P), ('full_batch_parts_per_step', q)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("--%s must be an integer, got %r" % (name, v))
+    P, q = int(P), int(q)
+    if P < 0:
+        raise ValueError("--full_batch_parts must be >= 0 (0 = off: one step over the whole graph), got %d" % P)
+    if norm not in PART_NORMS:
+        raise ValueError("--full_batch_part_norm must be one of %s, got %r" % ('/'.join(PART_NORMS), norm))
+    if P == 0:
+        return 0, q, norm
+    if not f.full_batch:
+        raise ValueError("--full_batch_parts needs --full_batch: its steps are exact steps on induced subgraphs of the "
+                         "training adjacency, and no other mode trains on that matrix")
+    if not 1 <= q <= P:
+        raise ValueError("--full_batch_parts_per_step must lie in [1, --full_batch_parts = %d], got %d" % (P, q))
+    if float(getattr(f, 'edge_dropout', 0.0)) > 0:
+        raise ValueError("--full_batch_parts is not supported with --edge_dropout: dropping the edges between parts already "
+                         "is edge sampling, and a part batch carries no edge mask")
+    if getattr(f, 'feature_dtype', 'fp32') == 'bf16':
+        raise ValueError("--full_batch_parts is not supported with --feature_dtype bf16: a step gathers its rows of the "
+                         "feature table into an fp32 table; there is no bfloat16-table form yet")
+    if f.full_batch_kernel in ('cs', 'lds'):
+        raise ValueError("--full_batch_parts is not supported with --full_batch_kernel %s: a part batch is cut anew every "
+                         "step and runs the row kernels (auto or rows); no sweep plan is made for it" % f.full_batch_kernel)
+    if num_vertices is not None and P > int(num_vertices):
+        raise ValueError("--full_batch_parts %d is more than the graph's %d vertices: every part holds at least one"
+                         % (P, int(num_vertices)))
+    return P, q, norm
+
+
+def partition(adj, P, seed=1):
+    """The vertices of ``adj`` cut into P parts, as P ascending int32 id arrays; deterministic in (adj, P, seed).
+
+    The communities of ops.reorder_labels(adj, seed=seed) (label propagation on the host), every community larger than
+    ceil(N / P) cut into id-contiguous pieces of at most that size, the pieces packed largest first into the currently
+    lightest of P bins (ties: the earlier piece, the lower bin).  Where that leaves fewer than P pieces the largest is
+    halved until there are P, so that no part is empty."""
+    N, P = int(adj.shape[0]), int(P)
+    if not 1 <= P <= N:
+        raise ValueError("partition: P must lie in [1, %d], got %d" % (N, P))
+    comm, _ = ops.reorder_labels(adj, seed=int(seed))
+    order = np.argsort(comm, kind='stable')                   # by community, ids ascending inside one
+    cuts = np.flatnonzero(np.diff(comm[order])) + 1
+    limit = -(-N // P)
+    pieces = []
+    for members in np.split(order, cuts):
+        pieces.extend(members[k:k + limit] for k in range(0, len(members), limit))
+    while len(pieces) < P:
+        k = max(range(len(pieces)), key=lambda i: (len(pieces[i]), -i))
+        big = pieces[k]
+        pieces[k:k + 1] = [big[:len(big) // 2], big[len(big) // 2:]]
+    bins, weight = [[] for _ in range(P)], [0] * P
+    for k in sorted(range(len(pieces)), key=lambda i: (-len(pieces[i]), i)):
+        j = min(range(P), key=lambda i: (weight[i], i))
+        bins[j].append(pieces[k])
+        weight[j] += len(pieces[k])
+    return [np.sort(np.concatenate(b)).astype(np.int32) for b in bins]
+
+
+class PartSchedule(object):
+    """Which parts a step unites: ``epoch(e)`` is a permutation of the parts seeded by (seed, e), cut into consecutive groups
+    of q (the last one may be shorter) -- ceil(P / q) steps that use every part exactly once.  ``groups(e)`` are the groups'
+    part indices, ``epoch(e)`` the sorted union of each group's vertices."""
+
+    def __init__(self, parts, q, seed=1):
+        self.parts, self.q, self.seed = [np.asarray(p, dtype=np.int32) for p in parts], int(q), int(seed)
+        if not 1 <= self.q <= len(self.parts):
+            raise ValueError("PartSchedule: q must lie in [1, %d], got %d" % (len(self.parts), self.q))
+
+    def __len__(self):
+        return -(-len(self.parts) // self.q)
+
+    def groups(self, e):
+        perm = np.random.RandomState([self.seed & 0xFFFFFFFF, int(e) & 0xFFFFFFFF]).permutation(len(self.parts))
+        return [perm[k:k + self.q] for k in range(0, len(perm), self.q)]
+
+    def epoch(self, e):
+        return [np.sort(np.concatenate([self.parts[j] for j in g])) for g in self.groups(e)]
+
+
+class InducedMatrix(StaticMatrix):
+    """The StaticMatrix of a part batch, over a block that ops.csr_induce cut on the device (a DeviceCSR with its transpose):
+    ``kernel`` is 'rows', ``rows_csr`` the block, ``transpose`` an InducedMatrix over the transposed block.  There is no host
+    matrix, no sweep plan, no plan cache and no edge mask; ``product``, ``max_product`` / ``max_backward``, ``attn_product`` /
+    ``attn_backward`` and ``gat_product`` / ``gat_backward`` are the inherited methods on the row kernel's CSR.  ``bf16``:
+    as StaticMatrix (--full_batch_dtype)."""
+
+    def __init__(self, block, device=None, bf16=False, _transpose_of=None):
+        if getattr(block, 'transpose', None) is None:
+            raise ValueError("an InducedMatrix needs a DeviceCSR with its transpose (ops.csr_induce)")
+        self.bf16, self._scratch, self._widened, self._redrawn = bool(bf16), {}, {}, {}
+        self.a, self.device = None, (device if device is not None else block.val.device)
+        self.shape, self.nnz = (int(block.shape[0]), int(block.shape[1])), int(block.nnz)
+        self.requested = self.kernel = 'rows'
+        self.products, self.d_hint, self.cache_path = 1, 0, None
+        self._rows, self._plan, self._transpose = block, None, _transpose_of
+        self._tuned, self.plan_from_cache = set(), False
+
+    @property
+    def transpose(self):
+        if self._transpose is None:
+            self._transpose = InducedMatrix(self._rows.transpose, self.device, self.bf16, _transpose_of=self)
+        return self._transpose
+
+    def describe(self, d):
+        return dict(plan_from_cache=False, pace=None, kernel="sgcn::spmm_seg_kernel", products=self.products)
+
+
+class PartBatch(StaticBatch):
+    """One Cluster-GCN step's batch: the static batch of the induced subgraph over ``ids`` (ascending, unique) -- the
+    InducedMatrix, labels[ids] (ops.gather_rows of the resident N x C table) and the loss rows, the POSITIONS within ``ids``
+    of the vertices the loss runs over.  ``ids_dev`` are the ids on the device: the model gathers its input rows by them."""
+
+    def __init__(self, ids, ids_dev, matrix, labels, rows, L, device=None):
+        n = int(matrix.shape[0])
+        if int(len(ids)) != n or int(ids_dev.shape[0]) != n:
+            raise ValueError("a part batch over %d vertices needs a matrix of that size, got %d" % (len(ids), n))
+        super(PartBatch, self).__init__(matrix, ops.gather_rows(labels, ids_dev), rows, L, device)
+        self.ids, self.ids_dev = np.asarray(ids, dtype=np.int32), ids_dev
+
+
+def part_stats(adj, parts, train_ids):
+    """What the set-up line of --full_batch_parts reports: part sizes, training vertices per part (min / median / max each)
+    and the share of the adjacency's stored entries whose row and column lie in one part."""
+    N = int(adj.shape[0])
+    owner = np.empty(N, dtype=np.int64)
+    for j, p in enumerate(parts):
+        owner[p] = j
+    a = adj.tocsr()
+    rows = np.repeat(np.arange(N), np.diff(a.indptr))
+    inside = int(np.count_nonzero(owner[rows] == owner[a.indices]))
+    sizes = np.array([len(p) for p in parts])
+    train = np.bincount(owner[np.asarray(train_ids, dtype=np.int64)], minlength=len(parts))
+    mmm = lambda v: (int(v.min()), float(np.median(v)), int(v.max()))      # noqa: E731
+    return dict(sizes=mmm(sizes), train=mmm(train), inside=inside / max(int(a.nnz), 1))

@@ -30,7 +30,7 @@ from . import ops
 from ._ffi import check, lib as _lib
 from .flags import FLAGS, check_polyak
 from .layers import (AugmentedDropoutDense, Dense, DetDropoutFC, Dropout, SparseInput)
-from .full_batch import StaticBatch, StaticCur, dense_bf16
+from .full_batch import PartBatch, StaticBatch, StaticCur, dense_bf16
 from .scheduler import PackedBatch, build_plan
 
 
@@ -630,7 +630,26 @@ class GCN(Model):
 
     def _upload_static(self, sb):
         """A full-graph batch (full_batch.StaticBatch): nothing to copy -- the input is the resident feature table itself,
-        all N rows in vertex order (dense: hstack(X, A.X) under --preprocess; sparse: the whole feature CSR)."""
+        all N rows in vertex order (dense: hstack(X, A.X) under --preprocess; sparse: the whole feature CSR).
+
+        A part batch (full_batch.PartBatch, --full_batch_parts): the batch's rows of that table, materialised by
+        ops.gather_rows into a table of the feature table's own pitch that every step reuses -- the dense layers then run
+        exactly the kernels of a full pass; a sparse feature CSR goes through ops.csr_slice, as ``upload`` does."""
+        if isinstance(sb, PartBatch):
+            if self._history or sb.L != self.L or sb.N > self.num_data:
+                raise ValueError("a part batch needs a model without history, with %d aggregation layer(s) over at least %d "
+                                 "vertices" % (sb.L, sb.N))
+            if self.feature_bf16:
+                raise ValueError("a part batch gathers its input rows into an fp32 table: this model's feature table is bfloat16")
+            if self.sparse_input and self.sparse_mm:
+                return sb.cur(SparseInput(ops.csr_slice(self.features_dev, sb.ids, rows_dev=sb.ids_dev, with_coo_rows=True)))
+            f = self.features_dev
+            tab = self.__dict__.get('_part_input')
+            if tab is None or tab.shape[0] < sb.N:
+                # (the rows of the largest batch seen, on the feature table's row pitch)
+                d, ld = int(f.shape[1]), int(f.stride(0)) if f.shape[0] > 1 else int(f.shape[1])
+                tab = self._part_input = torch.empty((sb.N, max(ld, d)), dtype=torch.float32, device=self.device)[:, :d]
+            return sb.cur(ops.gather_rows(f, sb.ids_dev, out=tab[:sb.N]))
         if self._history or sb.L != self.L or sb.N != self.num_data:
             raise ValueError("a static batch needs a model without history, with %d aggregation layer(s) over %d vertices"
                              % (sb.L, sb.N))

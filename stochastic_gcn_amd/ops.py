@@ -19,6 +19,8 @@ Reference seams replaced:
   spattn / spattn_bwd   softmax dot-product attention over a CSR pattern and its backward (--aggregator attn: every vertex weighs
                   its neighbours by a softmax over pairwise scores; no reference counterpart); ``keep`` < 1: dropout on the
                   coefficients (--attn_dropout) under the hash mask of attn_key / attn_kept
+  csr_induce      the induced subgraph A[S, S] of a resident CSR with its stable transpose and plans, cut on the device
+                  (--full_batch_parts: the matrix of a Cluster-GCN step; no reference counterpart)
   history_error   how far a stored history is from the exact activations (no reference counterpart; exact_history.py)
 """
 import ctypes as C
@@ -883,6 +885,134 @@ def gather_f32(src, idx):
     out = torch.empty(idx.shape[0], dtype=torch.float32, device=src.device)
     check(lib.sgcn_gather_f32(src.data_ptr(), idx.data_ptr(), int(idx.shape[0]), out.data_ptr(), _stream()))
     return out
+
+
+# ---- the induced subgraph A[S, S] of a resident CSR (sgcn_induce.hip; --full_batch_parts) -----------------------------------
+INDUCE_NORMS = ('keep', 'rows')
+
+
+def check_induce_ids(ids, N):
+    """The host check of a vertex subset (the device trusts it): int32 ids in [0, N), ascending and unique."""
+    r = np.asarray(ids)
+    if r.ndim != 1 or r.size == 0 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("the vertices of an induced subgraph must be a non-empty 1-D integer array")
+    if int(r[0]) < 0 or int(r[-1]) >= N or (r.size > 1 and not bool(np.all(r[1:] > r[:-1]))):
+        raise ValueError("the vertices of an induced subgraph must be ascending, unique and in [0, %d)" % N)
+    return np.ascontiguousarray(r, dtype=np.int32)
+
+
+class _InduceBuffers(object):
+    """What csr_induce writes, kept with the resident matrix and reused by every step: the vertex map (N words), the
+    per-row arrays (grown to the largest subset seen), the per-entry arrays of the block and of its transpose (grown to the
+    largest bound seen), the transposition's workspace, and one pinned host buffer for the two row pointers."""
+
+    def __init__(self, N, device):
+        self.device, self.rows, self.entries, self.ws_ints = device, -1, -1, -1
+        self.map = torch.empty(max(N, 1), dtype=torch.int32, device=device)
+
+    def fit(self, n, bound, transposition=True):
+        dev = self.device
+        if n > self.rows:
+            self.rows = n
+            # (n + 2 words each: the transposition runs over n + 1 columns, the pad column last)
+            self.rowptr, self.t_rowptr = (torch.empty(n + 2, dtype=torch.int32, device=dev) for _ in range(2))
+            self.full, self.kept, self.rscale = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+            self.host = torch.empty(2 * (n + 1), dtype=torch.int32).pin_memory()
+        if bound > self.entries:
+            self.entries = bound
+            e = max(bound, 1)
+            self.col, self.coo, self.t_row, self.t_src = (torch.empty(e, dtype=torch.int32, device=dev) for _ in range(4))
+            self.val, self.t_val = (torch.empty(e, dtype=torch.float32, device=dev) for _ in range(2))
+        need = int(lib.sgcn_csr_transpose_ws_ints(n + 1, bound)) if transposition else 0
+        if need > self.ws_ints:
+            self.ws_ints = need
+            self.ws = torch.empty(max(need, 1), dtype=torch.int32, device=dev)
+
+
+def csr_induce(A, ids_host, ids_dev=None, norm='keep', plan_T=0):
+    """The induced subgraph A[ids][:, ids] of the resident square DeviceCSR ``A`` as a DeviceCSR with ``.transpose`` set (and
+    ``.coo_rows``), cut on the device: sgcn_induce_map_i32, sgcn_csr_induce_count, sgcn_csr_induce_fill, then the stable
+    transposition of the block (sgcn_csr_transpose_index on its COO rows, the values following through sgcn_gather_f32).
+    Where ``A.transpose`` is resident (DeviceCSR.from_scipy(..., with_transpose=True): rows sorted), the transposed block is
+    instead the same cut of that matrix -- two more launches of the induce kernels, an entry scaled by its column's factor --
+    which is the stable transpose with the block's own value bits at a thousandth of the transposition's time on a block of
+    29,000 columns (profiles/full_batch_parts.jsonl); the trainer keeps the transpose resident for that reason.
+
+    ``ids_host``: ascending, unique, in [0, N) (checked here); ``ids_dev``: the same ids on the device, uploaded if not given.
+    ``norm``: 'keep' -- the stored values; with sorted, duplicate-free rows the block then has the row pointer, column ids
+    and value bits of SciPy's A[ids][:, ids].  'rows' -- row i is scaled by full_i / kept_i, the sums of its values over
+    all its entries and over the kept ones (1 where kept_i == 0), so that a row keeps its value sum: what a row-normalised
+    adjacency needs to stay one after inter-part edges are dropped.
+
+    Everything is launched before the host learns the block's size: the per-entry buffers hold ``bound`` elements, the
+    selected rows' stored entries (from A.host_rowptr), and fill pads the unused tail with a column behind the last one, which
+    the stable transposition sorts behind every real entry.  Both row pointers then reach the host through one pinned buffer
+    and ONE synchronisation, and the segment plans come from scheduler.build_plan(rowptr, plan_T) -- the call, with the same
+    T, that DeviceCSR.from_scipy makes.  The buffers belong to ``A`` and are reused: a block is valid until the next call."""
+    if A.host_rowptr is None:
+        raise ValueError("csr_induce needs A.host_rowptr")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("csr_induce needs a square (vertex x vertex) matrix")
+    if norm not in INDUCE_NORMS:
+        raise ValueError("norm must be one of %s, got %r" % ('/'.join(INDUCE_NORMS), norm))
+    N, dev = int(A.shape[0]), A.val.device
+    ids_host = check_induce_ids(ids_host, N)
+    n = int(ids_host.shape[0])
+    hp, At = A.host_rowptr, A.transpose
+    bound = int((hp[ids_host + 1].astype(np.int64) - hp[ids_host]).sum())
+    if At is not None:
+        if At.host_rowptr is None or tuple(At.shape) != tuple(A.shape):
+            raise ValueError("csr_induce needs the resident transpose with its host_rowptr")
+        tp = At.host_rowptr
+        bound = max(bound, int((tp[ids_host + 1].astype(np.int64) - tp[ids_host]).sum()))
+    if ids_dev is None:
+        ids_dev = torch.from_numpy(ids_host).to(dev, non_blocking=True)
+    _dev(ids_dev, torch.int32, "ids_dev")
+    b = getattr(A, '_induce', None)
+    if b is None:
+        b = A._induce = _InduceBuffers(N, dev)
+    b.fit(n, bound, transposition=At is None)
+    st = _stream()
+    a_p, a_c, a_v, ids, vmap = A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), ids_dev.data_ptr(), b.map.data_ptr()
+    check(lib.sgcn_induce_map_i32(ids, n, N, vmap, st))
+    check(lib.sgcn_csr_induce_count(a_p, a_c, a_v, ids, n, vmap, b.rowptr.data_ptr(), b.full.data_ptr(), b.kept.data_ptr(), st))
+    rscale = None
+    if norm == 'rows':
+        # n values, between two launches: full / kept is one correctly rounded fp32 division, exactly 1 where nothing was dropped
+        rscale = torch.where(b.kept[:n] == 0, torch.ones((), dtype=torch.float32, device=dev), b.full[:n] / b.kept[:n],
+                             out=b.rscale[:n])
+    check(lib.sgcn_csr_induce_fill(a_p, a_c, a_v, ids, n, vmap, b.rowptr.data_ptr(), _ptr(rscale), b.col.data_ptr(),
+                                   b.val.data_ptr(), b.coo.data_ptr(), 0, bound if At is None else 0, st))
+    if At is not None:
+        # the same cut of the resident transpose: row j of it holds the source rows of column j in ascending order, so its
+        # block IS the stable transpose of the block above; an entry's scale is that of its relabelled column (the block's row)
+        t_p, t_c, t_v = At.rowptr.data_ptr(), _ptr(At.col), _ptr(At.val)
+        check(lib.sgcn_csr_induce_count(t_p, t_c, None, ids, n, vmap, b.t_rowptr.data_ptr(), None, None, st))
+        check(lib.sgcn_csr_induce_fill(t_p, t_c, t_v, ids, n, vmap, b.t_rowptr.data_ptr(), _ptr(rscale), b.t_row.data_ptr(),
+                                       b.t_val.data_ptr(), None, 1, 0, st))
+    else:
+        check(lib.sgcn_csr_transpose_index(n + 1, bound, b.col.data_ptr(), b.coo.data_ptr(), b.t_rowptr.data_ptr(),
+                                           b.t_row.data_ptr(), b.t_src.data_ptr(), b.ws.data_ptr(), st))
+        check(lib.sgcn_gather_f32(b.val.data_ptr(), b.t_src.data_ptr(), bound, b.t_val.data_ptr(), st))
+    b.host[:n + 1].copy_(b.rowptr[:n + 1], non_blocking=True)
+    b.host[n + 1:2 * (n + 1)].copy_(b.t_rowptr[:n + 1], non_blocking=True)
+    torch.cuda.current_stream().synchronize()            # the one synchronisation of a build
+    rp, trp = (np.array(h, dtype=np.int32) for h in (b.host[:n + 1].numpy(), b.host[n + 1:2 * (n + 1)].numpy()))
+    nnz = int(rp[n])
+    if nnz > bound or int(trp[n]) != nnz:
+        raise RuntimeError("csr_induce: the block holds %d entries, its transpose %d, the bound is %d" % (nnz, int(trp[n]), bound))
+
+    def csr(rowptr_dev, host_rowptr, col, val):
+        seg, fix, nslots = build_plan(host_rowptr, plan_T)
+        return DeviceCSR((n, n), rowptr_dev[:n + 1], col[:nnz], val[:nnz], DevicePlan(seg, fix, nslots, dev),
+                         host_rowptr=host_rowptr)
+    block = csr(b.rowptr, rp, b.col, b.val)
+    block.coo_rows = b.coo[:nnz]
+    block.transpose = csr(b.t_rowptr, trp, b.t_row, b.t_val)
+    block.transpose.transpose = block
+    if getattr(A, '_unique_cols', False):          # (check_unique_cols passed on A: its blocks store no column twice either)
+        block._unique_cols = block.transpose._unique_cols = True
+    return block
 
 
 def adam_step(theta, grad, m, v, lr_t, beta1, beta2, eps=1e-8):

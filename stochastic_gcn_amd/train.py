@@ -26,7 +26,8 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
-from .full_batch import (StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
+from .full_batch import (InducedMatrix, PartBatch, PartSchedule, check_full_batch_parts, part_stats, partition,
+                         StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
 from .models import make_template
@@ -233,6 +234,9 @@ class Trainer(object):
         self.full_batch, self.test_full_batch = check_full_batch(world=int(os.environ.get("WORLD_SIZE", "1")))
         # (--edge_dropout outside [0, 1), without --full_batch, on the LDS sweep or with --gradvar: too)
         self.edge_dropout = check_edge_dropout()
+        # (--full_batch_parts negative, without --full_batch, q outside [1, P], with an edge mask, a bfloat16 feature table or a
+        # sweep kernel: too; P against the number of vertices once the graph is loaded)
+        self.parts, self.parts_per_step, self.part_norm = check_full_batch_parts()
         # (--aggregator max without both full-graph modes, with a bfloat16 table or an edge mask: too)
         self.max_aggregator = check_aggregator()
         # (--aggregator attn likewise; --attn_scale negative, non-finite, or set without attn: too)
@@ -344,7 +348,13 @@ class Trainer(object):
         self.static_matrices = []         # (adjacency, StaticMatrix): an exact history pass over the same adjacency shares it
         self._labels_dev = None           # ONE N x C label table on the device for both static batches
         caches = plan_cache_paths(FLAGS.dataset)
-        if self.full_batch:
+        if self.full_batch and self.parts:
+            # Cluster-GCN steps: no training StaticMatrix is planned -- train_adj lives once as a DeviceCSR, and every step
+            # cuts its own block out of it on the device
+            t = time()
+            self._setup_parts(train_adj)
+            self.static_setup_s += time() - t
+        elif self.full_batch:
             # exact full-graph training: no sampler, no prefetcher, no staging slots -- one static batch over train_adj
             t = time()
             self.train_static = self._static_batch(train_adj, 'train', caches[0], self.train_model, self.train_d,
@@ -409,6 +419,80 @@ class Trainer(object):
         if self._labels_dev is None:
             self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
         return StaticBatch(mat, self._labels_dev, np.sort(np.asarray(rows)), model.L, self.device)
+
+    # ---- Cluster-GCN steps on device-cut subgraphs (--full_batch_parts; full_batch.py) --------------------------------------
+    def _setup_parts(self, train_adj):
+        """The resident training adjacency (ONE DeviceCSR with its transpose, rows sorted: the blocks cut from it keep the
+        stored order), the parts, the schedule of their groupings, the label table and the training-vertex mask; prints the
+        set-up line."""
+        N = int(train_adj.shape[0])
+        check_full_batch_parts(num_vertices=N)
+        a = train_adj.tocsr()
+        if not a.has_sorted_indices:
+            a = a.copy()
+            a.sort_indices()
+        # (with its transpose: the transposed block of a step is then the same cut of that matrix, ops.csr_induce)
+        self.train_csr = ops.DeviceCSR.from_scipy(a, self.device, with_plan=False, with_transpose=True)
+        if self.max_aggregator:
+            ops.check_unique_cols(self.train_csr)     # once, here: every block inherits the answer (ops.csr_induce)
+        self.part_ids = partition(a, self.parts, FLAGS.seed)
+        self.part_schedule = PartSchedule(self.part_ids, self.parts_per_step, FLAGS.seed)
+        self._parts_epoch = 0
+        self._train_mask = np.zeros(N, dtype=bool)
+        self._train_mask[np.asarray(self.train_d, dtype=np.int64)] = True
+        if self._labels_dev is None:
+            self._labels_dev = torch.from_numpy(np.ascontiguousarray(self.labels, dtype=np.float32)).to(self.device)
+        s = self.part_stats = part_stats(a, self.part_ids, self.train_d)
+        self.log('[sgcn] --full_batch_parts {}: {} parts per step, {} steps per epoch on induced subgraphs cut on the device '
+                 '(values: {}) | part sizes min / median / max = {} / {:g} / {} | training vertices per part = {} / {:g} / {} | '
+                 '{:.1f} % of the nonzeros lie inside parts'.format(
+                     self.parts, self.parts_per_step, len(self.part_schedule), self.part_norm, s['sizes'][0], s['sizes'][1],
+                     s['sizes'][2], s['train'][0], s['train'][1], s['train'][2], 100.0 * s['inside']))
+
+    def part_batch(self, ids):
+        """The batch of one step over the vertex set ``ids`` (ascending): the block cut out of the resident adjacency with its
+        transpose and plans (ops.csr_induce), labels[ids], and the loss rows -- the positions within ``ids`` of the training
+        vertices.  None where ``ids`` holds no training vertex."""
+        rows = np.flatnonzero(self._train_mask[ids]).astype(np.int32)
+        if rows.size == 0:
+            return None
+        ids_dev = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.device, non_blocking=True)
+        block = ops.csr_induce(self.train_csr, ids, ids_dev, norm=self.part_norm)
+        return PartBatch(ids, ids_dev, InducedMatrix(block, self.device, bf16=full_batch_bf16()), self._labels_dev, rows,
+                         self.train_model.L, self.device)
+
+    def train_epoch_parts(self):
+        """One epoch of Cluster-GCN steps: for every group of the epoch's schedule build the batch, run_one_step, next.  A
+        group without a training vertex is skipped and counted; last_epoch['steps'] is the number of steps run.  Building a
+        batch synchronises once (the block's row pointers), so the host does not run ahead of the device by more than a step."""
+        model = self.train_model
+        t = time()
+        model.init_counts()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        outs, steps, skipped, build_s = None, 0, 0, 0.0
+        for ids in self.part_schedule.epoch(self._parts_epoch):
+            t1 = time()
+            batch = self.part_batch(ids)
+            build_s += time() - t1
+            if batch is None:
+                skipped += 1
+                continue
+            batch.dropout = FLAGS.dropout
+            outs = model.run_one_step(self.sess, batch, sync=False)
+            steps += 1
+        self._parts_epoch += 1
+        host_loop_s = time() - t
+        ev1.record()
+        torch.cuda.synchronize()
+        model.run_t = max(model.run_t, ev0.elapsed_time(ev1) * 1e-3)
+        if outs is not None:          # Averager(1) of the reference = the last step's values
+            self.avg_loss.add(float(outs[1]))
+            self.avg_acc.add(float(outs[2]))
+        self.last_epoch = dict(train_wall_s=time() - t, steps=steps, skipped=skipped, sch_wait_s=build_s, host_loop_s=host_loop_s,
+                               producer_s=None, sampled_edges=float(model.adj_sizes.sum()), full_edges=0.0,
+                               field0=float(model.field_sizes[0]))
+        return t, build_s
 
     # ---- the exact history passes (exact_history.py) ------------------------------------------------
     def _exact_history(self, model, adj, which, cache_path):
@@ -606,7 +690,10 @@ class Trainer(object):
     # ---- one training epoch (gcn/train.py:182-209) ----------------------------------------------
     def train_epoch_full_batch(self):
         """One eager step over the whole graph: forward, loss over the train ids, backward, Adam.  No step program: at N
-        rows the launch chain is not the bound.  The dropout keys come from the model's step counter, as in any step."""
+        rows the launch chain is not the bound.  The dropout keys come from the model's step counter, as in any step.
+        Under --full_batch_parts: the epoch's Cluster-GCN steps (train_epoch_parts)."""
+        if getattr(self, 'parts', 0):
+            return self.train_epoch_parts()
         model = self.train_model
         t = time()
         model.init_counts()
