@@ -60,7 +60,9 @@ const char* sgcn_last_error(void);
  *       sgcn_spattn_mh_csr_f32 / sgcn_spattn_mh_csr_bwd_q_f32 / sgcn_spattn_mh_csr_bwd_kv_f32; their forms with dropout on
  *       the coefficients -- sgcn_spattn_drop_csr_f32 / sgcn_spattn_drop_csr_bwd_q_f32 / sgcn_spattn_drop_csr_bwd_kv_f32;
  *       learned additive attention scores (GAT) -- sgcn_gat_scores_f32 / sgcn_spgat_csr_f32 / sgcn_spgat_csr_bwd_u_f32 /
- *       sgcn_spgat_csr_bwd_v_f32 / sgcn_gat_scores_bwd_f32) */
+ *       sgcn_spgat_csr_bwd_v_f32 / sgcn_gat_scores_bwd_f32; dictionary plans of the column sweep -- sgcn_csbuild_dict /
+ *       sgcn_csbuild_export_dict and the trailing fields dev_tile_vals / dev_tile_nvals / dict_bits of sgcn_csplan_t, which a
+ *       plan without a dictionary leaves zero) */
 int sgcn_abi_version(void);
 
 /* ======================================================================================
@@ -155,6 +157,13 @@ typedef struct {
                                        the POSITION of its column to the clock (G = 2 / 4 kernels; pace and slack keep
                                        their units).  Pacing only -- results do not depend on it.                     */
     int32_t warp_shift;
+    /* A DICTIONARY plan (sgcn_csbuild_dict; G = 2 only; additive trailing fields: all zero = a plan with dev_val): the
+     * values of a tile's entries live in a table of the tile's distinct value bit patterns and an entry's column word
+     * carries its table index in bits [28 - dict_bits, 28) -- colrow = col | index << (28 - dict_bits) | local_row << 28,
+     * K <= 2^(28 - dict_bits).  dev_val is not read (null).  The sweep kernels keep a wave's table in the LDS. */
+    const float* dev_tile_vals;     /* [ntiles << dict_bits]: tile t's table at t << dict_bits, ascending as uint32     */
+    const int32_t* dev_tile_nvals;  /* [ntiles]: filled length of each table, 1 .. 2^dict_bits (0 for an empty tile)      */
+    int32_t dict_bits;              /* 0 = not a dictionary plan; otherwise 5 .. 10                                       */
 } sgcn_csplan_t;
 /* row_group (nullable, [M], labels >= 0): tiles are formed inside groups, groups in label order
  * (locality-preserving reordering of a graph that has communities, e.g. from sgcn_reorder_lp);
@@ -199,6 +208,16 @@ int sgcn_csbuild_sizes(const sgcn_csbuild_t* b, int64_t* ntiles, int64_t* nentri
 int sgcn_csbuild_export(const sgcn_csbuild_t* b, int64_t* host_tile_ptr, int32_t* host_colrow, float* host_valout,
                         int32_t* host_tile_rows, int32_t* host_tile_slots, sgcn_fix_t* host_fix);
 void sgcn_csbuild_free(sgcn_csbuild_t* b);
+/* Turn a built two-group plan (ngroups = 2; any other is left as it is) of a matrix with K columns into a DICTIONARY plan (sgcn_csplan_t.dict_bits)
+ * where that is possible: bits = min(10, 28 - ceil(log2 K)); when sgcn_tune "cs_dict" is 1, bits >= 5 and EVERY tile, the
+ * pad marker 0x80000000 included, holds at most 2^bits distinct value bit patterns -- and the tables together are at most
+ * half as long as the entries (a matrix of arbitrary values gains nothing) --, *bits_out = bits, the builder's column
+ * words get the table indices, and sgcn_csbuild_export may be given a null valout; sgcn_csbuild_export_dict then copies
+ * the tables out: tile_vals [ntiles << bits] (a tile's distinct patterns ascending as uint32 -- a function of the matrix
+ * alone --, zero-filled behind them), tile_nvals [ntiles].  Otherwise *bits_out = 0 and the builder is left untouched,
+ * byte for byte.  The decision is per plan.  A column >= K is an error. */
+int sgcn_csbuild_dict(sgcn_csbuild_t* b, int32_t K, int32_t* bits_out);
+int sgcn_csbuild_export_dict(const sgcn_csbuild_t* b, float* host_tile_vals, int32_t* host_tile_nvals);
 /* sgcn_csplan_t.dev_warp's HOST copy from the matrix's column array (parallel histogram): table[b] = share of the
  * nonzeros in columns < (b << *shift), scaled to [0, K), for the smallest shift that gives <= max_buckets entries
  * (table must hold max_buckets).  mode 0 ("auto"): *nbuckets = 0 (no table: the clock stays linear in the column id)
@@ -310,6 +329,9 @@ int sgcn_lds_profile_buffer(void* dev_buf);
  *   line -- and a plan of several launch rounds keeps its tiles longest first: fewer pads, a shorter heaviest tile per
  *   round, the same products bit for bit; 0 = dealt by weight alone (the plan every build before the knob made).  G = 1
  *   plans are dealt by weight either way.
+ *   cs_dict (default 1), read by sgcn_csbuild_dict: 1 = a two-group plan whose tiles each hold few distinct values (a
+ *   normalised adjacency: one value per row or per column) keeps them in per-tile tables instead of one fp32 per entry --
+ *   half the plan-entry bytes of every sweep launch, the same products bit for bit; 0 = every plan keeps dev_val.
  *   step_overlap (library default 1; the step program sets it from its flags, 0 unless --agg_overlap or a non-lean mode):
  *   in sgcn_step_run the AUX_* / VR_AGG_PRE ops (and, without --group_dw / --lean_sync, weight-gradient GEMMs and loss
  *   statistics) go to an auxiliary stream

@@ -38,7 +38,9 @@ class CsPlan(C.Structure):
                 ("nslots", C.c_int64), ("dev_ws", C.c_void_p), ("ws_elems", C.c_int64),
                 ("round_tiles", C.c_int64), ("host_tile_nnz_hint", C.c_void_p),
                 ("pace_ns_per_nnz", C.c_int32), ("G", C.c_int32), ("xcd_map", C.c_int32),
-                ("dev_warp", C.c_void_p), ("warp_shift", C.c_int32)]
+                ("dev_warp", C.c_void_p), ("warp_shift", C.c_int32),
+                # a dictionary plan (sgcn_csbuild_dict); all zero otherwise
+                ("dev_tile_vals", C.c_void_p), ("dev_tile_nvals", C.c_void_p), ("dict_bits", C.c_int32)]
 
 
 class LdsPlan(C.Structure):
@@ -109,6 +111,8 @@ SIGNATURES = {
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sgcn_csbuild_export": (C.c_int, [P, P, P, P, P, P, P]),
     "sgcn_csbuild_free": (None, [P]),
+    "sgcn_csbuild_dict": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int32)]),
+    "sgcn_csbuild_export_dict": (C.c_int, [P, P, P]),
     "sgcn_cs_warp_table": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, P,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sgcn_csr_transpose_host": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),

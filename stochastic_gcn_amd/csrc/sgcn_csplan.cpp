@@ -441,6 +441,9 @@ struct sgcn_csbuild {
     std::vector<int32_t> tile_tid;
     std::vector<int64_t> tile_off;
     int nthreads = 1;
+    int32_t dict_bits = 0;                            // > 0: a dictionary plan (sgcn_csbuild_dict) -- the column words carry table indices
+    std::vector<uint32_t> tile_vals;                  // [ntiles << dict_bits] value bit patterns
+    std::vector<int32_t> tile_nvals;                  // [ntiles]
 };
 
 namespace {
@@ -603,7 +606,7 @@ int export_plan(const sgcn_csbuild* B, int64_t* tile_ptr, int32_t* colrow, float
                 int32_t* tile_slots, sgcn_fix_t* fix) {
     if (B->count_only) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export: a count-only build holds no entries");
     if (B->ntiles > 0 && (!tile_ptr || !tile_rows || !tile_slots)) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export: bad argument");
-    if (B->nentries > 0 && (!colrow || !valout)) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export: bad argument");
+    if (B->nentries > 0 && (!colrow || (!valout && B->dict_bits == 0))) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export: bad argument");
     if (B->nfix > 0 && !fix) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export: split rows but no fix array");
     if (tile_ptr) memcpy(tile_ptr, B->tile_ptr.data(), B->tile_ptr.size() * sizeof(int64_t));
     if (B->tile_rows.size()) {
@@ -614,6 +617,7 @@ int export_plan(const sgcn_csbuild* B, int64_t* tile_ptr, int32_t* colrow, float
     auto split = [&](const uint64_t* src, int64_t n, int64_t at) {
         for (int64_t i = 0; i < n; i++) {
             colrow[at + i] = (int32_t)(uint32_t)src[i];
+            if (!valout) continue;                                // (a dictionary plan: the values are in the tiles' tables)
             const uint32_t bits = (uint32_t)(src[i] >> 32);
             memcpy(valout + at + i, &bits, 4);
         }
@@ -630,9 +634,103 @@ int export_plan(const sgcn_csbuild* B, int64_t* tile_ptr, int32_t* colrow, float
     return SGCN_OK;
 }
 
+// ---- dictionary plans (sgcn_csplan_t.dict_bits) ----------------------------------------------------------------------
+// The values of a normalised adjacency say little: a tile of A (one value per row) holds ~25 distinct bit patterns, a tile
+// of A^T (one per column) a few hundred, and the column word of a matrix with K < 2^18 columns has ten idle bits.  So a
+// tile's values become a table of its distinct patterns -- ascending as uint32: a function of the tile's entries alone,
+// whatever thread built it -- and an entry carries its index next to its column.  The pad marker is a pattern like any
+// other.  One more pass over the entries the builder holds, tile-parallel; nothing is changed unless every tile fits.
+int make_dict(sgcn_csbuild* B, int32_t K, int32_t* bits_out) {
+    *bits_out = 0;
+    if (B->count_only) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: a count-only build holds no entries");
+    if (B->dict_bits != 0) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: already a dictionary plan");
+    if (K < 0 || K > (1 << 28)) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: K outside [0, 2^28]");
+    if (B->G != 2) return SGCN_OK;                                  // (the two-group kernel is the one that reads tables)
+    if (sgcn_tune_get("cs_dict") <= 0) return SGCN_OK;
+    int lg = 0;
+    while (((int64_t)1 << lg) < (int64_t)K) lg++;                   // ceil(log2 K)
+    const int bits = std::min(10, 28 - lg);
+    if (bits < 5 || B->ntiles == 0) return SGCN_OK;
+    const uint32_t colbits = (uint32_t)(28 - bits), cap = 1u << bits;
+    const int64_t nt = B->ntiles;
+    auto tile_entries = [&](int64_t t) { return B->arena[(size_t)B->tile_tid[(size_t)t]].data() + B->tile_off[(size_t)t]; };
+    std::vector<uint32_t> vals;
+    std::vector<int32_t> nvals;
+    try {
+        vals.assign((size_t)nt << bits, 0u);
+        nvals.assign((size_t)nt, 0);
+    } catch (...) { return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: out of host memory"); }
+    std::atomic<int> over{0}, badcol{0};
+    bool ok = parallel_chunks(nt, 8, B->nthreads, [&](int64_t t0, int64_t t1, int) {
+        std::vector<uint32_t> u;
+        for (int64_t t = t0; t < t1 && !over.load(std::memory_order_relaxed); t++) {
+            const uint64_t* e = tile_entries(t);
+            const int64_t n = B->tile_ptr[(size_t)t + 1] - B->tile_ptr[(size_t)t];
+            u.resize((size_t)n);
+            int bad = 0;
+            for (int64_t i = 0; i < n; i++) {
+                u[(size_t)i] = (uint32_t)(e[i] >> 32);
+                bad |= ((uint32_t)e[i] & 0x0FFFFFFFu) >= (uint32_t)std::max(K, 1);
+            }
+            if (bad) badcol.store(1);
+            std::sort(u.begin(), u.end());
+            u.erase(std::unique(u.begin(), u.end()), u.end());
+            if (u.size() > cap) { over.store(1); return; }
+            nvals[(size_t)t] = (int32_t)u.size();
+            std::copy(u.begin(), u.end(), vals.begin() + ((size_t)t << bits));
+        }
+    });
+    if (!ok) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: out of host memory");
+    if (badcol.load()) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: a column outside [0, K)");
+    if (over.load()) return SGCN_OK;                                // some tile has too many distinct values: the plan stays as built
+    // ... and so does a plan whose tables would not be SHORT: a launch reads a tile's table where it read the tile's values,
+    // so tables of more than half the entries (a matrix of arbitrary values, every nonzero its own pattern) save little
+    // and cost an LDS write and read per value on top
+    int64_t total = 0;
+    for (int64_t t = 0; t < nt; t++) total += nvals[(size_t)t];
+    if (2 * total > B->nentries) return SGCN_OK;
+    ok = parallel_chunks(nt, 8, B->nthreads, [&](int64_t t0, int64_t t1, int) {
+        for (int64_t t = t0; t < t1; t++) {
+            uint64_t* e = const_cast<uint64_t*>(tile_entries(t));
+            const int64_t n = B->tile_ptr[(size_t)t + 1] - B->tile_ptr[(size_t)t];
+            const uint32_t* tab = vals.data() + ((size_t)t << bits);
+            const uint32_t* tab_end = tab + nvals[(size_t)t];
+            for (int64_t i = 0; i < n; i++) {
+                const uint32_t idx = (uint32_t)(std::lower_bound(tab, tab_end, (uint32_t)(e[i] >> 32)) - tab);
+                e[i] |= (uint64_t)idx << colbits;
+            }
+        }
+    });
+    if (!ok) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: out of host memory");
+    B->dict_bits = bits;
+    B->tile_vals.swap(vals);
+    B->tile_nvals.swap(nvals);
+    *bits_out = bits;
+    return SGCN_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sgcn_csbuild_dict(sgcn_csbuild_t* b, int32_t K, int32_t* bits_out) {
+    if (!b || !bits_out) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: bad argument");
+    try {
+        return make_dict(b, K, bits_out);
+    } catch (...) {
+        return sgcn::fail(SGCN_ERR_INVALID, "csbuild_dict: out of host memory");
+    }
+}
+
+int sgcn_csbuild_export_dict(const sgcn_csbuild_t* b, float* tile_vals, int32_t* tile_nvals) {
+    if (!b || b->dict_bits == 0) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export_dict: not a dictionary plan");
+    if (b->ntiles > 0 && (!tile_vals || !tile_nvals)) return sgcn::fail(SGCN_ERR_INVALID, "csbuild_export_dict: bad argument");
+    if (b->ntiles > 0) {
+        memcpy(tile_vals, b->tile_vals.data(), b->tile_vals.size() * sizeof(uint32_t));
+        memcpy(tile_nvals, b->tile_nvals.data(), b->tile_nvals.size() * sizeof(int32_t));
+    }
+    return SGCN_OK;
+}
 
 int sgcn_csplan_build(const int32_t* rowptr, const int32_t* col, const float* val, int32_t M, int32_t ngroups, int32_t R,
                       int32_t T, int32_t round_tiles, int32_t align, const int32_t* row_group, const uint32_t* host_warp,

@@ -36,6 +36,7 @@ int g_tune_cs_pace = 0;
 int g_tune_cs_slack = 0;
 int g_tune_cs_noextra = 0;
 int g_tune_cs_deal = 1;               // lane-group plans (sgcn_csplan.cpp): 1 = rows dealt to bins by column spread too, 0 = by weight alone
+int g_tune_cs_dict = 1;               // lane-group plans (sgcn_csbuild_dict): 1 = per-tile value tables where every tile has few distinct values
 int g_tune_step_overlap = 1;
 int g_tune_step_fuse = 127;           // bit 0: the output layer's forward as the loss kernel's head, bit 1: its input gradient as the
                                      // tail, bit 2: the dense layer behind a split-K layer in that layer's reduce pass, bit 3: a layer's
@@ -66,6 +67,7 @@ int tune_get(const char* key) {
     if (!strcmp(key, "cs_slack")) return g_tune_cs_slack;
     if (!strcmp(key, "cs_noextra")) return g_tune_cs_noextra;
     if (!strcmp(key, "cs_deal")) return g_tune_cs_deal;
+    if (!strcmp(key, "cs_dict")) return g_tune_cs_dict;
     if (!strcmp(key, "step_overlap")) return tl_step_overlap >= 0 ? tl_step_overlap : g_tune_step_overlap;
     if (!strcmp(key, "step_fuse")) return tl_step_fuse >= 0 ? tl_step_fuse : g_tune_step_fuse;
     if (!strcmp(key, "cs_g2_wide")) return g_tune_cs_g2_wide;
@@ -319,6 +321,7 @@ extern "C" int sgcn_tune(const char* key, int64_t value) {
     if (!strcmp(key, "cs_slack")) { SGCN_REQUIRE(value >= 0, "cs_slack >= 0"); g_tune_cs_slack = (int)value; return SGCN_OK; }
     if (!strcmp(key, "cs_noextra")) { g_tune_cs_noextra = value != 0; return SGCN_OK; }
     if (!strcmp(key, "cs_deal")) { SGCN_REQUIRE(value == 0 || value == 1, "cs_deal in {0, 1}"); g_tune_cs_deal = (int)value; return SGCN_OK; }
+    if (!strcmp(key, "cs_dict")) { SGCN_REQUIRE(value == 0 || value == 1, "cs_dict in {0, 1}"); g_tune_cs_dict = (int)value; return SGCN_OK; }
     if (!strcmp(key, "step_overlap")) { g_tune_step_overlap = value != 0; return SGCN_OK; }
     if (!strcmp(key, "step_fuse")) { SGCN_REQUIRE(value >= 0 && value <= 127, "step_fuse in 0..127"); g_tune_step_fuse = (int)value; return SGCN_OK; }
     if (!strcmp(key, "cs_g2_wide")) { g_tune_cs_g2_wide = value != 0; return SGCN_OK; }

@@ -28,7 +28,8 @@
 // 32-row tiles -- live in git history, their measurements in profiles/HISTORY.md 3.1b and DESIGN.md 3.2):
 //   cs_spmm16_kernel<U, EXTRA>     one 16-row tile per wavefront, pinned accumulators, up to 320 columns per pass
 //   cs_spmm16g2k_kernel<U, WIDE>   two 16-row bins per wavefront on 128-column passes, software-pipelined, packed FMAs:
-//                                  what ColumnSweepCSR.choose_g selects for most widths (bench default at d = 602)
+//                                  what ColumnSweepCSR.choose_g selects for most widths (bench default at d = 602);
+//                                  DICT: the entries' values from a per-tile table in LDS (dictionary plans)
 //   cs_epilogue<G>                 the end of the G = 2 / G = 4 kernels: row ids and slots read once per wave, 16 stores back to back
 //   cs_fix_kernel<VW>              ordered sum of a split row's workspace slots
 // Every asm statement that enters the VGPR-indexing mode (s_set_gpr_idx_*: the index lives in M0) or points M0 at an
@@ -36,6 +37,7 @@
 // it.  M0 is a reserved (non-allocatable) register, which makes clang warn about the entry; the entry is intended.
 #pragma clang diagnostic ignored "-Winline-asm"
 #include "sgcn_dev.h"
+#include <cstring>
 
 namespace sgcn {
 
@@ -59,6 +61,13 @@ struct CsArgs {
     int32_t xcd_map;       // consecutive tiles of the launch on the same XCD (grouped plans)
     const uint32_t* warp;  // sweep position of column bucket (col >> warp_shift), in [0, K): the clock runs in WORK
     int32_t warp_shift;    // coordinates (plan->dev_warp; null: positions are the column ids themselves)
+};
+// ... and of a dictionary plan (plan->dict_bits): what the DICT instantiations of cs_spmm16g2k_kernel take.  A type of its own,
+// so that every other kernel keeps the argument block -- and with it the instructions -- it had.
+struct CsDictArgs : CsArgs {
+    const float* tile_vals;        // tile t's value table at t << dict_bits
+    const int32_t* tile_nvals;     // its filled length
+    int32_t dict_bits;             // the table index of an entry: bits [28 - dict_bits, 28) of its column word
 };
 
 // The sweep clock in work coordinates.  A clock that is linear in the COLUMN ID holds the lock-step only if the nonzeros are
@@ -395,8 +404,18 @@ __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
 //  * the clock comparison is integer scalar arithmetic.
 // Requires every tile's entry count to be a multiple of 64 (the plan pads to that).  WIDE: K >= 2^24 or B beyond 4 GiB
 // -- 64-bit row offsets.
-template <int U, bool WIDE, bool WARP = false, class BT = float>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void cs_spmm16g2k_kernel(CsArgs a) {
+//
+// DICT (a dictionary plan, sgcn_csplan_t.dict_bits): the one compulsory stream of a launch that is pure overhead is the
+// plan entries, fetched again in every pass, and half of it is the fp32 value of each entry -- which on a normalised
+// adjacency is one of a few dozen (A) or a few hundred (A^T) bit patterns per tile.  The wave copies its tile's table
+// (at most 1,024 floats) into its own 4 KiB of LDS in the prologue, beside the tile_ptr load, and an entry's value is one
+// ds_read_b32 at the index that rides in the column word; the word alone is fetched.  The lookup of a chunk's entries is
+// made where the chunk's words are first needed anyway (the last batch of the chunk in front of it gathers from them),
+// never right behind their load, and it strips the index from the word, so everything that takes a column from the word
+// -- pace, wpos, gather, gidx, the u24 multiply -- sees the parent's word.  The same value bits feed the same FMAs in the
+// same order: the same output bits.  No barrier: a wave reads only what it wrote itself.
+template <int U, bool WIDE, bool WARP = false, class BT = float, bool DICT = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void cs_spmm16g2k_kernel(std::conditional_t<DICT, CsDictArgs, CsArgs> a) {
     typedef Vec<4>::type VT;
     typedef typename HRaw<BT, 4>::type RT;
     constexpr uint32_t kEsz = (uint32_t)sizeof(BT);
@@ -406,6 +425,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     constexpr int kLanesPerStep = 2;
     constexpr int kBatches = kSteps / U;
     static_assert(kBatches % 2 == 0, "the two buffers alternate evenly over a chunk");
+    static_assert(!DICT || kBatches >= 4, "a chunk's values are looked up three batches before its end");
     const int lane = threadIdx.x & 63;
     const bool hi = lane >= 32;
     const int li = lane & 31;
@@ -431,7 +451,37 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     // columns per tick in 16.16 fixed point (a launch lasts < 2^16 ticks of 10 ns; K / ticks < 2^15)
     const uint32_t cpt16 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.cols_per_tick * 65536.0f));
     const uint32_t slack = (uint32_t)a.slack_cols;
+    // DICT: the table's length first -- its loads then run beside the tile_ptr -> entries chain, not behind it
+    typedef __attribute__((address_space(3))) float lds_float;
+    typedef __attribute__((address_space(3))) VT lds_vec;
+    lds_float* tab = nullptr;
+    uint32_t colbits = 0, idxmask = 0;
+    int nvals = 0;
+    if constexpr (DICT) {
+        __shared__ VT dict_tab[kBlock / kWave][1024 / 4];        // 4 KiB per wave, 16 KiB per workgroup: 64 KiB per CU at 4 waves per SIMD
+        tab = (lds_float*)dict_tab[threadIdx.x / kWave];
+        colbits = 28u - (uint32_t)a.dict_bits;
+        idxmask = (1u << a.dict_bits) - 1u;
+        nvals = min(__builtin_amdgcn_readfirstlane(a.tile_nvals[tile]), 1 << a.dict_bits);
+    }
     const int64_t start = a.tile_ptr[tile], end = a.tile_ptr[tile + 1];
+    if constexpr (DICT) {
+        // (tables lie 2^dict_bits >= 32 floats apart and are zero-filled: the last float4 of a table stays inside it)
+        const VT* src = reinterpret_cast<const VT*>(a.tile_vals + (tile << a.dict_bits));
+        VT t[4];
+        static_for<4>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            t[q] = vzero<4>();
+            if (4 * (q * kWave + lane) < nvals) t[q] = src[q * kWave + lane];
+        });
+        static_for<4>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            if (4 * (q * kWave + lane) < nvals) *(lds_vec*)(tab + 4 * (q * kWave + lane)) = t[q];
+        });
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the wave reads what its other lanes wrote: order only, no instruction)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
 
     // one chunk of plan entries: lane l holds entry l (even lanes bin 0, odd lanes bin 1 of step l / 2)
     auto entries = [&](int64_t p, uint32_t& cr, float& v) {
@@ -439,13 +489,35 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         v = __int_as_float((int)0x80000000);                       // beyond the tile: pads on column 0
         if (p < end) {
             cr = a.colrow[p + lane];
-            v = a.val[p + lane];
-            uint32_t c = cr & kColMask;
-            if (a.cscale && __float_as_int(v) != (int)0x80000000) {
-                v *= a.cscale[c];
-                if (__float_as_int(v) == (int)0x80000000) v = 0.f;
+            if constexpr (DICT) v = 0.f;                           // (DICT: the word alone; +0 = lookup() has yet to make the entry of it)
+            if constexpr (!DICT) {
+                v = a.val[p + lane];
+                uint32_t c = cr & kColMask;
+                if (a.cscale && __float_as_int(v) != (int)0x80000000) {
+                    v *= a.cscale[c];
+                    if (__float_as_int(v) == (int)0x80000000) v = 0.f;
+                }
+                if (a.gidx) { c = (uint32_t)a.gidx[c]; cr = (cr & ~kColMask) | c; }
             }
-            if (a.gidx) { c = (uint32_t)a.gidx[c]; cr = (cr & ~kColMask) | c; }
+        }
+    };
+    // DICT: a chunk's values from the table, the index stripped from the words -- afterwards (cr, v) is what entries() of a
+    // plan with a value array returns, cscale and gidx included (a chunk beyond the tile stays the pads it is)
+    auto lookup = [&](uint32_t& cr, float& v) {
+        if constexpr (DICT) {
+            if (__float_as_int(v) != (int)0x80000000) {
+                v = tab[(cr >> colbits) & idxmask];
+                cr &= ~(idxmask << colbits);
+                uint32_t c = cr & kColMask;
+                if (a.cscale) {                                    // (asked first: without a column scale nothing here waits for v)
+                    const float s = a.cscale[c];
+                    if (__float_as_int(v) != (int)0x80000000) {
+                        v *= s;
+                        if (__float_as_int(v) == (int)0x80000000) v = 0.f;
+                    }
+                }
+                if (a.gidx) { c = (uint32_t)a.gidx[c]; cr = (cr & ~kColMask) | c; }
+            }
         }
     };
     // per-chunk scalars: the register offset (2 x local row id) of every entry's accumulator pair, 4 lanes x 8 bits per
@@ -537,6 +609,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     float cv, nv;
     entries(start, ccr, cv);
     entries(start + kWave, ncr, nv);
+    lookup(ccr, cv);                                // (DICT; the next chunk's: in the loop, two batches before its first use)
+    auto lookup_next = [&]() { if constexpr (DICT) lookup(ncr, nv); };
     Meta cm = meta(ccr, cv);
     RT buf[2][U];                                   // raw dwords: a bf16 operand is widened when it is applied
     uint32_t pnext = 0;                             // WARP: position of the next batch's first column
@@ -571,6 +645,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
                 hpin<BT, 4>(buf[k & 1][u]);
                 fma2(cm, cv, std::integral_constant<int, k * U + u>{}, hwiden<4>(buf[k & 1][u]));
             });
+            // DICT: the next chunk's words were asked for a chunk ago; wpos (the next batch) and gather (the one behind it) read
+            // them.  (The last statement of the body and a name of its own: the body's captures stay what they are without DICT.)
+            if constexpr (DICT && k == kBatches - 3) lookup_next();
         });
         ccr = ncr; cv = nv;
         cm = meta(ccr, cv);
@@ -912,6 +989,10 @@ static int cs_variant_text(const sgcn_csplan_t* plan, int32_t d, char* buf, int3
              b16 ? " [bf16 operand]" : "",
              (int)(v.nslab * ((plan->ntiles + round - 1) / round)), v.nslab, v.slab_floats,
              (long long)((plan->ntiles + round - 1) / round), (long long)round);
+    if (plan->dict_bits != 0) {      // (behind the geometry: bench.py makes the profiler's kernel name of the text in front of " x ")
+        const size_t n = strlen(buf);
+        if (n > 0 && buf[n - 1] == ')') snprintf(buf + n - 1, (size_t)buflen - (n - 1), "; values in per-tile tables of %d)", 1 << plan->dict_bits);
+    }
     return SGCN_OK;
 }
 
@@ -939,6 +1020,11 @@ static int spmm_cs(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
                  "spmm_cs: the plan must have 16-row bins and one, two or four lane groups per wavefront");
     SGCN_REQUIRE(plan->dev_tile_ptr && plan->dev_tile_rows && plan->dev_tile_slots && B && C,
                  "spmm_cs: null operand");
+    if (plan->dict_bits != 0) {      // a dictionary plan: two-group kernel only, the column and the index share 28 bits of the word
+        SGCN_REQUIRE(plan->G == 2 && plan->dict_bits >= 5 && plan->dict_bits <= 10 && plan->dev_tile_vals && plan->dev_tile_nvals,
+                     "spmm_cs: a dictionary plan has two lane groups, 5 .. 10 index bits and its tables");
+        SGCN_REQUIRE((int64_t)K <= ((int64_t)1 << (28 - plan->dict_bits)), "spmm_cs: K does not fit beside the plan's %d index bits", plan->dict_bits);
+    }
     SGCN_REQUIRE(K < (1 << 28), "spmm_cs: K too large for the packed column word");
     const int VW = 4;               // float4 per lane (16-byte aligned rows)
     if (kB16) {
@@ -1008,6 +1094,14 @@ static int spmm_cs(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
                 if (warp) hipLaunchKernelGGL((KERNEL<4, WIDE_, true, BT>), dim3(blocks), dim3(kBlock), 0, st, a);      \
                 else hipLaunchKernelGGL((KERNEL<4, WIDE_, false, BT>), dim3(blocks), dim3(kBlock), 0, st, a);          \
             } while (0)
+#define SGCN_CSG2D(WIDE_)      /* a dictionary plan: the entries' values from the tile's table in LDS */                \
+            do {                                                                                                        \
+                CsDictArgs da{};                                                                                        \
+                static_cast<CsArgs&>(da) = a;                                                                           \
+                da.tile_vals = plan->dev_tile_vals; da.tile_nvals = plan->dev_tile_nvals; da.dict_bits = plan->dict_bits; \
+                if (warp) hipLaunchKernelGGL((cs_spmm16g2k_kernel<4, WIDE_, true, BT, true>), dim3(blocks), dim3(kBlock), 0, st, da); \
+                else hipLaunchKernelGGL((cs_spmm16g2k_kernel<4, WIDE_, false, BT, true>), dim3(blocks), dim3(kBlock), 0, st, da);     \
+            } while (0)
             if (plan->G == 4) {
                 const bool wide = K >= (1 << 24) || ldb * kEsz >= (1 << 24) || (int64_t)K * ldb * kEsz >= (1ll << 32) ||
                                   tune_get("cs_g2_wide") > 0;
@@ -1015,13 +1109,15 @@ static int spmm_cs(const sgcn_csplan_t* plan, int32_t M, int32_t K, int32_t d,
             } else if (plan->G == 2) {
                 const bool wide = K >= (1 << 24) || ldb * kEsz >= (1 << 24) || (int64_t)K * ldb * kEsz >= (1ll << 32) ||
                                   tune_get("cs_g2_wide") > 0;
-                if (wide) SGCN_CSG(cs_spmm16g2k_kernel, true); else SGCN_CSG(cs_spmm16g2k_kernel, false);
+                if (plan->dict_bits != 0) { if (wide) SGCN_CSG2D(true); else SGCN_CSG2D(false); }
+                else if (wide) SGCN_CSG(cs_spmm16g2k_kernel, true); else SGCN_CSG(cs_spmm16g2k_kernel, false);
             } else {
                 if (extra) { if (U == 8) SGCN_CS16(8, true); else SGCN_CS16(4, true); }
                 else { if (U == 4) SGCN_CS16(4, false); else SGCN_CS16(8, false); }
             }
 #undef SGCN_CS16
 #undef SGCN_CSG
+#undef SGCN_CSG2D
         }
     }
     SGCN_HIP_TRY(hipGetLastError());

@@ -375,7 +375,9 @@ class StaticMatrix(object):
                 if self._plan is not None:
                     return 'lds'
         G = ops.ColumnSweepCSR.choose_g(d, self.nnz / max(self.shape[0], 1), self.shape[0])
-        self._plan, self.plan_from_cache = ops.ColumnSweepCSR.cached(a, self.device, self.cache_path, G=G)
+        # (under an edge mask the plan's value array is re-drawn every step: it must have one)
+        values = {} if self.edge is None else {"dictionary": False}
+        self._plan, self.plan_from_cache = ops.ColumnSweepCSR.cached(a, self.device, self.cache_path, G=G, **values)
         return 'cs'
 
     @property

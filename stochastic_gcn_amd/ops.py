@@ -1231,7 +1231,7 @@ class ColumnSweepCSR(object):
         return np.ascontiguousarray(table[:nb.value]), int(shift.value)
 
     def __init__(self, a, device, R=16, T=0, round_tiles=0, col_labels=None, row_labels=None, G=1, align='auto', warp='auto',
-                 col_ranges=0):
+                 col_ranges=0, dictionary=True):
         """G = 2: two 16-row lane groups per wavefront on 128-column passes (sgcn_csplang_*), half the passes of
         the dense operand through every XCD per register byte; ``align``: columns one bin of a wave may run ahead
         of the slowest (the plan pads the bins that are ahead; 'auto': a third of the L2 window, ``auto_align``; with a
@@ -1239,7 +1239,10 @@ class ColumnSweepCSR(object):
         bench and the training path call it: S-Reddit d = 602 3.51 vs 3.67 ms sustained, S-RMAT d = 256 2.61 vs
         2.82 ms.  G = 4 (four groups, 64-column passes, every row of a 233 k-row graph resident in one round): instruction-
         bound on a full graph (3.75 ms on S-Reddit; its gathers alone 3.21: DESIGN.md 3.2), but the better sweep for a SPARSE
-        matrix such as the LDS sweep's residual, which is what uses it."""
+        matrix such as the LDS sweep's residual, which is what uses it.
+        ``dictionary``: let the library keep the entries' values in per-tile tables where every tile has few distinct ones
+        (sgcn_csbuild_dict, sgcn_tune "cs_dict": the library decides, per plan); False for a plan whose value array is
+        re-drawn every step (``live_val``; a dictionary plan takes one too, on a second copy of its words)."""
         a = a.tocsr()
         G, labelled = int(G), col_labels is not None or row_labels is not None
         if R != 16:
@@ -1253,7 +1256,7 @@ class ColumnSweepCSR(object):
         elif G != 1:
             if labelled:
                 raise ValueError("G = 2 plans are ungrouped and use 16-row bins")
-            p = self._plan_groups(a, G, T, round_tiles, align, warp)
+            p = self._plan_groups(a, G, T, round_tiles, align, warp, dictionary)
         else:
             p = self._plan_one(a, T, round_tiles, col_labels, row_labels, warp)
         self._finish(p, device, round_tiles)
@@ -1261,8 +1264,9 @@ class ColumnSweepCSR(object):
     # What a builder (_plan_one / _plan_groups / _plan_ranged) or the cache file (_load) hands to _finish: the host arrays
     # ``tile_ptr, colrow, val, tile_rows, tile_slots, fix``, ``nslots``, ``shape``, ``nnz`` and the entries below, which
     # default to what a plan without them has.  ``host_plan_s``: what the builder spent in the plan builder proper.
+    # A dictionary plan (``dict_bits`` > 0) has ``val`` None and the tables ``tile_vals`` [ntiles << dict_bits] / ``tile_nvals``.
     _RECORD = dict(R=16, G=1, T=None, align=None, pad_fraction=0.0, ranged=0, range_cuts=None, grouped=False, pos2col=None,
-                   warp=None, warp_shift=0, host_plan_s=None)
+                   warp=None, warp_shift=0, host_plan_s=None, dict_bits=0, tile_vals=None, tile_nvals=None)
 
     @staticmethod
     def _record(built, **entries):
@@ -1286,7 +1290,10 @@ class ColumnSweepCSR(object):
         self._hint, self._hint_round = None, None
         self._clocks = clocks or (SweepClock(), SweepClock())                     # (fp32 operand, bfloat16 operand)
         self._tuning, self._cache = False, None                                    # (_cache: where ``cached`` wants it stored)
-        self.tile_ptr, self.colrow, self.val = to(p["tile_ptr"]), to(p["colrow"]), to(p["val"])
+        self.tile_ptr, self.colrow, self._val = to(p["tile_ptr"]), to(p["colrow"]), to(p["val"])
+        # a dictionary plan: no value array (``val`` decodes one on demand), the tiles' tables instead
+        self.dict_bits, self.tile_vals, self.tile_nvals = int(p["dict_bits"]), to(p["tile_vals"]), to(p["tile_nvals"])
+        self._colrow_plain = None  # (the words without their indices, made when a ``live_val`` is first handed to such a plan)
         self.live_val = None       # a re-drawn value array the products read instead of ``val`` (full_batch.StaticMatrix,
                                    # inside a training step under --edge_dropout); ``val``, the base values, is what is saved
         self.tile_rows, self.tile_slots = to(p["tile_rows"]), to(p["tile_slots"])
@@ -1298,6 +1305,24 @@ class ColumnSweepCSR(object):
         # what the plan cost to set up (the product it serves may run once: gcn/utils.py:321-322); None on a loaded plan
         self.setup_s = None if p["host_plan_s"] is None else {
             "host_plan_s": p["host_plan_s"], "upload_s": time.perf_counter() - t_up, "host_threads": int(lib.sgcn_host_threads())}
+
+    @property
+    def val(self):
+        """The value of every entry.  A dictionary plan keeps none: it is decoded from the tiles' tables, for the callers
+        that inspect a plan (the products never ask)."""
+        if self.dict_bits == 0:
+            return self._val
+        tile = torch.repeat_interleave(torch.arange(self.ntiles, device=self.tile_ptr.device), self.tile_ptr[1:] - self.tile_ptr[:-1])
+        idx = (self.colrow.long() >> (28 - self.dict_bits)) & ((1 << self.dict_bits) - 1)
+        return self.tile_vals[(tile << self.dict_bits) + idx]
+
+    def columns_rows(self):
+        """``colrow`` on the host as a plan with a value array has it: col | local row << 28 (a dictionary plan's index bits
+        cleared)."""
+        cr = self.colrow.cpu().numpy()
+        if self.dict_bits:
+            cr = (cr.view(np.uint32) & np.uint32(((1 << (28 - self.dict_bits)) - 1) | 0xF0000000)).view(np.int32)
+        return cr
 
     @staticmethod
     def _plan_one(a, T, round_tiles, col_labels, row_labels, warp):
@@ -1468,8 +1493,8 @@ class ColumnSweepCSR(object):
                                       nslots=int(total[split].sum()), warp=table, warp_shift=shift, host_plan_s=t_build)
 
     @staticmethod
-    def _plan_groups(a, G, T, round_tiles, align, warp):
-        """G = 2 / 4 lane groups per wavefront (sgcn_csplang_*)"""
+    def _plan_groups(a, G, T, round_tiles, align, warp, dictionary=False):
+        """G = 2 / 4 lane groups per wavefront (sgcn_csplang_*); ``dictionary``: offered to sgcn_csbuild_dict, which decides"""
         rowptr = np.ascontiguousarray(a.indptr, dtype=np.int32)
         col = np.ascontiguousarray(a.indices, dtype=np.int32)
         val = np.ascontiguousarray(a.data, dtype=np.float32)
@@ -1482,34 +1507,47 @@ class ColumnSweepCSR(object):
         if align is None or align == 'auto':
             align = ColumnSweepCSR.auto_align(K, col.shape[0], M, G, rnd)
         t_build = time.perf_counter()
-        built = ColumnSweepCSR._build(rowptr, col, val, M, G, 16, T, rnd, int(align), None,
-                                      wtab.ctypes.data if wtab is not None else None, shift)
+        built, (bits, tile_vals, tile_nvals) = ColumnSweepCSR._build(rowptr, col, val, M, G, 16, T, rnd, int(align), None,
+                                                                     wtab.ctypes.data if wtab is not None else None, shift,
+                                                                     K=K if dictionary else -1)
         t_build = time.perf_counter() - t_build
         return ColumnSweepCSR._record(built, shape=(int(a.shape[0]), K), nnz=int(col.shape[0]), G=G, T=int(T), align=int(align),
                                       pad_fraction=1.0 - col.shape[0] / max(int(built[1].shape[0]), 1), warp=wtab,
-                                      warp_shift=shift, host_plan_s=t_build)
+                                      warp_shift=shift, host_plan_s=t_build, dict_bits=bits, tile_vals=tile_vals,
+                                      tile_nvals=tile_nvals)
 
     @staticmethod
-    def _build(rowptr, col, val, M, G, R, T, rnd, align, rgp, wp, warp_shift, threads=0):
-        """sgcn_csplan_build + export: the plan's host arrays, built in one pass on every core the process may use."""
+    def _build(rowptr, col, val, M, G, R, T, rnd, align, rgp, wp, warp_shift, threads=0, K=None):
+        """sgcn_csplan_build + export: the plan's host arrays, built in one pass on every core the process may use.
+        ``K`` given: the plan is offered to sgcn_csbuild_dict (K < 0: not offered) and the result is the pair
+        (arrays, (dict_bits, tile_vals, tile_nvals)) -- a dictionary plan's value array is None."""
         h = C.c_void_p()
         check(lib.sgcn_csplan_build(rowptr.ctypes.data, col.ctypes.data, val.ctypes.data, M, G, R, int(T), int(rnd), int(align),
                                     rgp, wp, int(warp_shift), int(threads), C.byref(h)))
         try:
             nt, ne, nfix, nslots = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
             check(lib.sgcn_csbuild_sizes(h, C.byref(nt), C.byref(ne), C.byref(nfix), C.byref(nslots), None, None))
+            bits = C.c_int32(0)
+            if K is not None and K >= 0:
+                check(lib.sgcn_csbuild_dict(h, int(K), C.byref(bits)))
             tile_ptr = np.empty(nt.value + 1, dtype=np.int64)
             colrow = np.empty(ne.value, dtype=np.int32)
-            valout = np.empty(ne.value, dtype=np.float32)
+            valout = np.empty(ne.value, dtype=np.float32) if bits.value == 0 else None
             tile_rows = np.empty(nt.value * R * G, dtype=np.int32)
             tile_slots = np.empty(nt.value * R * G, dtype=np.int32)
             fix = np.empty((nfix.value, 3), dtype=np.int32)
-            check(lib.sgcn_csbuild_export(h, tile_ptr.ctypes.data, colrow.ctypes.data, valout.ctypes.data,
+            check(lib.sgcn_csbuild_export(h, tile_ptr.ctypes.data, colrow.ctypes.data, valout.ctypes.data if valout is not None else None,
                                           tile_rows.ctypes.data, tile_slots.ctypes.data,
                                           fix.ctypes.data if nfix.value else None))
+            tile_vals = tile_nvals = None
+            if bits.value:
+                tile_vals = np.empty(nt.value << bits.value, dtype=np.float32)
+                tile_nvals = np.empty(nt.value, dtype=np.int32)
+                check(lib.sgcn_csbuild_export_dict(h, tile_vals.ctypes.data, tile_nvals.ctypes.data))
         finally:
             lib.sgcn_csbuild_free(h)
-        return tile_ptr, colrow, valout, tile_rows, tile_slots, fix, nt.value, nfix.value, nslots.value
+        built = tile_ptr, colrow, valout, tile_rows, tile_slots, fix, nt.value, nfix.value, nslots.value
+        return built if K is None else (built, (bits.value, tile_vals, tile_nvals))
 
     # ---- on-disk plan cache (beside the dataset's .npz, SURVEY.md 8f f-3) -------------------------
     @staticmethod
@@ -1554,10 +1592,13 @@ class ColumnSweepCSR(object):
         t = lambda x: x.cpu().numpy()          # noqa: E731
         blob = dict(key=np.array(key), G=self.G, pad_fraction=float(self.pad_fraction),
                     R=self.R, shape=np.array(self.shape, np.int64), nslots=self.nslots,
-                    round_tiles=self.round_tiles, tile_ptr=t(self.tile_ptr), colrow=t(self.colrow), val=t(self.val),
+                    round_tiles=self.round_tiles, tile_ptr=t(self.tile_ptr), colrow=t(self.colrow),
+                    val=t(self._val) if self.dict_bits == 0 else np.zeros(0, np.float32),
                     tile_rows=t(self.tile_rows), tile_slots=t(self.tile_slots),
                     fix=t(self.fix) if self.fix is not None else np.zeros((0, 3), np.int32),
                     warp=t(self.warp) if self.warp is not None else np.zeros(0, np.int32), warp_shift=self.warp_shift)
+        if self.dict_bits:       # (a plan with a value array writes the file it always wrote)
+            blob.update(dict_bits=self.dict_bits, tile_vals=t(self.tile_vals), tile_nvals=t(self.tile_nvals))
         # each operand type's clocks under keys of their own: a build without the bfloat16 operand reads the rest unchanged
         for clock, (pace_key, tuned_key) in zip(self._clocks, self.CLOCK_KEYS):
             blob[pace_key], blob[tuned_key] = clock.to_npz()
@@ -1603,23 +1644,27 @@ class ColumnSweepCSR(object):
                  pad_fraction=float(z["pad_fraction"]) if "pad_fraction" in z.files else 0.0, nslots=int(z["nslots"]),
                  warp=warp, warp_shift=int(z["warp_shift"]) if warp is not None else 0,
                  **{k: z[k] for k in ("tile_ptr", "colrow", "val", "tile_rows", "tile_slots", "fix")})
+        if "dict_bits" in z.files and int(z["dict_bits"]):
+            p.update(val=None, dict_bits=int(z["dict_bits"]), tile_vals=z["tile_vals"], tile_nvals=z["tile_nvals"])
         self = cls.__new__(cls)
         self._finish(p, device, int(z["round_tiles"]), tuple(SweepClock.from_npz(z, *keys) for keys in cls.CLOCK_KEYS))
         return self
 
     @classmethod
-    def cached(cls, a, device, path=None, G=1):
+    def cached(cls, a, device, path=None, G=1, dictionary=True):
         """Plan of ``a`` (with G lane groups per wavefront): loaded from ``path`` when that file holds such a
         plan of this very matrix, otherwise built (and written to ``path``).  Returns (plan, came_from_cache)."""
         if path is None:
-            return cls(a, device, G=G), False
+            return cls(a, device, G=G, dictionary=dictionary), False
         # the identity of the matrix AND of the build parameters the plan depends on (tiles per launch round)
         # (cached() builds with the default T / align; d: how the rows were dealt to the bins, sgcn_tune "cs_deal")
         key = "%s:r%d:Tauto:aauto:w1:d%d" % (cls.matrix_key(a), _cs_round(), _ffi.lib.sgcn_tune_get(b"cs_deal"))
+        if dictionary and _ffi.lib.sgcn_tune_get(b"cs_dict") > 0:     # (v: the plan was offered to sgcn_csbuild_dict)
+            key += ":v1"
         hit = cls.load(path, device, key, g=G)
         if hit is not None:
             return hit, True
-        plan = cls(a, device, G=G)
+        plan = cls(a, device, G=G, dictionary=dictionary)
         plan._cache = (path, key)
         return plan, False
 
@@ -1641,13 +1686,21 @@ class ColumnSweepCSR(object):
             pad[:self.ntiles] = self._tile_nnz
             self._hint = np.ascontiguousarray(pad.reshape(nl, rnd).max(axis=1))
             self._hint_round = rnd
-        return _ffi.CsPlan(self.R, self.ntiles, self.tile_ptr.data_ptr(), self.colrow.data_ptr(),
-                           (self.val if self.live_val is None else self.live_val).data_ptr(), self.tile_rows.data_ptr(),
+        colrow, tables = self.colrow, (self.tile_vals, self.tile_nvals, self.dict_bits)
+        if self.dict_bits and self.live_val is not None:
+            # a value array handed to a dictionary plan: the product reads it, on the words without their table indices
+            # (made once; a plan that is to be re-valued every step is better built with dictionary=False)
+            if self._colrow_plain is None:
+                self._colrow_plain = torch.from_numpy(np.ascontiguousarray(self.columns_rows())).to(self.device)
+            colrow, tables = self._colrow_plain, (None, None, 0)
+        return _ffi.CsPlan(self.R, self.ntiles, self.tile_ptr.data_ptr(), colrow.data_ptr(),
+                           _ptr(self._val if self.live_val is None else self.live_val), self.tile_rows.data_ptr(),
                            self.tile_slots.data_ptr(),
                            _ptr(self.fix), self.nfix, self.nslots, _ptr(self.ws),
                            0 if self.ws is None else self.ws.numel(), rnd, self._hint.ctypes.data,
                            -1 if self.grouped else int(self.clock(bf16).pace.get(d, 0)), self.G,
-                           1 if (self.grouped or self.ranged) else 0, _ptr(self.warp), self.warp_shift)
+                           1 if (self.grouped or self.ranged) else 0, _ptr(self.warp), self.warp_shift,
+                           _ptr(tables[0]), _ptr(tables[1]), tables[2])
 
     def variant(self, d, bf16=False):
         """The kernel variant / launch geometry sgcn_spmm_cs_f32 (``bf16``: sgcn_spmm_cs_b16) uses for this plan and width."""
@@ -2265,7 +2318,7 @@ def plan_entries(plan):
     if isinstance(plan, ColumnSweepCSR):
         if plan.grouped or plan.ranged or plan.pos2col is not None or plan.R != 16:
             raise ValueError("edge dropout decodes unlabelled column-sweep plans without column ranges only")
-        return cs_entries(plan.tile_ptr.cpu().numpy(), plan.colrow.cpu().numpy(), plan.val.cpu().numpy(),
+        return cs_entries(plan.tile_ptr.cpu().numpy(), plan.columns_rows(), plan.val.cpu().numpy(),
                           plan.tile_rows.cpu().numpy(), plan.G)
     raise ValueError("edge dropout has no decode for a %s (the LDS sweep's unit plans carry no value array)" % type(plan).__name__)
 
