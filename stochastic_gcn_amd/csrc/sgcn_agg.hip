@@ -13,15 +13,14 @@
 //
 // The three sums are kept in separate fp32 accumulators and combined in the reference's
 // order.  P rows are full neighbour lists (power-law): they follow the same host plan /
-// workspace-slot / ordered fix-up scheme as sgcn_spmm.hip.  One G-lane group per row, one
+// workspace-slot / ordered fix-up scheme as sgcn_spmm.hip (the checks on the plan, the slot pitch, group_lanes and the
+// vector-width ladder come from sgcn_seg.h; the launch macro and its grid are this file's own).  One G-lane group per row, one
 // 16-byte vector per lane (G = 32 for d = 128, 8 for d = 32), feature slabs of G vectors
 // for wider rows.
 #include "sgcn_dev.h"
-#include <type_traits>
+#include "sgcn_seg.h"
 
 namespace sgcn {
-
-int group_lanes(int nvec);  // sgcn_spmm.hip
 
 // HT: the history's element -- float, or uint16_t for a bfloat16 table (sgcn_vr_aggregate_*_h16); everything else is fp32
 template <class HT>
@@ -140,7 +139,7 @@ __device__ __forceinline__ void agg_finish(const AggArgsT<HT>& a, int row, int v
 // P row in the same order even when the fused pass runs narrower vectors (more lanes per group, fewer groups): its
 // groups then take several chunks each.
 static int p_chunks(int32_t d, const void* Hbar, int64_t ldh, const float* ws) {
-    const int vw = pick_vw(d, {Hbar, ws}, {ldh, ((int64_t)d + 3) / 4 * 4});
+    const int vw = pick_vw(d, {Hbar, ws}, {ldh, seg_slot_pitch(d)});
     return kBlock / group_lanes((d + vw - 1) / vw) - 1;
 }
 
@@ -361,13 +360,9 @@ static int vr_aggregate(const char* who, const int32_t* a_rowptr, const int32_t*
     a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
     a.nseg = n1;
     if (f_plan) {
-        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "%s: malformed plan", who);
-        a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg;
-        a.ws = f_plan->dev_ws; a.ldw = ((int64_t)d + 3) / 4 * 4;
-        if (f_plan->nfix > 0) {
-            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "%s: plan needs dev_fix/dev_ws", who);
-            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "%s: workspace too small", who);
-        }
+        a.ldw = seg_slot_pitch(d);
+        if (const int rc = seg_plan_ok(who, f_plan, n1, a.ldw)) return rc;
+        a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg; a.ws = f_plan->dev_ws;
     }
     // the output offset `off` = d must keep vector alignment too
     int vw = pick_vw(d, {h, mu, vw_table(Hbar), out_h, out_mu, f_plan ? f_plan->dev_ws : nullptr}, {ldx, ldh, ldo});
@@ -377,9 +372,7 @@ static int vr_aggregate(const char* who, const int32_t* a_rowptr, const int32_t*
     a.pchunks = p_chunks(d, vw_table(Hbar), ldh, f_plan ? f_plan->dev_ws : nullptr);
     a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     hipStream_t st = (hipStream_t)stream;
-    if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
-    if (vw == 2) return launch_agg<2>(G, a, f_plan, st);
-    return launch_agg<1>(G, a, f_plan, st);
+    return with_vw(vw, [&](auto VW) { return launch_agg<decltype(VW)::value>(G, a, f_plan, st); });
 }
 
 // ---- the same aggregate in two phases -------------------------------------------------------------
@@ -404,16 +397,12 @@ static int vr_aggregate_pre(const char* who, const int32_t* f_rowptr, const int3
     AggArgsT<HT> a{};
     a.f_rowptr = f_rowptr; a.f_col = f_col; a.f_val = f_val;
     a.H = Hbar; a.ldh = ldh; a.ffield = ffield; a.d = d;
-    a.ldw = ((int64_t)d + 3) / 4 * 4;
+    a.ldw = seg_slot_pitch(d);
     a.accP_out = accP;
     a.nseg = n1;
     if (f_plan) {
-        SGCN_REQUIRE(f_plan->dev_seg && f_plan->nseg >= n1, "%s: malformed plan", who);
+        if (const int rc = seg_plan_ok(who, f_plan, n1, a.ldw)) return rc;
         a.seg = f_plan->dev_seg; a.nseg = f_plan->nseg; a.ws = f_plan->dev_ws;
-        if (f_plan->nfix > 0) {
-            SGCN_REQUIRE(f_plan->dev_fix && f_plan->dev_ws, "%s: plan needs dev_fix/dev_ws", who);
-            SGCN_REQUIRE(f_plan->ws_elems >= f_plan->nslots * a.ldw, "%s: workspace too small", who);
-        }
     }
     const int vw = pick_vw(d, {vw_table(Hbar), accP, f_plan ? f_plan->dev_ws : nullptr}, {ldh, a.ldw});
     a.nvec = (d + vw - 1) / vw;
@@ -421,9 +410,7 @@ static int vr_aggregate_pre(const char* who, const int32_t* f_rowptr, const int3
     a.pchunks = p_chunks(d, vw_table(Hbar), ldh, f_plan ? f_plan->dev_ws : nullptr);
     a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
     hipStream_t st = (hipStream_t)stream;
-    if (vw == 4) return launch_agg<4>(G, a, f_plan, st);
-    if (vw == 2) return launch_agg<2>(G, a, f_plan, st);
-    return launch_agg<1>(G, a, f_plan, st);
+    return with_vw(vw, [&](auto VW) { return launch_agg<decltype(VW)::value>(G, a, f_plan, st); });
 }
 
 template <class HT>
@@ -445,16 +432,14 @@ static int vr_aggregate_post(const char* who, const int32_t* a_rowptr, const int
     a.h = h; a.mu = mu; a.ldx = ldx; a.H = Hbar; a.ldh = ldh; a.ifield = ifield; a.s = s;
     a.out_h = out_h; a.out_mu = out_mu; a.ldo = ldo;
     a.d = d; a.cvd = cvd; a.concat = concat_self; a.off = concat_self ? d : 0;
-    a.ldw = ((int64_t)d + 3) / 4 * 4;
+    a.ldw = seg_slot_pitch(d);
     a.accP_in = accP;
     int vw = pick_vw(d, {h, mu, vw_table(Hbar), out_h, out_mu, accP}, {ldx, ldh, ldo, a.ldw});
     if (concat_self) while (vw > 1 && d % vw != 0) vw >>= 1;
     a.nvec = (d + vw - 1) / vw;
     const int G = group_lanes(a.nvec);
     hipStream_t st = (hipStream_t)stream;
-    if (vw == 4) return launch_agg_post<4>(G, a, n1, st);
-    if (vw == 2) return launch_agg_post<2>(G, a, n1, st);
-    return launch_agg_post<1>(G, a, n1, st);
+    return with_vw(vw, [&](auto VW) { return launch_agg_post<decltype(VW)::value>(G, a, n1, st); });
 }
 
 extern "C" int sgcn_vr_aggregate_f32(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,

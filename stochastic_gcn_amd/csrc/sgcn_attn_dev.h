@@ -1,16 +1,15 @@
 // What the attention kernels over a CSR pattern share (sgcn_spattn.hip: dot-product scores; sgcn_spgat.hip: learned additive
 // scores).  Device: the kernel arguments, the coefficient mask, a lane's share of a row, the reductions over a group or a
 // head, the forward slots' ordered fix-up, the backward's epilogue.  Host: the slot widths, the checks every export opens
-// with, and the one path from checked arguments to a launch -- geometry, dispatch ladder, fix-up -- which each translation
-// unit instantiates with a launcher for its own kernels.
+// with, and the one path from checked arguments to a launch -- the multi-head geometry, the choice of (DR, MH), the fix-up --
+// which each translation unit instantiates with a launcher for its own kernels.  The checks on a plan, the one-head geometry and
+// the ladders over (VW, G, NV) are those of every row-segment launch (sgcn_seg.h).
 #pragma once
 #include <cmath>
 #include "sgcn_dev.h"
+#include "sgcn_seg.h"
 
 namespace sgcn {
-
-int group_lanes(int nvec);   // sgcn_spmm.hip: lanes per row group for `nvec` vectors
-
 namespace {
 
 constexpr int kMaxVec = 256;   // vectors per row: 64 lanes x NV <= 4
@@ -318,24 +317,13 @@ AttnDrop drop_of(float keep, uint32_t key) {
     return dm;
 }
 
-int plan_ok(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw) {
-    SGCN_REQUIRE(plan->dev_seg && plan->nseg >= nrows, "%s: malformed plan", who);
-    if (plan->nfix > 0) {
-        SGCN_REQUIRE(plan->dev_fix && plan->dev_ws, "%s: plan with split rows needs dev_fix/dev_ws", who);
-        SGCN_REQUIRE(plan->ws_elems >= plan->nslots * ldw, "%s: workspace too small (%lld < %lld floats)", who,
-                     (long long)plan->ws_elems, (long long)(plan->nslots * ldw));
-    }
-    return SGCN_OK;
-}
-
 // ---- the slots of a split row (ops.attn_slot mirrors these four) -----------------------------------------------------------
 constexpr int kScalarSlot = 8;   // floats a GAT backward slot keeps for the per-head scalar sums (H <= 8)
-inline int64_t ceil4(int64_t d) { return (d + 3) / 4 * 4; }
 // forward, both score kinds: the accumulator on a 16-byte pitch, then one vector (m, l, -, -) per head
-inline int64_t fwd_slot(int32_t d, int32_t heads) { return ceil4(d) + 4 * (int64_t)heads; }
-inline int64_t bwd_slot(int32_t d) { return ceil4(d); }                         // dot-product bwd_q / bwd_kv: the row
-constexpr int64_t kGatBwdUSlot = kScalarSlot;                                   // GAT bwd_u: the heads' dU alone
-inline int64_t gat_bwd_v_slot(int32_t d) { return ceil4(d) + kScalarSlot; }     // GAT bwd_v: the row, then the heads' dV
+inline int64_t fwd_slot(int32_t d, int32_t heads) { return seg_slot_pitch(d) + 4 * (int64_t)heads; }
+inline int64_t bwd_slot(int32_t d) { return seg_slot_pitch(d); }                          // dot-product bwd_q / bwd_kv: the row
+constexpr int64_t kGatBwdUSlot = kScalarSlot;                                             // GAT bwd_u: the heads' dU alone
+inline int64_t gat_bwd_v_slot(int32_t d) { return seg_slot_pitch(d) + kScalarSlot; }      // GAT bwd_v: the row, then the heads' dV
 
 // ---- what the six host bodies open with ------------------------------------------------------------------------------------
 // first: the sizes, the width, the heads and the mask's keep
@@ -354,15 +342,15 @@ inline const void* split_ws(const sgcn_plan_t* plan) { return plan && plan->nfix
 inline int attn_plan_width(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw, int32_t d, int32_t heads,
                            std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds, int& vw) {
     if (plan)
-        if (const int rc = plan_ok(who, plan, nrows, ldw)) return rc;
+        if (const int rc = seg_plan_ok(who, plan, nrows, ldw)) return rc;
     vw = head_vw(pick_vw(d, ptrs, lds), d, heads);
     return width_ok(who, d, vw, heads);
 }
 
 // ---- one launch ------------------------------------------------------------------------------------------------------------
 // The lane geometry of a launch: G lanes per row segment and NV vectors per lane from d, vw and heads; fills what the kernels
-// read of it (nvec, ragged, heads, gh, nvh).  One head: the row kernels' group for nvec vectors (group_lanes), past 64 lanes
-// NV = ceil(nvec / 64).  Several: the smallest group whose sub-groups of G / heads lanes hold a head's nvh vectors one per
+// read of it (nvec, ragged, heads, gh, nvh).  One head: the row kernels' geometry (seg_geometry), which for nvec <= 256 is one
+// slab, past 64 lanes with NV = ceil(nvec / 64).  Several: the smallest group whose sub-groups of G / heads lanes hold a head's nvh vectors one per
 // lane, at least 8 lanes; past 64 lanes the sub-group is 64 / heads and a lane takes NV = ceil(nvh / Gh) <= 4 of them
 // (heads * nvh <= 256, width_ok).
 inline void attn_geometry(AttnArgs& a, int vw, int32_t heads, int& G, int& NV) {
@@ -370,8 +358,8 @@ inline void attn_geometry(AttnArgs& a, int vw, int32_t heads, int& G, int& NV) {
     a.ragged = a.d % vw != 0;
     a.heads = heads;
     if (heads == 1) {
-        G = group_lanes(a.nvec);
-        NV = G == 64 ? (a.nvec + 63) / 64 : 1;
+        const SegGeom g = seg_geometry(a.nvec, a.nseg);
+        G = g.G; NV = g.NV;
         a.gh = G; a.nvh = a.nvec;
     } else {
         a.nvh = a.d / heads / vw;
@@ -383,34 +371,12 @@ inline void attn_geometry(AttnArgs& a, int vw, int32_t heads, int& G, int& NV) {
     }
 }
 
-// The ladder over (DR, MH, VW, G, NV).  L is a translation unit's launcher for one kind of launch:
+// The choice of (DR, MH) is attention's; (VW, G, NV) walk the ladders of sgcn_seg.h.  L is a translation unit's launcher for one
+// kind of launch:
 //   template <int G, int NV, int VW, bool MH, bool DR> static void launch(dim3 grid, hipStream_t, const KA&... the kernel's arguments)
 //   static void fix(int vw, const AttnArgs&, const sgcn_plan_t*, hipStream_t, const X&... what it has beside them)
 //   static constexpr int64_t max_fix: the split rows its fix-up's grid can count
-template <class L, int VW, bool MH, bool DR, class... KA>
-bool dispatch_gnv(int G, int NV, dim3 grid, hipStream_t st, const KA&... ka) {
-    switch (G) {
-        case 8: L::template launch<8, 1, VW, MH, DR>(grid, st, ka...); return true;
-        case 16: L::template launch<16, 1, VW, MH, DR>(grid, st, ka...); return true;
-        case 32: L::template launch<32, 1, VW, MH, DR>(grid, st, ka...); return true;
-        case 64:
-            switch (NV) {
-                case 1: L::template launch<64, 1, VW, MH, DR>(grid, st, ka...); return true;
-                case 2: L::template launch<64, 2, VW, MH, DR>(grid, st, ka...); return true;
-                case 3: L::template launch<64, 3, VW, MH, DR>(grid, st, ka...); return true;
-                case 4: L::template launch<64, 4, VW, MH, DR>(grid, st, ka...); return true;
-            }
-    }
-    return false;
-}
-
-template <class L, bool MH, bool DR, class... KA>
-bool dispatch_vw(int vw, int G, int NV, dim3 grid, hipStream_t st, const KA&... ka) {
-    if (vw == 4) return dispatch_gnv<L, 4, MH, DR>(G, NV, grid, st, ka...);
-    if (vw == 2) return dispatch_gnv<L, 2, MH, DR>(G, NV, grid, st, ka...);
-    return dispatch_gnv<L, 1, MH, DR>(G, NV, grid, st, ka...);
-}
-
+//
 // A launch from its checked arguments: the segments and the slots from the plan, the geometry, the kernel off the ladder (the
 // kernels take a, x..., dm), then L's fix-up where the plan has split rows.  dm.mk == 0 (drop_of: keep == 1) and heads == 1
 // select the DR = false and the MH = false kernels.
@@ -428,10 +394,16 @@ int attn_run(const char* who, AttnArgs& a, int32_t nrows, const sgcn_plan_t* pla
 
     const dim3 grid((unsigned)nblocks);
     const bool drop = dm.mk > 0.f;
-    const bool ok = drop ? (heads == 1 ? dispatch_vw<L, false, true>(vw, G, NV, grid, st, a, x..., dm)
-                                       : dispatch_vw<L, true, true>(vw, G, NV, grid, st, a, x..., dm))
-                         : (heads == 1 ? dispatch_vw<L, false, false>(vw, G, NV, grid, st, a, x..., dm)
-                                       : dispatch_vw<L, true, false>(vw, G, NV, grid, st, a, x..., dm));
+    auto ladder = [&](auto MH, auto DR) {
+        return with_vw(vw, [&](auto VW) {
+            return with_gnv(G, NV, [&](auto g, auto nv) {
+                L::template launch<decltype(g)::value, decltype(nv)::value, decltype(VW)::value, decltype(MH)::value,
+                                   decltype(DR)::value>(grid, st, a, x..., dm);
+            });
+        });
+    };
+    const bool ok = drop ? (heads == 1 ? ladder(std::false_type{}, std::true_type{}) : ladder(std::true_type{}, std::true_type{}))
+                         : (heads == 1 ? ladder(std::false_type{}, std::false_type{}) : ladder(std::true_type{}, std::false_type{}));
     SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
     SGCN_HIP_TRY(hipGetLastError());
 
@@ -447,9 +419,9 @@ int attn_run(const char* who, AttnArgs& a, int32_t nrows, const sgcn_plan_t* pla
 template <bool MH>
 void launch_fix(int vw, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
     const dim3 grid((unsigned)plan->nfix), block(kBlock);
-    if (vw == 4) hipLaunchKernelGGL((spattn_fix_kernel<4, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
-    else if (vw == 2) hipLaunchKernelGGL((spattn_fix_kernel<2, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
-    else hipLaunchKernelGGL((spattn_fix_kernel<1, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
+    with_vw(vw, [&](auto VW) {
+        hipLaunchKernelGGL((spattn_fix_kernel<decltype(VW)::value, MH>), grid, block, 0, st, a, plan->dev_fix, plan->nfix);
+    });
 }
 inline void launch_fwd_fix(int vw, const AttnArgs& a, const sgcn_plan_t* plan, hipStream_t st) {
     if (a.heads == 1) launch_fix<false>(vw, a, plan, st);

@@ -13,15 +13,7 @@
             return sgcn::fail(SGCN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__));   \
     } while (0)
 
-#define SGCN_REQUIRE(cond, ...)                                       \
-    do {                                                              \
-        if (!(cond)) return sgcn::fail(SGCN_ERR_INVALID, __VA_ARGS__); \
-    } while (0)
-
 namespace sgcn {
-
-constexpr int kWave = 64;      // gfx950 wavefront
-constexpr int kBlock = 256;    // 4 wavefronts per workgroup, one per SIMD
 
 template <int VW> struct Vec;
 template <> struct Vec<4> { typedef float type __attribute__((ext_vector_type(4))); };

@@ -4,7 +4,16 @@
 #include <cstdio>
 #include <cstdarg>
 
+// a refusal: SGCN_ERR_INVALID (include/sgcn.h) and the message behind sgcn_last_error()
+#define SGCN_REQUIRE(cond, ...)                                       \
+    do {                                                              \
+        if (!(cond)) return sgcn::fail(SGCN_ERR_INVALID, __VA_ARGS__); \
+    } while (0)
+
 namespace sgcn {
+
+constexpr int kWave = 64;      // gfx950 wavefront
+constexpr int kBlock = 256;    // 4 wavefronts per workgroup, one per SIMD
 
 // Thread-local error slot behind sgcn_last_error().
 char* error_slot();

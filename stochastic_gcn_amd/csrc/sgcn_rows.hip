@@ -10,10 +10,9 @@
 // wavefront's accesses to a row are contiguous; the feature matrix and the history stay
 // resident in HBM (288 GB) instead of being gathered on the host.
 #include "sgcn_dev.h"
+#include "sgcn_seg.h"
 
 namespace sgcn {
-
-int group_lanes(int nvec);  // sgcn_spmm.hip
 
 template <int VW, bool SCATTER>
 __global__ __launch_bounds__(kBlock) void rows_kernel(const float* __restrict__ in, int64_t ldi,
@@ -47,9 +46,9 @@ static int launch_rows(const float* in, int64_t ldi, const int32_t* r, int32_t n
     const int G = group_lanes(nvec);
     const int64_t blocks = ((int64_t)n + (kBlock / G) - 1) / (kBlock / G);
     dim3 grid((unsigned)blocks), block(kBlock);
-    if (vw == 4) hipLaunchKernelGGL((rows_kernel<4, SCATTER>), grid, block, 0, st, in, ldi, r, n, d, nvec, G, out, ldo);
-    else if (vw == 2) hipLaunchKernelGGL((rows_kernel<2, SCATTER>), grid, block, 0, st, in, ldi, r, n, d, nvec, G, out, ldo);
-    else hipLaunchKernelGGL((rows_kernel<1, SCATTER>), grid, block, 0, st, in, ldi, r, n, d, nvec, G, out, ldo);
+    with_vw(vw, [&](auto VW) {
+        hipLaunchKernelGGL((rows_kernel<decltype(VW)::value, SCATTER>), grid, block, 0, st, in, ldi, r, n, d, nvec, G, out, ldo);
+    });
     SGCN_HIP_TRY(hipGetLastError());
     return SGCN_OK;
 }
@@ -124,9 +123,9 @@ static int launch_rows_h16(uint16_t* H, int64_t ldh, const int32_t* r, int32_t n
     const int G = group_lanes(nvec);
     const int64_t blocks = ((int64_t)n + (kBlock / G) - 1) / (kBlock / G);
     dim3 grid((unsigned)blocks), block(kBlock);
-    if (vw == 4) hipLaunchKernelGGL((rows_h16_kernel<4, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
-    else if (vw == 2) hipLaunchKernelGGL((rows_h16_kernel<2, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
-    else hipLaunchKernelGGL((rows_h16_kernel<1, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
+    with_vw(vw, [&](auto VW) {
+        hipLaunchKernelGGL((rows_h16_kernel<decltype(VW)::value, SCATTER>), grid, block, 0, st, H, ldh, r, n, d, nvec, G, x, ldx);
+    });
     SGCN_HIP_TRY(hipGetLastError());
     return SGCN_OK;
 }

@@ -41,8 +41,9 @@
 //
 // This file holds the three pattern kernels, the backward's fix-up kernel, the launcher that names them (Dot) and the exports'
 // own operand checks.  The arguments, the mask, a lane's share of a row, the reductions, the forward's fix-up kernel and the
-// backward's epilogue live in sgcn_attn_dev.h, and so does the whole host path from checked arguments to a launch -- slot widths,
-// opening checks, lane geometry, dispatch ladder, fix-up step (attn_run) -- which sgcn_spgat.hip (learned additive scores) shares.
+// backward's epilogue live in sgcn_attn_dev.h, and so does the host path from checked arguments to a launch -- slot widths,
+// opening checks, multi-head geometry, the choice of (DR, MH), fix-up step (attn_run) -- which sgcn_spgat.hip (learned additive
+// scores) shares; the plan checks, the one-head geometry and the ladders over (VW, G, NV) under it are sgcn_seg.h's.
 #include <cmath>
 #include "sgcn_attn_dev.h"
 
@@ -377,9 +378,9 @@ struct Dot {
         else {
             const dim3 grid((unsigned)plan->nfix), block(kBlock);      // one workgroup per split row: nvec <= 256 = kBlock threads
             const float mul = KIND == BWD_Q ? a.scale : 1.f;
-            if (vw == 4) hipLaunchKernelGGL((spattn_bwd_fix_kernel<4>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
-            else if (vw == 2) hipLaunchKernelGGL((spattn_bwd_fix_kernel<2>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
-            else hipLaunchKernelGGL((spattn_bwd_fix_kernel<1>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
+            with_vw(vw, [&](auto VW) {
+                hipLaunchKernelGGL((spattn_bwd_fix_kernel<decltype(VW)::value>), grid, block, 0, st, a, plan->dev_fix, plan->nfix, mul);
+            });
         }
     }
 };

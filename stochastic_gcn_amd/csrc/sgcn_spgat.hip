@@ -15,8 +15,8 @@
 // backward launch carries one more per-lane scalar sum (dU, dV), which a split row keeps in its slot beside the row.
 // delta and t go through the SAME reduction tree in the same per-lane order, so where C[i] holds the bits of one B[j] (a
 // saturated softmax) t - delta is exactly 0 for it.  Nothing nnz-sized is written and there are no atomics.
-// The host side is sgcn_attn_dev.h's as well: slot widths, opening checks, lane geometry, dispatch ladder and fix-up step
-// (attn_run); this file adds the launcher that names its kernels (Gat), slope_ok and each export's own operand checks.
+// The host side is sgcn_attn_dev.h's as well: slot widths, opening checks, lane geometry and fix-up step (attn_run), over the
+// plan checks and the ladders of sgcn_seg.h; this file adds the launcher that names its kernels (Gat), slope_ok and each export's own operand checks.
 #include <cmath>
 #include "sgcn_attn_dev.h"
 
@@ -446,9 +446,9 @@ struct Gat {
             hipLaunchKernelGGL(spgat_bwd_u_fix_kernel, g1, dim3(kBlock), 0, st, a, x, plan->dev_fix, plan->nfix);
         } else {
             const dim3 grid((unsigned)plan->nfix), block(kBlock);      // one workgroup per split row: nvec <= 256 = kBlock threads
-            if (vw == 4) hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<4>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
-            else if (vw == 2) hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<2>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
-            else hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<1>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
+            with_vw(vw, [&](auto VW) {
+                hipLaunchKernelGGL((spgat_bwd_v_fix_kernel<decltype(VW)::value>), grid, block, 0, st, a, x, plan->dev_fix, plan->nfix);
+            });
         }
     }
 };

@@ -13,17 +13,17 @@
 // before the first compare / add, wide rows are cut into feature slabs, and power-law rows into segments by the host plan
 // of include/sgcn.h: a split row's segments write partial results to workspace slots and an ordered fix-up pass walks
 // them -- with the same strict `>` forward, so the first maximum of the WHOLE row survives wherever the cuts fall, and
-// by addition in slot order backward (the scheme of spmm_fix_kernel).
+// by addition in slot order backward (the scheme of spmm_fix_kernel).  The host side of a launch (`run`) takes the plan checks,
+// the geometry, the ladders and the fix-up's grid from sgcn_seg.h, as the row SpMM does; the forward's check of the id
+// workspace is this file's own.
 //
 // The tie rule is np.argmax's: the best starts as the first entry, a later entry replaces it only when v > best.  That
 // keeps the first of +0.0 / -0.0 and the first of equal values; +-inf are ordinary values; an empty row gives +0.0 and
 // arg = -1.  NaN-free input is the caller's promise (a NaN never wins a strict comparison and, once first, never loses).
 #include "sgcn_dev.h"
+#include "sgcn_seg.h"
 
 namespace sgcn {
-
-int group_lanes(int nvec);   // sgcn_spmm.hip: lanes per row group for `nvec` vectors
-
 namespace {
 
 template <int VW> struct IVec;
@@ -369,82 +369,39 @@ __global__ __launch_bounds__(kBlock) void spmax_bwd_fix_kernel(SpmaxArgs a, cons
     bwd_store<VW>(a, fx.row, vi, acc);
 }
 
-template <bool BWD, int G, int NV, int VW>
-void launch_seg(const SpmaxArgs& a, int64_t nblocks, hipStream_t st) {
-    if constexpr (BWD) hipLaunchKernelGGL((spmax_bwd_seg_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL((spmax_seg_kernel<G, NV, VW>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-}
-
-template <bool BWD, int VW>
-bool dispatch_gnv(int G, int NV, const SpmaxArgs& a, int64_t nblocks, hipStream_t st) {
-    switch (G) {
-        case 8: launch_seg<BWD, 8, 1, VW>(a, nblocks, st); return true;
-        case 16: launch_seg<BWD, 16, 1, VW>(a, nblocks, st); return true;
-        case 32: launch_seg<BWD, 32, 1, VW>(a, nblocks, st); return true;
-        case 64:
-            switch (NV) {
-                case 1: launch_seg<BWD, 64, 1, VW>(a, nblocks, st); return true;
-                case 2: launch_seg<BWD, 64, 2, VW>(a, nblocks, st); return true;
-                case 3: launch_seg<BWD, 64, 3, VW>(a, nblocks, st); return true;
-                case 4: launch_seg<BWD, 64, 4, VW>(a, nblocks, st); return true;
-            }
-    }
-    return false;
-}
-
-// Everything a launch needs that the row SpMM derives the same way: the plan's tables, the vector width, the lane
-// geometry, the grid.  `a` arrives with its operands set; nrows = rows of the pattern at hand.
+// A launch from its checked arguments: the plan's tables, the lane geometry and the ladder of sgcn_seg.h, then the ordered
+// fix-up where the plan has split rows.  `a` arrives with its operands set; nrows = rows of the pattern at hand.
 template <bool BWD>
 int run(SpmaxArgs& a, const char* who, int32_t nrows, const sgcn_plan_t* plan, int vw, hipStream_t st) {
     a.nseg = nrows;
     a.slabmajor = tune_get("spmm_slabmajor");
     if (plan) { a.seg = plan->dev_seg; a.nseg = plan->nseg; }
     a.nvec = (a.d + vw - 1) / vw;
-    const int G = group_lanes(a.nvec);
-    int NV = 1;
-    if (G == 64) {
-        const int per_wave = (a.nvec + 63) / 64;          // vectors per lane to cover the row
-        const int nslab0 = (per_wave + 3) / 4;            // slabs at the NV <= 4 cap
-        NV = (per_wave + nslab0 - 1) / nslab0;
-    }
-    const int nslab = (a.nvec + G * NV - 1) / (G * NV);
-    a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
-    const int64_t nblocks = a.nsegblk * nslab;
-    SGCN_REQUIRE(nblocks < (1ll << 31), "%s: grid too large", who);
+    const SegGeom g = seg_geometry(a.nvec, a.nseg);
+    a.nsegblk = g.nsegblk;
+    SGCN_REQUIRE(g.nblocks < (1ll << 31), "%s: grid too large", who);
 
-    bool ok = false;
-    if (vw == 4) ok = dispatch_gnv<BWD, 4>(G, NV, a, nblocks, st);
-    else if (vw == 2) ok = dispatch_gnv<BWD, 2>(G, NV, a, nblocks, st);
-    else ok = dispatch_gnv<BWD, 1>(G, NV, a, nblocks, st);
-    SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, G, NV);
+    const dim3 grid((unsigned)g.nblocks), block(kBlock);
+    const bool ok = with_vw(vw, [&](auto VW) {
+        return with_gnv(g.G, g.NV, [&](auto G, auto NV) {
+            constexpr int kG = decltype(G)::value, kNV = decltype(NV)::value, kVW = decltype(VW)::value;
+            if constexpr (BWD) hipLaunchKernelGGL((spmax_bwd_seg_kernel<kG, kNV, kVW>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((spmax_seg_kernel<kG, kNV, kVW>), grid, block, 0, st, a);
+        });
+    });
+    SGCN_REQUIRE(ok, "%s: no kernel for G=%d NV=%d", who, g.G, g.NV);
     SGCN_HIP_TRY(hipGetLastError());
 
     if (plan && plan->nfix > 0) {
-        const int64_t nfblk = (int64_t)((a.nvec + kBlock - 1) / kBlock) * plan->nfix;
+        const int64_t nfblk = seg_fix_blocks(a.nvec, plan->nfix);
         SGCN_REQUIRE(nfblk < (1ll << 31), "%s: too many split rows", who);
-        dim3 grid((unsigned)nfblk);
-        if constexpr (BWD) {
-            if (vw == 4) hipLaunchKernelGGL((spmax_bwd_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-            else if (vw == 2) hipLaunchKernelGGL((spmax_bwd_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-            else hipLaunchKernelGGL((spmax_bwd_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-        } else {
-            if (vw == 4) hipLaunchKernelGGL((spmax_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-            else if (vw == 2) hipLaunchKernelGGL((spmax_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-            else hipLaunchKernelGGL((spmax_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-        }
+        const dim3 fgrid((unsigned)nfblk);
+        with_vw(vw, [&](auto VW) {
+            constexpr int kVW = decltype(VW)::value;
+            if constexpr (BWD) hipLaunchKernelGGL((spmax_bwd_fix_kernel<kVW>), fgrid, block, 0, st, a, plan->dev_fix, plan->nfix);
+            else hipLaunchKernelGGL((spmax_fix_kernel<kVW>), fgrid, block, 0, st, a, plan->dev_fix, plan->nfix);
+        });
         SGCN_HIP_TRY(hipGetLastError());
-    }
-    return SGCN_OK;
-}
-
-// the checks on a plan that both directions share; forward: the id workspace too
-int plan_ok(const char* who, const sgcn_plan_t* plan, int32_t nrows, int64_t ldw, bool need_ids, const int32_t* ws_ids) {
-    SGCN_REQUIRE(plan->dev_seg && plan->nseg >= nrows, "%s: malformed plan", who);
-    if (plan->nfix > 0) {
-        SGCN_REQUIRE(plan->dev_fix && plan->dev_ws, "%s: plan with split rows needs dev_fix/dev_ws", who);
-        SGCN_REQUIRE(!need_ids || ws_ids, "%s: plan with split rows needs dev_ws_arg (the slots' ids)", who);
-        SGCN_REQUIRE(plan->ws_elems >= plan->nslots * ldw, "%s: workspace too small (%lld < %lld floats)", who,
-                     (long long)plan->ws_elems, (long long)(plan->nslots * ldw));
     }
     return SGCN_OK;
 }
@@ -461,8 +418,12 @@ extern "C" int sgcn_spmax_csr_f32(const int32_t* rowptr, const int32_t* col, int
     SGCN_REQUIRE(d > 0, "spmax: d must be positive (got %d)", d);
     SGCN_REQUIRE(rowptr && C && (B || K == 0), "spmax: null operand");
     SGCN_REQUIRE(ldb >= d && ldc >= d && (!arg || ldarg >= d), "spmax: leading dimension smaller than d");
-    const int64_t ldw = ((int64_t)d + 3) / 4 * 4;
-    if (plan) { const int rc = plan_ok("spmax", plan, M, ldw, true, dev_ws_arg); if (rc) return rc; }
+    const int64_t ldw = seg_slot_pitch(d);
+    if (plan) {
+        if (const int rc = seg_plan_tables("spmax", plan, M)) return rc;
+        SGCN_REQUIRE(plan->nfix <= 0 || dev_ws_arg, "spmax: plan with split rows needs dev_ws_arg (the slots' ids)");
+        if (const int rc = seg_plan_room("spmax", plan, ldw)) return rc;
+    }
     if (M == 0) return SGCN_OK;
 
     SpmaxArgs a{};
@@ -484,8 +445,9 @@ extern "C" int sgcn_spmax_csr_bwd_f32(const int32_t* t_rowptr, const int32_t* t_
     SGCN_REQUIRE(ldg >= d && ldarg >= d && lddb >= d, "spmax_bwd: leading dimension smaller than d");
     const bool with_add = add && add_rows > 0;
     if (with_add) SGCN_REQUIRE(ldadd >= d && add_rows <= K, "spmax_bwd: bad addend");
-    const int64_t ldw = ((int64_t)d + 3) / 4 * 4;
-    if (t_plan) { const int rc = plan_ok("spmax_bwd", t_plan, K, ldw, false, nullptr); if (rc) return rc; }
+    const int64_t ldw = seg_slot_pitch(d);
+    if (t_plan)
+        if (const int rc = seg_plan_ok("spmax_bwd", t_plan, K, ldw)) return rc;
     if (K == 0) return SGCN_OK;
 
     SpmaxArgs a{};

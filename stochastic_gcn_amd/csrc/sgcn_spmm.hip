@@ -21,7 +21,11 @@
 //     resident in the 256 MiB Infinity Cache while every row visits it);
 //   * power-law rows are cut into <= T-nonzero segments by a host plan (include/sgcn.h);
 //     split rows go through workspace slots and an ordered fix-up pass (deterministic).
+// The host side of a launch -- the checks on the plan, G / NV / slabs / grid, the ladders over (VW, G, NV), the fix-up's grid --
+// is sgcn_seg.h's, shared with every kernel over a row pattern; spmm_csr_add adds the operand checks, the operand list the
+// vector width is picked from, the unroll U and the two tuning knobs (spmm_nv, spmm_unroll).
 #include "sgcn_dev.h"
+#include "sgcn_seg.h"
 #include <cstring>
 
 namespace sgcn {
@@ -263,46 +267,6 @@ __global__ __launch_bounds__(kBlock) void spmm_fix_kernel(SpmmArgs a, const sgcn
     epilogue_store<VW>(a, fx.row, vi, acc, rs);
 }
 
-template <int G, int NV, int VW, int U, class BT>
-static void launch_seg(const SpmmArgs& a, int64_t nblocks, hipStream_t st) {
-    hipLaunchKernelGGL((spmm_seg_kernel<G, NV, VW, U, BT>), dim3((unsigned)nblocks), dim3(kBlock), 0, st, a);
-}
-
-template <int VW, int U, class BT>
-static bool dispatch_gnv(int G, int NV, const SpmmArgs& a, int64_t nblocks, hipStream_t st) {
-    switch (G) {
-        case 8: launch_seg<8, 1, VW, U, BT>(a, nblocks, st); return true;
-        case 16: launch_seg<16, 1, VW, U, BT>(a, nblocks, st); return true;
-        case 32: launch_seg<32, 1, VW, U, BT>(a, nblocks, st); return true;
-        case 64:
-            switch (NV) {
-                case 1: launch_seg<64, 1, VW, U, BT>(a, nblocks, st); return true;
-                case 2: launch_seg<64, 2, VW, U, BT>(a, nblocks, st); return true;
-                case 3: launch_seg<64, 3, VW, U, BT>(a, nblocks, st); return true;
-                case 4: launch_seg<64, 4, VW, U, BT>(a, nblocks, st); return true;
-            }
-    }
-    return false;
-}
-
-template <int VW, class BT>
-static bool dispatch_u(int U, int G, int NV, const SpmmArgs& a, int64_t nblocks, hipStream_t st) {
-    switch (U) {
-        case 2: return dispatch_gnv<VW, 2, BT>(G, NV, a, nblocks, st);
-        case 4: return dispatch_gnv<VW, 4, BT>(G, NV, a, nblocks, st);
-        case 8: return dispatch_gnv<VW, 8, BT>(G, NV, a, nblocks, st);
-    }
-    return false;
-}
-
-// Geometry shared with the aggregator kernels: lanes per row group for `nvec` vectors.
-int group_lanes(int nvec) {
-    if (nvec <= 8) return 8;
-    if (nvec <= 16) return 16;
-    if (nvec <= 32) return 32;
-    return 64;
-}
-
 }  // namespace sgcn
 
 using namespace sgcn;
@@ -375,47 +339,36 @@ static int spmm_csr_add(const int32_t* rowptr, const int32_t* col, const float* 
         a.add = add; a.ldadd = ldadd; a.add_rows = add_rows;
     }
     if (plan) {
-        SGCN_REQUIRE(plan->dev_seg && plan->nseg >= M, "spmm: malformed plan");
-        a.seg = plan->dev_seg; a.nseg = plan->nseg;
-        a.ws = plan->dev_ws; a.ldw = ((int64_t)d + 3) / 4 * 4;
-        if (plan->nfix > 0) {
-            SGCN_REQUIRE(plan->dev_fix && plan->dev_ws, "spmm: plan with split rows needs dev_fix/dev_ws");
-            SGCN_REQUIRE(plan->ws_elems >= plan->nslots * a.ldw,
-                         "spmm: workspace too small (%lld < %lld floats)", (long long)plan->ws_elems,
-                         (long long)(plan->nslots * a.ldw));
-        }
+        a.ldw = seg_slot_pitch(d);
+        if (const int rc = seg_plan_ok("spmm", plan, M, a.ldw)) return rc;
+        a.seg = plan->dev_seg; a.nseg = plan->nseg; a.ws = plan->dev_ws;
     }
     const int vw = pick_vw(d, {kB16 ? nullptr : (const void*)B, C, plan ? plan->dev_ws : nullptr, a.add},
                            {ldb, ldc, a.add ? a.ldadd : ldc});
     a.nvec = (d + vw - 1) / vw;
-    const int G = group_lanes(a.nvec);
-    int NV = 1;
-    if (G == 64) {
-        const int per_wave = (a.nvec + 63) / 64;          // vectors per lane to cover the row
-        const int nslab0 = (per_wave + 3) / 4;            // slabs at the NV<=4 cap
-        NV = (per_wave + nslab0 - 1) / nslab0;
-        if (g_tune_nv > 0) NV = g_tune_nv;
-    }
-    const int nslab = (a.nvec + G * NV - 1) / (G * NV);
-    const int U = g_tune_unroll > 0 ? g_tune_unroll : (NV >= 3 ? 4 : 8);
-    a.nsegblk = (a.nseg + (kBlock / G) - 1) / (kBlock / G);
-    const int64_t nblocks = a.nsegblk * nslab;
-    SGCN_REQUIRE(nblocks < (1ll << 31), "spmm: grid too large");
+    const SegGeom g = seg_geometry(a.nvec, a.nseg, g_tune_nv);
+    const int U = g_tune_unroll > 0 ? g_tune_unroll : (g.NV >= 3 ? 4 : 8);
+    a.nsegblk = g.nsegblk;
+    SGCN_REQUIRE(g.nblocks < (1ll << 31), "spmm: grid too large");
 
-    bool ok = false;
-    if (vw == 4) ok = dispatch_u<4, BT>(U, G, NV, a, nblocks, st);
-    else if (vw == 2) ok = dispatch_u<2, BT>(U, G, NV, a, nblocks, st);
-    else ok = dispatch_u<1, BT>(U, G, NV, a, nblocks, st);
-    SGCN_REQUIRE(ok, "spmm: no kernel for G=%d NV=%d U=%d", G, NV, U);
+    const dim3 grid((unsigned)g.nblocks), block(kBlock);
+    const bool ok = (U == 2 || U == 4 || U == 8) && with_vw(vw, [&](auto VW) {
+        return with_gnv(g.G, g.NV, [&](auto G, auto NV) {
+            constexpr int kG = decltype(G)::value, kNV = decltype(NV)::value, kVW = decltype(VW)::value;
+            if (U == 2) hipLaunchKernelGGL((spmm_seg_kernel<kG, kNV, kVW, 2, BT>), grid, block, 0, st, a);
+            else if (U == 4) hipLaunchKernelGGL((spmm_seg_kernel<kG, kNV, kVW, 4, BT>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((spmm_seg_kernel<kG, kNV, kVW, 8, BT>), grid, block, 0, st, a);
+        });
+    });
+    SGCN_REQUIRE(ok, "spmm: no kernel for G=%d NV=%d U=%d", g.G, g.NV, U);
     SGCN_HIP_TRY(hipGetLastError());
 
     if (plan && plan->nfix > 0) {
-        const int64_t nfblk = (int64_t)((a.nvec + kBlock - 1) / kBlock) * plan->nfix;
+        const int64_t nfblk = seg_fix_blocks(a.nvec, plan->nfix);
         SGCN_REQUIRE(nfblk < (1ll << 31), "spmm: too many split rows");
-        dim3 grid((unsigned)nfblk);
-        if (vw == 4) hipLaunchKernelGGL((spmm_fix_kernel<4>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-        else if (vw == 2) hipLaunchKernelGGL((spmm_fix_kernel<2>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
-        else hipLaunchKernelGGL((spmm_fix_kernel<1>), grid, dim3(kBlock), 0, st, a, plan->dev_fix, plan->nfix);
+        with_vw(vw, [&](auto VW) {
+            hipLaunchKernelGGL((spmm_fix_kernel<decltype(VW)::value>), dim3((unsigned)nfblk), block, 0, st, a, plan->dev_fix, plan->nfix);
+        });
         SGCN_HIP_TRY(hipGetLastError());
     }
     return SGCN_OK;

@@ -18,7 +18,7 @@ import zlib
 
 import numpy as np
 
-kBlock, kWave = 256, 64              # sgcn_dev.h
+kBlock, kWave = 256, 64              # sgcn_host.h
 kTChunk, kTLdsCols = 512, 16384      # sgcn_rows.hip: nonzeros per transpose chunk; counters in LDS up to this many columns
 kTailRows = kBlock // 32             # sgcn_dense.hip kTailRowsPerBlock: history rows per workgroup of the optimizer's launch
 kTailCols = 128                      # ... and the columns one trip of its 32 lanes x float4 covers
@@ -46,7 +46,7 @@ def pitches(d):
 
 # ---- launch_rows ------------------------------------------------------------------------------------------------------------
 def group_lanes(nvec):
-    """sgcn_spmm.hip group_lanes"""
+    """sgcn_seg.h group_lanes"""
     return 8 if nvec <= 8 else 16 if nvec <= 16 else 32 if nvec <= 32 else 64
 
 

@@ -20,7 +20,8 @@ import spmax_ref as ref
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (1, 3, 4, 5, 31, 32, 33, 64, 65, 128, 130)
+# (at the odd pitch -- scalar lanes -- 200 is 200 vectors: a lane keeps NV = 4; 260 is 260: NV = 3 and two feature slabs)
+WIDTHS = (1, 3, 4, 5, 31, 32, 33, 64, 65, 128, 130, 200, 260)
 PLANS = ("none", "default", "T", "1")
 SENTINEL = -77
 
