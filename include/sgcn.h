@@ -821,6 +821,27 @@ int sgcn_csr_induce_fill(const int32_t* dev_rowptr, const int32_t* dev_col, cons
                          int32_t n, const int32_t* dev_map, const int32_t* dev_o_rowptr, const float* dev_rscale,
                          int32_t* dev_o_col, float* dev_o_val, int32_t* dev_o_coo_row, int32_t scale_cols, int64_t cap,
                          void* stream);
+/* The two-table gather product of a part step that keeps its out-of-part entries (--full_batch_part_history: GNNAutoScale /
+ * Cluster-GCN with historical embeddings; sgcn_spmm_pull.hip):
+ *
+ *   C[i, :] = sum over e in [rowptr[ids[i]], rowptr[ids[i] + 1]) of
+ *             val[e] * ( map[col[e]] >= 0 ? X[map[col[e]], :] : H[col[e], :] )        i = 0 .. n-1
+ *
+ * The CSR is the RESIDENT N x N training adjacency, never copied; ids are the ids of S, ascending and unique; map is what
+ * sgcn_induce_map_i32 writes for ids.  X is n x d fp32 (the fresh rows: never rounded), H is N x d -- fp32 (_f32), or a
+ * bfloat16 table of N x ldh uint16 (_h16: ldh in ELEMENTS and a multiple of 8, base 16-byte aligned), widened exactly
+ * (bits << 16) in front of the multiply-add; the sums and C stay fp32, and _h16 gives the bits of _f32 on the widened table.
+ * Rows of H inside S are never read, rows of X only where map selects them.  One lane group owns one selected row: NO plan
+ * and NO split rows in this version -- a launch runs as long as its longest selected row.  Every sum is taken in stored
+ * order, without atomics: the same bits on every run.  The vector width is the widest that the alignment of X, H (_f32), C
+ * and the three pitches allow.  SGCN_ERR_INVALID, before any HIP call, for a negative size, n > N, d <= 0, a pitch below d,
+ * a null operand with n > 0; n == 0 returns SGCN_OK without a launch. */
+int sgcn_spmm_pull_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, const int32_t* dev_ids,
+                       int32_t n, int32_t N, const int32_t* dev_map, int32_t d, const float* dev_X, int64_t ldx,
+                       const float* dev_H, int64_t ldh, float* dev_C, int64_t ldc, void* stream);
+int sgcn_spmm_pull_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, const int32_t* dev_ids,
+                       int32_t n, int32_t N, const int32_t* dev_map, int32_t d, const float* dev_X, int64_t ldx,
+                       const uint16_t* dev_H, int64_t ldh, float* dev_C, int64_t ldc, void* stream);
 /* out[i] = src[idx[i]] */
 int sgcn_gather_f32(const float* dev_src, const int32_t* dev_idx, int64_t n, float* dev_out, void* stream);
 

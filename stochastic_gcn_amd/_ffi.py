@@ -276,6 +276,10 @@ SIGNATURES = {
     "sgcn_induce_map_i32": (C.c_int, [P, C.c_int32, C.c_int32, P, P]),
     "sgcn_csr_induce_count": (C.c_int, [P, P, P, P, C.c_int32, P, P, P, P, P]),
     "sgcn_csr_induce_fill": (C.c_int, [P, P, P, P, C.c_int32, P, P, P, P, P, P, C.c_int32, C.c_int64, P]),
+    # the two-table gather product of a part step with history (--full_batch_part_history):
+    # (rowptr, col, val, ids, n, N, map, d, X, ldx, H, ldh, C, ldc, stream)
+    "sgcn_spmm_pull_f32": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P]),
+    "sgcn_spmm_pull_h16": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P]),
     "sgcn_step_run": (C.c_int, [C.POINTER(StepOp), C.c_int32, P, C.c_int32, P]),
     "sgcn_step_fill": (C.c_int, [C.POINTER(StepFill), P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                                  P, C.c_int64]),

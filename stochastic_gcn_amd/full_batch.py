@@ -29,6 +29,9 @@ two products).
   PartSchedule   per epoch a seeded permutation of the parts in groups of q; a step runs on the union S of a group
   InducedMatrix  the StaticMatrix of A[S, S], over the block ops.csr_induce cut out of the resident CSR on the device
   PartBatch      the StaticBatch of that block: labels[S] and the positions within S of the training vertices
+  PulledMatrix   --full_batch_part_history (GNNAutoScale): the InducedMatrix of the 'keep' block that also carries the resident
+                 adjacency, the ids and map of S and the model's history tables; ``pull_product`` sums over every stored entry of
+                 the rows of S, fresh rows for columns in S and stored rows for the others (ops.spmm_pull)
 """
 import numpy as np
 import torch
@@ -767,6 +770,32 @@ def check_full_batch_parts(flags=None, num_vertices=None):
     return P, q, norm
 
 
+def check_part_history(flags=None):
+    """(on, bf16) of --full_batch_part_history / --history_dtype: part steps that read stored rows for their out-of-part
+    neighbours (GNNAutoScale), with what the two-table product has no kernel or no meaning for refused.  Needs no device; a
+    sibling of check_full_batch_parts, called beside it."""
+    f = FLAGS if flags is None else flags
+    if not bool(getattr(f, 'full_batch_part_history', False)):
+        return False, False
+    if int(getattr(f, 'full_batch_parts', 0) or 0) <= 0:
+        raise ValueError("--full_batch_part_history needs --full_batch_parts > 0: it is the estimator of a part step's "
+                         "out-of-part neighbours, and no other mode has them")
+    agg = getattr(f, 'aggregator', 'sum')
+    if agg != 'sum':
+        raise ValueError("--full_batch_part_history is not supported with --aggregator %s: the maximum and the attention "
+                         "kernels gather from one table; a two-table form is a follow-up" % agg)
+    if getattr(f, 'reverse', False):
+        raise ValueError("--full_batch_part_history is not supported with --reverse: the aggregator's input would be a "
+                         "dropout-masked table, and the stored rows would hold one step's mask")
+    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
+        raise ValueError("--full_batch_part_history is not supported with --full_batch_dtype bf16: the pull kernel's fresh "
+                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)")
+    hd = getattr(f, 'history_dtype', 'fp32')
+    if hd not in _CHOICES['history_dtype']:
+        raise ValueError("--history_dtype must be one of %s, got %r" % ('/'.join(_CHOICES['history_dtype']), hd))
+    return True, hd == 'bf16'
+
+
 def partition(adj, P, seed=1):
     """The vertices of ``adj`` cut into P parts, as P ascending int32 id arrays; deterministic in (adj, P, seed).
 
@@ -845,6 +874,37 @@ class InducedMatrix(StaticMatrix):
         return dict(plan_from_cache=False, pace=None, kernel="sgcn::spmm_seg_kernel", products=self.products)
 
 
+class PulledMatrix(InducedMatrix):
+    """The matrix of a part step under --full_batch_part_history: the InducedMatrix of the 'keep' block A[S, S] -- ``transpose``
+    and every inherited product are that block's, so the backward, ``A.transpose.product(g, ...)``, sees in-part entries only
+    and stored rows are constants -- which also carries what the forward reads instead: the RESIDENT adjacency, the ids of S
+    on the device, their position map (the block's, ops.csr_induce) and the model's history tables, one per aggregation
+    layer.  ``pull_product(x, l)`` is the neighbour sum of layer l over EVERY stored entry of the rows of S (ops.spmm_pull:
+    fresh rows of ``x`` for columns in S, rows of table l for the others); ``push(x, l)`` then stores the layer's input rows
+    into table l (ops.scatter_rows) -- columns in S never read the table, so push-after-pull is safe.  A table that is not
+    ``owned`` (the resident feature table under an aggregation layer with no layer in front of it) is exact and never written."""
+
+    def __init__(self, block, resident, ids_dev, tables, owned, device=None):
+        if getattr(block, 'map', None) is None:
+            raise ValueError("a PulledMatrix needs the block's position map (ops.csr_induce)")
+        super(PulledMatrix, self).__init__(block, device, bf16=False)
+        if int(resident.shape[0]) != int(resident.shape[1]) or int(ids_dev.shape[0]) != self.shape[0]:
+            raise ValueError("a PulledMatrix needs the square resident matrix and the %d ids of its block" % self.shape[0])
+        if len(tables) != len(owned):
+            raise ValueError("a PulledMatrix needs one owned flag per history table")
+        self.resident, self.ids_dev, self.map, self.tables, self.owned = resident, ids_dev, block.map, list(tables), list(owned)
+
+    def pull_product(self, x, l, out=None):
+        return ops.spmm_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], out=out)
+
+    def push(self, x, l):
+        if self.owned[l]:
+            ops.scatter_rows(self.tables[l], self.ids_dev, x)
+
+    def describe(self, d):
+        return dict(plan_from_cache=False, pace=None, kernel="sgcn::spmm_pull_kernel", products=self.products)
+
+
 class PartBatch(StaticBatch):
     """One Cluster-GCN step's batch: the static batch of the induced subgraph over ``ids`` (ascending, unique) -- the
     InducedMatrix, labels[ids] (ops.gather_rows of the resident N x C table) and the loss rows, the POSITIONS within ``ids``
@@ -854,7 +914,8 @@ class PartBatch(StaticBatch):
         n = int(matrix.shape[0])
         if int(len(ids)) != n or int(ids_dev.shape[0]) != n:
             raise ValueError("a part batch over %d vertices needs a matrix of that size, got %d" % (len(ids), n))
-        super(PartBatch, self).__init__(matrix, ops.gather_rows(labels, ids_dev), rows, L, device)
+        # (labels and rows both None: a batch for forward passes only -- the refresh of a group without a training vertex)
+        super(PartBatch, self).__init__(matrix, None if labels is None else ops.gather_rows(labels, ids_dev), rows, L, device)
         self.ids, self.ids_dev = np.asarray(ids, dtype=np.int32), ids_dev
 
 

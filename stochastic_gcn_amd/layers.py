@@ -475,14 +475,27 @@ class PlainAggregator(Layer):
             out[:, :d] = x[:n1]
             self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads, **self._drop)
             return out
+        # --full_batch_part_history: the step's matrix (full_batch.PulledMatrix) sums over EVERY stored entry of its rows --
+        # fresh rows of x for columns inside the step's vertex set, this layer's stored rows for the others -- and the layer
+        # then pushes its input rows into that table (columns inside the set never read it: push-after-pull is safe).  The
+        # backward stays A.transpose.product: the 'keep' block, in-part entries only
+        pull = hasattr(A, 'pull_product')
         if not concat:
-            return A.product(x)
+            if not pull:
+                return A.product(x)
+            out = A.pull_product(x, self.l)
+            A.push(x, self.l)
+            return out
         out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
         if x.dtype == torch.bfloat16:       # the feature table under --feature_dtype bf16: the self half widened in place
             ops.gather_rows(x[:n1], None, out=out[:, :d])
         else:
             out[:, :d] = x[:n1]
-        A.product(x, out=out[:, d:])
+        if pull:
+            A.pull_product(x, self.l, out=out[:, d:])
+            A.push(x, self.l)
+        else:
+            A.product(x, out=out[:, d:])
         return out
 
     def backward(self, g):

@@ -391,6 +391,28 @@ class GCN(Model):
     def _build_history(self):
         self.history = []
 
+    # --full_batch_part_history: what a part step reads for its out-of-part neighbours, one table per aggregation layer --
+    # (tables, owned).  None without the flag.  Not the control-variate history (``_history`` stays empty: _upload_static keeps
+    # refusing cv models) and not written to checkpoints.
+    part_history = None
+
+    def alloc_part_history(self, bf16=False):
+        """Allocates ``part_history`` and returns the bytes it took.  An aggregation layer with no layer in front of it (layer
+        0 under --nopreprocess) reads the resident feature table -- exact, never written, nothing allocated; every other layer
+        owns one zero-filled N x width table of ops.history_alloc (fp32, or bfloat16)."""
+        tables, owned, nbytes = [], [], 0
+        for l in range(self.L):
+            if l == 0 and not self.preprocess:
+                tables.append(self.features_dev)
+                owned.append(False)
+                continue
+            t = ops.history_alloc(int(self.num_data), int(self.agg0_dim if l == 0 else FLAGS.hidden1), self.device, bf16=bf16)
+            nbytes += int(t.shape[0]) * int(t.stride(0)) * t.element_size()
+            tables.append(t)
+            owned.append(True)
+        self.part_history = (tables, owned)
+        return nbytes
+
     def _build_aggregators(self):
         pass
 
@@ -1060,6 +1082,25 @@ class GCN(Model):
             outs = [None, loss, acc] if self.is_training else [loss, acc, pred]
         self.run_t += time() - t
         return outs
+
+    def refresh_part_history(self, feed_dict):
+        """--full_batch_part_history, a group without a training vertex: the training-mode forward of the part batch up to the
+        LAST aggregation layer's input, so that every table takes the group's rows -- the layers in front push their own
+        (layers.PlainAggregator), the last layer's input is pushed here.  No loss, no backward, no optimizer step."""
+        from .layers import PlainAggregator, dense_of
+        if not hasattr(feed_dict.matrix, 'push'):
+            raise ValueError("refresh_part_history needs a part batch over a full_batch.PulledMatrix")
+        self.dropout = float(getattr(feed_dict, 'dropout', 0.0) or 0.0) if self.is_training else 0.0
+        cur = self.get_data(feed_dict)
+        last = max(i for i, layer in enumerate(self.layers) if isinstance(layer, PlainAggregator))
+        ops.pin_stream()
+        try:
+            self.forward(cur, stop=last)
+            if feed_dict.matrix.owned[self.L - 1]:
+                feed_dict.matrix.push(dense_of(self.activations[-1]), self.L - 1)
+        finally:
+            ops.unpin_stream()
+        self.dropout_step += 1
 
     def get_pred_and_grad(self, sess, feed_dict):
         """Prediction and the gradient of the loss wrt the first variable (gcn/models.py:196),

@@ -1010,9 +1010,44 @@ def csr_induce(A, ids_host, ids_dev=None, norm='keep', plan_T=0):
     block.coo_rows = b.coo[:nnz]
     block.transpose = csr(b.t_rowptr, trp, b.t_row, b.t_val)
     block.transpose.transpose = block
-    if getattr(A, '_unique_cols', False):          # (check_unique_cols passed on A: its blocks store no column twice either)
+    block.map = b.map          # the position map of ``ids`` (N words; valid, like the block, until the next call): ops.spmm_pull
+    if getattr(A, '_unique_cols', False):         # (check_unique_cols passed on A: its blocks store no column twice either)
         block._unique_cols = block.transpose._unique_cols = True
     return block
+
+
+def spmm_pull(A, ids_dev, map_dev, x, H, out=None):
+    """out[i] = sum over the stored entries e of row ids[i] of the RESIDENT square DeviceCSR ``A`` of
+    val[e] * (x[map[col[e]]] if map[col[e]] >= 0 else H[col[e]])   (sgcn_spmm_pull_f32 / _h16; --full_batch_part_history).
+
+    ``ids_dev``: the n selected vertices on the device, ascending and unique; ``map_dev``: their position map (N words,
+    ``csr_induce(...).map``); ``x``: n x d fp32, the rows the step computes; ``H``: N x d, the stored rows of every vertex --
+    fp32, or a bfloat16 table of ``history_alloc(..., bf16=True)``'s layout, widened exactly.  ``A`` is read in place: no
+    cut, no plan, no synchronisation; one lane group per selected row, however long."""
+    N = int(A.shape[0])
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("spmm_pull needs a square (vertex x vertex) matrix")
+    _dev(ids_dev, torch.int32, "ids_dev")
+    _dev(map_dev, torch.int32, "map_dev")
+    n = int(ids_dev.shape[0])
+    xptr, ldx = _rows2d(x, "x")
+    hptr, ldh, h16 = _hist2d(H, "H")
+    d = int(x.shape[1])
+    if int(x.shape[0]) != n:
+        raise ValueError("x has %d rows, ids_dev %d entries" % (int(x.shape[0]), n))
+    if int(H.shape[0]) < N or int(H.shape[1]) != d:
+        raise ValueError("H has shape %s, need (>=%d, %d)" % (tuple(H.shape), N, d))
+    if int(map_dev.shape[0]) < N:
+        raise ValueError("map_dev has %d words, the matrix %d vertices" % (int(map_dev.shape[0]), N))
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != n or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), n, d))
+    check((lib.sgcn_spmm_pull_h16 if h16 else lib.sgcn_spmm_pull_f32)(
+        A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, xptr, ldx, hptr, ldh,
+        cptr, ldc, _stream()))
+    return out
 
 
 def adam_step(theta, grad, m, v, lr_t, beta1, beta2, eps=1e-8):

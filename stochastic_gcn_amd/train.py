@@ -26,7 +26,8 @@ import torch
 
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
-from .full_batch import (InducedMatrix, PartBatch, PartSchedule, check_full_batch_parts, part_stats, partition,
+from .full_batch import (InducedMatrix, PartBatch, PartSchedule, PulledMatrix, check_full_batch_parts, check_part_history,
+                         part_stats, partition,
                          StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
@@ -237,6 +238,8 @@ class Trainer(object):
         # (--full_batch_parts negative, without --full_batch, q outside [1, P], with an edge mask, a bfloat16 feature table or a
         # sweep kernel: too; P against the number of vertices once the graph is loaded)
         self.parts, self.parts_per_step, self.part_norm = check_full_batch_parts()
+        # (--full_batch_part_history without parts, with --aggregator max / attn, --reverse or a bfloat16 operand: too)
+        self.part_history, self.part_history_bf16 = check_part_history()
         # (--aggregator max without both full-graph modes, with a bfloat16 table or an edge mask: too)
         self.max_aggregator = check_aggregator()
         # (--aggregator attn likewise; --attn_scale negative, non-finite, or set without attn: too)
@@ -446,31 +449,53 @@ class Trainer(object):
         self.log('[sgcn] --full_batch_parts {}: {} parts per step, {} steps per epoch on induced subgraphs cut on the device '
                  '(values: {}) | part sizes min / median / max = {} / {:g} / {} | training vertices per part = {} / {:g} / {} | '
                  '{:.1f} % of the nonzeros lie inside parts'.format(
-                     self.parts, self.parts_per_step, len(self.part_schedule), self.part_norm, s['sizes'][0], s['sizes'][1],
+                     self.parts, self.parts_per_step, len(self.part_schedule), 'history' if self.part_history else self.part_norm,
+                     s['sizes'][0], s['sizes'][1],
                      s['sizes'][2], s['train'][0], s['train'][1], s['train'][2], 100.0 * s['inside']))
+        if self.part_history:
+            # out-of-part neighbours read stored rows: one table per aggregation layer, on the training model
+            nbytes = self.train_model.alloc_part_history(self.part_history_bf16)
+            tables, owned = self.train_model.part_history
+            self.log('[sgcn] --full_batch_part_history: a step sums over every stored entry of its rows -- fresh rows inside its '
+                     'vertex set, stored rows outside (nothing dropped, nothing rescaled) | {} table(s) of {} rows, {}: {:.1f} '
+                     'MiB, zero-filled{} | a group without a training vertex runs the forward only and pushes its rows'.format(
+                         sum(owned), N, 'bf16' if self.part_history_bf16 else 'fp32', nbytes / 2.0 ** 20,
+                         '' if all(owned) else '; the first aggregation layer reads the resident feature table'))
 
     def part_batch(self, ids):
         """The batch of one step over the vertex set ``ids`` (ascending): the block cut out of the resident adjacency with its
         transpose and plans (ops.csr_induce), labels[ids], and the loss rows -- the positions within ``ids`` of the training
-        vertices.  None where ``ids`` holds no training vertex."""
+        vertices.  None where ``ids`` holds no training vertex.
+
+        Under --full_batch_part_history the cut is made with norm='keep' and the matrix is a PulledMatrix; a set without a
+        training vertex gives a batch for the forward only (no labels, no loss rows)."""
         rows = np.flatnonzero(self._train_mask[ids]).astype(np.int32)
-        if rows.size == 0:
+        if rows.size == 0 and not self.part_history:
             return None
         ids_dev = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.device, non_blocking=True)
+        if self.part_history:
+            block = ops.csr_induce(self.train_csr, ids, ids_dev, norm='keep')
+            tables, owned = self.train_model.part_history
+            matrix = PulledMatrix(block, self.train_csr, ids_dev, tables, owned, self.device)
+            if rows.size == 0:
+                return PartBatch(ids, ids_dev, matrix, None, None, self.train_model.L, self.device)
+            return PartBatch(ids, ids_dev, matrix, self._labels_dev, rows, self.train_model.L, self.device)
         block = ops.csr_induce(self.train_csr, ids, ids_dev, norm=self.part_norm)
         return PartBatch(ids, ids_dev, InducedMatrix(block, self.device, bf16=full_batch_bf16()), self._labels_dev, rows,
                          self.train_model.L, self.device)
 
     def train_epoch_parts(self):
         """One epoch of Cluster-GCN steps: for every group of the epoch's schedule build the batch, run_one_step, next.  A
-        group without a training vertex is skipped and counted; last_epoch['steps'] is the number of steps run.  Building a
+        group without a training vertex is skipped and counted; last_epoch['steps'] is the number of steps run.  Under
+        --full_batch_part_history such a group is not skipped: it runs the forward only, so that its rows reach the tables
+        (Model.refresh_part_history), and is counted as last_epoch['refreshed'].  Building a
         batch synchronises once (the block's row pointers), so the host does not run ahead of the device by more than a step."""
         model = self.train_model
         t = time()
         model.init_counts()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-        outs, steps, skipped, build_s = None, 0, 0, 0.0
+        outs, steps, skipped, refreshed, build_s = None, 0, 0, 0, 0.0
         for ids in self.part_schedule.epoch(self._parts_epoch):
             t1 = time()
             batch = self.part_batch(ids)
@@ -479,6 +504,11 @@ class Trainer(object):
                 skipped += 1
                 continue
             batch.dropout = FLAGS.dropout
+            if batch.rows is None:
+                # --full_batch_part_history: skipped, the group's rows would stay zero and every neighbour keep reading zeros
+                model.refresh_part_history(batch)
+                refreshed += 1
+                continue
             outs = model.run_one_step(self.sess, batch, sync=False)
             steps += 1
         self._parts_epoch += 1
@@ -492,6 +522,8 @@ class Trainer(object):
         self.last_epoch = dict(train_wall_s=time() - t, steps=steps, skipped=skipped, sch_wait_s=build_s, host_loop_s=host_loop_s,
                                producer_s=None, sampled_edges=float(model.adj_sizes.sum()), full_edges=0.0,
                                field0=float(model.field_sizes[0]))
+        if self.part_history:
+            self.last_epoch['refreshed'] = refreshed
         return t, build_s
 
     # ---- the exact history passes (exact_history.py) ------------------------------------------------
