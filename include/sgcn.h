@@ -842,6 +842,53 @@ int sgcn_spmm_pull_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const 
 int sgcn_spmm_pull_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, const int32_t* dev_ids,
                        int32_t n, int32_t N, const int32_t* dev_map, int32_t d, const float* dev_X, int64_t ldx,
                        const uint16_t* dev_H, int64_t ldh, float* dev_C, int64_t ldc, void* stream);
+/* Two-table softmax dot-product attention of a part step that keeps its out-of-part entries (--full_batch_part_pull with
+ * --aggregator attn; sgcn_spattn_pull.hip).  The setting is that of sgcn_spmm_pull_*: the CSR is the RESIDENT N x N adjacency,
+ * read in place (stored values are not read; column ids unique per row), ids the n ids of S, ascending and unique, map what
+ * sgcn_induce_map_i32 wrote for ids; X is n x d fp32 -- the fresh rows: the queries, and the keys / values of in-part columns
+ * -- and H is N x d, fp32 (_f32) or a bfloat16 table with the layout and the checks of sgcn_spmm_pull_h16, widened exactly.
+ * For a stored entry e of row ids[i], with c = col[e]:   B_e = map[c] >= 0 ? X[map[c]] : H[c].   Per head h, with the head
+ * slicing of sgcn_spattn_mh_csr_f32 (heads in 1/2/4/8, d % heads == 0):
+ *
+ *   s_e = scale * <X[i], B_e>_h,   lse[i, h] = log sum_e exp(s_e),   C[i]^h = sum_e exp(s_e - lse[i, h]) B_e^h
+ *
+ * Everything else is that call's definition: online softmax, true division acc / l, lse = m + log l in fp64 rounded once, an
+ * empty row gives +0.0 and -inf, a chunk's pads have weight exactly 0.  lse is n x heads, nullable.  One lane group owns one
+ * selected row: NO plan, NO split rows and no workspace in this version -- a launch runs as long as its longest selected row --
+ * and the per-row arithmetic is the one-table kernel's, so a launch gives, bit for bit, what sgcn_spattn_mh_csr_f32 without a
+ * plan gives on (the rows ids of the CSR, Q = X, B = H with the rows of S replaced by X).  Rows of H inside S are never read.
+ * No atomics, nothing nnz-sized is written: the same bits on every run.  _h16 gives the bits of _f32 on the widened table.
+ * The vector width is the widest that X, H (_f32), C and the three pitches allow and that divides d / heads; d <= 256 * VW.
+ * SGCN_ERR_INVALID, before any HIP call and with nothing written, for a negative size, n > N, d <= 0, heads outside 1/2/4/8 or
+ * not dividing d, a pitch below d, a null operand with n > 0, a non-finite scale, a width over the limit, a malformed
+ * bfloat16 table; n == 0 returns SGCN_OK without a launch. */
+int sgcn_spattn_pull_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                         const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx, const float* dev_H,
+                         int64_t ldh, float scale, float* dev_C, int64_t ldc, float* dev_lse, void* stream);
+int sgcn_spattn_pull_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                         const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx, const uint16_t* dev_H,
+                         int64_t ldh, float scale, float* dev_C, int64_t ldc, float* dev_lse, void* stream);
+/* The query's half of that attention's backward, for G = dL/dC (n x d) with the forward's C and lse:
+ *
+ *   delta[i, h] = <G[i], C[i]>_h,   e_e = exp(s_e - lse[i, h]) (<G[i], B_e>_h - delta[i, h]),
+ *   dQ[i] = scale * sum_e e_e B_e  (+ add[i] for i < add_rows)
+ *
+ * over ALL stored entries of row ids[i]: stored rows are constants, but the query's gradient sees them.  delta (out) is
+ * n x heads.  The gradient to keys / values flows through in-part entries only: sgcn_spattn_mh_csr_bwd_kv_f32 over the
+ * transposed induced block A[S, S]^T with Q = B = X, this lse and delta, add = dQ and add_rows = n gives
+ * dX = dB + dQ without a further pass.  Geometry, restrictions, reproducibility and the bit identity with
+ * sgcn_spattn_mh_csr_bwd_q_f32 on the merged table as above; the vector width also looks at G, C, dQ, add and their pitches.
+ * SGCN_ERR_INVALID as above, and for a bad addend (ldadd < d or add_rows > n). */
+int sgcn_spattn_pull_bwd_q_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                               const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx,
+                               const float* dev_H, int64_t ldh, float scale, const float* dev_G, int64_t ldg,
+                               const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dQ,
+                               int64_t lddq, const float* dev_add, int64_t ldadd, int32_t add_rows, void* stream);
+int sgcn_spattn_pull_bwd_q_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                               const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx,
+                               const uint16_t* dev_H, int64_t ldh, float scale, const float* dev_G, int64_t ldg,
+                               const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dQ,
+                               int64_t lddq, const float* dev_add, int64_t ldadd, int32_t add_rows, void* stream);
 /* out[i] = src[idx[i]] */
 int sgcn_gather_f32(const float* dev_src, const int32_t* dev_idx, int64_t n, float* dev_out, void* stream);
 

@@ -280,6 +280,20 @@ SIGNATURES = {
     # (rowptr, col, val, ids, n, N, map, d, X, ldx, H, ldh, C, ldc, stream)
     "sgcn_spmm_pull_f32": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P]),
     "sgcn_spmm_pull_h16": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P]),
+    # two-table attention of a part step with stale rows (--full_batch_part_pull, --aggregator attn):
+    # (rowptr, col, ids, n, N, map, d, heads, X, ldx, H, ldh, scale, C, ldc, lse, stream),
+    # (rowptr, col, ids, n, N, map, d, heads, X, ldx, H, ldh, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd, add_rows,
+    #  stream)
+    "sgcn_spattn_pull_f32": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                       C.c_float, P, C.c_int64, P, P]),
+    "sgcn_spattn_pull_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                       C.c_float, P, C.c_int64, P, P]),
+    "sgcn_spattn_pull_bwd_q_f32": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                             C.c_float, P, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int32,
+                                             P]),
+    "sgcn_spattn_pull_bwd_q_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                             C.c_float, P, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int32,
+                                             P]),
     "sgcn_step_run": (C.c_int, [C.POINTER(StepOp), C.c_int32, P, C.c_int32, P]),
     "sgcn_step_fill": (C.c_int, [C.POINTER(StepFill), P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                                  P, C.c_int64]),

@@ -307,7 +307,7 @@ int keep_ok(const char* who, float keep) {
 }
 
 // the mask of a call; keep == 1: mk = 0, which `run` reads as `the kernels without dropout`
-AttnDrop drop_of(float keep, uint32_t key) {
+inline AttnDrop drop_of(float keep, uint32_t key) {
     AttnDrop dm{};
     if (keep >= 1.0f) return dm;
     sgcn_dropout_t d{};

@@ -36,6 +36,7 @@
 // S-Reddit at d = 128 -- supposedly the per-entry branch between the two load widths inside the U-deep request loop, which
 // the f32 form does not have; a branch-free h16 form is the second follow-up.
 #include "sgcn_dev.h"
+#include "sgcn_pull_dev.h"
 #include "sgcn_seg.h"
 
 namespace sgcn {
@@ -59,53 +60,6 @@ struct PullArgs {
     int32_t nvec;            // ceil(d / VW)
     int32_t slabmajor;
 };
-
-// the raw image of VW operand elements: VW dwords (a fresh fp32 vector; a bfloat16 vector in the lower half)
-template <int VW> struct PullRaw { typedef uint32_t type __attribute__((ext_vector_type(VW))); };
-template <> struct PullRaw<1> { typedef uint32_t type; };
-
-template <int VW, class HT>
-__device__ __forceinline__ typename PullRaw<VW>::type pull_load(const char* src, uint32_t xoff, bool stale) {
-    typedef typename PullRaw<VW>::type RT;
-    if constexpr (std::is_same<HT, float>::value) {
-        return *reinterpret_cast<const RT*>(src + xoff);                        // either table: fp32 rows
-    } else {
-        RT r = {};
-        if (stale) {
-            const uint16_t* p = reinterpret_cast<const uint16_t*>(src + (xoff >> 1));
-            if constexpr (VW == 4) { const auto h = hraw<4>(p); r.x = h.x; r.y = h.y; }
-            else if constexpr (VW == 2) r.x = hraw<2>(p);
-            else r = hraw<1>(p);
-        } else {
-            r = *reinterpret_cast<const RT*>(src + xoff);
-        }
-        return r;
-    }
-}
-
-template <int VW, class HT>
-__device__ __forceinline__ typename Vec<VW>::type pull_value(typename PullRaw<VW>::type r, bool stale) {
-    typedef typename Vec<VW>::type VT;
-    if constexpr (VW == 1) {
-        if constexpr (!std::is_same<HT, float>::value) { if (stale) return hwiden1(r); }
-        return __uint_as_float(r);
-    } else {
-        VT v;
-        if constexpr (!std::is_same<HT, float>::value) {
-            if (stale) {
-                if constexpr (VW == 2) { v[0] = hwiden1(r.x); v[1] = __uint_as_float(r.x & 0xffff0000u); }
-                else {
-                    v[0] = hwiden1(r.x); v[1] = __uint_as_float(r.x & 0xffff0000u);
-                    v[2] = hwiden1(r.y); v[3] = __uint_as_float(r.y & 0xffff0000u);
-                }
-                return v;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < VW; e++) v[e] = __uint_as_float(r[e]);
-        return v;
-    }
-}
 
 template <int G, int NV, int VW, int U, class HT>
 __global__ __launch_bounds__(kBlock) void spmm_pull_kernel(PullArgs a) {

@@ -31,7 +31,9 @@ two products).
   PartBatch      the StaticBatch of that block: labels[S] and the positions within S of the training vertices
   PulledMatrix   --full_batch_part_history (GNNAutoScale): the InducedMatrix of the 'keep' block that also carries the resident
                  adjacency, the ids and map of S and the model's history tables; ``pull_product`` sums over every stored entry of
-                 the rows of S, fresh rows for columns in S and stored rows for the others (ops.spmm_pull)
+                 the rows of S, fresh rows for columns in S and stored rows for the others (ops.spmm_pull); under
+                 --full_batch_part_pull with --aggregator attn ``pull_attn_product`` / ``pull_attn_backward`` attend over
+                 the same entries (ops.spattn_pull, ops.spattn_pull_bwd_q, then the block's bwd_kv)
 """
 import numpy as np
 import torch
@@ -796,6 +798,43 @@ def check_part_history(flags=None):
     return True, hd == 'bf16'
 
 
+def check_part_pull(flags=None):
+    """(on, bf16) of --full_batch_part_pull / --history_dtype: part steps of the sum AND the attention aggregator that read
+    stored rows for their out-of-part neighbours.  With --aggregator sum it is --full_batch_part_history exactly; with
+    --aggregator attn every aggregation layer attends over every stored neighbour (ops.spattn_pull).  What the two-table
+    kernels have no form or no meaning for is refused.  Needs no device; called beside check_part_history, which keeps its
+    own contract and, with both flags on, speaks first."""
+    f = FLAGS if flags is None else flags
+    if not bool(getattr(f, 'full_batch_part_pull', False)):
+        return False, False
+    if int(getattr(f, 'full_batch_parts', 0) or 0) <= 0:
+        raise ValueError("--full_batch_part_pull needs --full_batch_parts > 0: it is the estimator of a part step's "
+                         "out-of-part neighbours, and no other mode has them")
+    agg = getattr(f, 'aggregator', 'sum')
+    if agg == 'max':
+        raise ValueError("--full_batch_part_pull is not supported with --aggregator max: the maximum kernel gathers from one "
+                         "table; a two-table maximum is a follow-up")
+    if agg not in ('sum', 'attn'):
+        raise ValueError("--full_batch_part_pull is not supported with --aggregator %s" % agg)
+    if agg == 'attn':
+        if getattr(f, 'attn_score', 'dot') == 'gat':
+            raise ValueError("--full_batch_part_pull is not supported with --attn_score gat: its score table would need "
+                             "stale scores for the out-of-part neighbours; a two-table form is a follow-up")
+        if float(getattr(f, 'attn_dropout', 0.0) or 0.0) > 0:
+            raise ValueError("--full_batch_part_pull is not supported with --attn_dropout > 0: in this version the mask of "
+                             "out-of-part entries is not defined")
+    if getattr(f, 'reverse', False):
+        raise ValueError("--full_batch_part_pull is not supported with --reverse: the aggregator's input would be a "
+                         "dropout-masked table, and the stored rows would hold one step's mask")
+    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
+        raise ValueError("--full_batch_part_pull is not supported with --full_batch_dtype bf16: the pull kernels' fresh "
+                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)")
+    hd = getattr(f, 'history_dtype', 'fp32')
+    if hd not in _CHOICES['history_dtype']:
+        raise ValueError("--history_dtype must be one of %s, got %r" % ('/'.join(_CHOICES['history_dtype']), hd))
+    return True, hd == 'bf16'
+
+
 def partition(adj, P, seed=1):
     """The vertices of ``adj`` cut into P parts, as P ascending int32 id arrays; deterministic in (adj, P, seed).
 
@@ -882,7 +921,10 @@ class PulledMatrix(InducedMatrix):
     layer.  ``pull_product(x, l)`` is the neighbour sum of layer l over EVERY stored entry of the rows of S (ops.spmm_pull:
     fresh rows of ``x`` for columns in S, rows of table l for the others); ``push(x, l)`` then stores the layer's input rows
     into table l (ops.scatter_rows) -- columns in S never read the table, so push-after-pull is safe.  A table that is not
-    ``owned`` (the resident feature table under an aggregation layer with no layer in front of it) is exact and never written."""
+    ``owned`` (the resident feature table under an aggregation layer with no layer in front of it) is exact and never written.
+    ``pull_attn_product`` / ``pull_attn_backward`` are the attention over the same entries (--full_batch_part_pull).  The pull
+    launches take their operands as they are: nothing is staged, so a table too wide for its alignment (602 columns on a pitch
+    of 602 floats) is refused with the kernels' width message."""
 
     def __init__(self, block, resident, ids_dev, tables, owned, device=None):
         if getattr(block, 'map', None) is None:
@@ -896,6 +938,27 @@ class PulledMatrix(InducedMatrix):
 
     def pull_product(self, x, l, out=None):
         return ops.spmm_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], out=out)
+
+    def pull_attn_product(self, x, l, scale, out=None, want_lse=True, heads=1):
+        """(out, lse) of layer l's attention over EVERY stored entry of the rows of S (ops.spattn_pull): the queries are the
+        rows of ``x``, a key / value row is the fresh row of ``x`` for a column in S and the row of table l for the others.
+        ``out`` may be a pitched view (the neighbour half of a concatenated output).  --full_batch_part_pull."""
+        if x.dtype != torch.float32:
+            raise ValueError("attention has no bfloat16-operand form")
+        return ops.spattn_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], scale, out=out, want_lse=want_lse,
+                               heads=heads)
+
+    def pull_attn_backward(self, x, l, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1):
+        """dx, the gradient of ``pull_attn_product(x, l, scale)`` with respect to ``x`` for g = dL/dout (+ add on the first
+        ``add_rows`` rows): the query's half over all stored entries (ops.spattn_pull_bwd_q; stored rows are constants, but
+        the query's gradient sees them), then the keys' / values' half through in-part entries only -- the block's one-table
+        bwd_kv over A[S, S]^T with the full rows' lse and delta and dq as its addend (ops.spattn_pull_bwd_kv).  Called
+        after ``push(x, l)``: the backward re-reads only rows outside S, which the step leaves untouched."""
+        if x.dtype != torch.float32:
+            raise ValueError("attention has no bfloat16-operand form")
+        dq, delta = ops.spattn_pull_bwd_q(self.resident, self.ids_dev, self.map, x, self.tables[l], g, out_fwd, lse, scale,
+                                          add=add, add_rows=add_rows, heads=heads)
+        return ops.spattn_pull_bwd_kv(self.transpose.rows_csr, x, g, lse, delta, dq, scale, heads=heads)
 
     def push(self, x, l):
         if self.owned[l]:

@@ -468,12 +468,27 @@ class PlainAggregator(Layer):
                                             **self._drop)
                 self._out, self._lse, self._S = res, lse, (S if want else None)
                 return out if concat else res
+            # --full_batch_part_pull: the step's matrix (full_batch.PulledMatrix) attends over EVERY stored entry of its rows --
+            # fresh rows of x for columns inside the step's vertex set, this layer's stored rows for the others -- and the
+            # layer then pushes its input rows (push-after-pull is safe: columns inside the set never read the table, and the
+            # backward re-reads only rows outside it)
+            self._pull = hasattr(A, 'pull_attn_product')
+            if self._pull and self._drop:
+                raise RuntimeError("--attn_dropout has no two-table form: the mask of out-of-part entries is not defined")
             if not concat:
-                self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads, **self._drop)
+                if self._pull:
+                    self._out, self._lse = A.pull_attn_product(x, self.l, scale, want_lse=want, heads=heads)
+                    A.push(x, self.l)
+                else:
+                    self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads, **self._drop)
                 return self._out
             out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
             out[:, :d] = x[:n1]
-            self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads, **self._drop)
+            if self._pull:
+                self._out, self._lse = A.pull_attn_product(x, self.l, scale, out=out[:, d:], want_lse=want, heads=heads)
+                A.push(x, self.l)
+            else:
+                self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads, **self._drop)
             return out
         # --full_batch_part_history: the step's matrix (full_batch.PulledMatrix) sums over EVERY stored entry of its rows --
         # fresh rows of x for columns inside the step's vertex set, this layer's stored rows for the others -- and the layer
@@ -525,6 +540,12 @@ class PlainAggregator(Layer):
             return dx
         if self._attn:
             # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
+            if self._pull:
+                # --full_batch_part_pull: dQ over every stored entry, dB through the in-part block with dQ as its addend
+                if not self._concat:
+                    return A.pull_attn_backward(self._x, self.l, g, self._out, self._lse, self._scale, heads=self._heads)
+                return A.pull_attn_backward(self._x, self.l, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d],
+                                            add_rows=A.shape[0], heads=self._heads)
             if not self._concat:
                 return A.attn_backward(self._x, g, self._out, self._lse, self._scale, heads=self._heads, **self._drop)
             return A.attn_backward(self._x, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d], add_rows=A.shape[0],

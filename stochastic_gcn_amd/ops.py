@@ -487,19 +487,31 @@ def spattn_bwd(A, At, x, q, g, out_fwd, lse, scale, add=None, add_rows=0, heads=
         A, x, heads, queries, bwd=(g, out_fwd, lse, add, add_rows), vector_lse=True)
     delta = torch.empty((M * heads,), dtype=torch.float32, device=x.device)
     dq = _attn_out(M, d, x.device, heads)
-    dx = _attn_out(K, d, x.device, heads)
     plan = A.plan.struct(attn_slot('bwd', d)) if A.plan is not None else None
-    tplan = At.plan.struct(attn_slot('bwd', d)) if At.plan is not None else None
     fused = q is None
     key = int(key) & 0xFFFFFFFF
     check(lib.sgcn_spattn_drop_csr_bwd_q_f32(A.rowptr.data_ptr(), _ptr(A.col), M, K, d, heads, keep, key, qptr, ldq, bptr, ldb,
                                              float(scale), gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(),
                                              dq.data_ptr(), _rows2d(dq, "dq")[1], aptr, ldadd, add_rows, _byref(plan), _stream()))
-    check(lib.sgcn_spattn_drop_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, qptr, ldq, bptr,
-                                              ldb, float(scale), gptr, ldg, lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
+    dx = _spattn_bwd_kv(At, d, heads, keep, key, (qptr, ldq), (bptr, ldb), scale, (gptr, ldg), lse, delta, x.device,
+                        dq if fused else None)
+    return (None if fused else dq), dx
+
+
+def _spattn_bwd_kv(At, d, heads, keep, key, q, b, scale, g, lse, delta, device, dq):
+    """dx (K x d): the keys' / values' half of the attention backward -- sgcn_spattn_drop_csr_bwd_kv_f32 over ``At`` (K x M, the
+    TRANSPOSED pattern) with the (ptr, pitch) pairs ``q``, ``b``, ``g`` and the rows' ``lse`` and ``delta``; ``dq`` (M x d, or
+    None) is added to its first M rows in the launch's epilogue.  The second half of ``spattn_bwd``, and of
+    ``full_batch.PulledMatrix.pull_attn_backward``, whose lse and delta come from the two-table launches."""
+    K, M = At.shape
+    dx = _attn_out(K, d, device, heads)
+    tplan = At.plan.struct(attn_slot('bwd', d)) if At.plan is not None else None
+    fused = dq is not None
+    check(lib.sgcn_spattn_drop_csr_bwd_kv_f32(At.rowptr.data_ptr(), _ptr(At.col), K, M, d, heads, keep, key, q[0], q[1], b[0],
+                                              b[1], float(scale), g[0], g[1], lse.data_ptr(), delta.data_ptr(), dx.data_ptr(),
                                               _rows2d(dx, "dx")[1], dq.data_ptr() if fused else None,
                                               _rows2d(dq, "dq")[1] if fused else 0, M if fused else 0, _byref(tplan), _stream()))
-    return (None if fused else dq), dx
+    return dx
 
 
 GAT_RED_ROWS = 64            # sgcn_gat_scores_bwd_f32: rows per partial sum of da
@@ -1048,6 +1060,98 @@ def spmm_pull(A, ids_dev, map_dev, x, H, out=None):
         A.rowptr.data_ptr(), _ptr(A.col), _ptr(A.val), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, xptr, ldx, hptr, ldh,
         cptr, ldc, _stream()))
     return out
+
+
+def _pull_operands(who, A, ids_dev, map_dev, x, H, heads):
+    """The checks ``spattn_pull`` and ``spattn_pull_bwd_q`` share -- ``spmm_pull``'s on the matrix, the ids, the map and the
+    two tables, then the heads.  Returns n, N, d, heads, x's (ptr, pitch) and H's (ptr, pitch, h16)."""
+    check_unique_cols(A)
+    N = int(A.shape[0])
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("%s needs a square (vertex x vertex) matrix" % who)
+    _dev(ids_dev, torch.int32, "ids_dev")
+    _dev(map_dev, torch.int32, "map_dev")
+    n = int(ids_dev.shape[0])
+    xp = _rows2d(x, "x")
+    hp = _hist2d(H, "H")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    if int(x.shape[0]) != n:
+        raise ValueError("x has %d rows, ids_dev %d entries" % (int(x.shape[0]), n))
+    if int(H.shape[0]) < N or int(H.shape[1]) != d:
+        raise ValueError("H has shape %s, need (>=%d, %d)" % (tuple(H.shape), N, d))
+    if int(map_dev.shape[0]) < N:
+        raise ValueError("map_dev has %d words, the matrix %d vertices" % (int(map_dev.shape[0]), N))
+    return n, N, d, heads, xp, hp
+
+
+def spattn_pull(A, ids_dev, map_dev, x, H, scale, out=None, want_lse=True, heads=1):
+    """(out, lse): softmax dot-product attention of the n selected rows ``ids_dev`` of the RESIDENT square DeviceCSR ``A`` over
+    EVERY stored entry e of row ids[i], the entry's key / value row being x[map[col[e]]] if map[col[e]] >= 0 else H[col[e]]
+    and the query x[i]   (sgcn_spattn_pull_f32 / _h16; --full_batch_part_pull with --aggregator attn).
+
+    ``ids_dev``, ``map_dev``, ``x`` (n x d fp32, the rows the step computes) and ``H`` (N x d: fp32, or a bfloat16 table of
+    ``history_alloc(..., bf16=True)``'s layout, widened exactly) as in ``spmm_pull``; ``scale``, ``out`` (may be a pitched
+    (n, >= d) view), ``want_lse`` and ``heads`` as in ``spattn``: lse is (n,) for heads == 1, else (n, heads).  ``A`` is read
+    in place: no cut, no plan, no synchronisation; one lane group per selected row, however long.  The result has the bits
+    of ``spattn`` without a plan on the rows ``ids`` of ``A`` and the merged table (H with the rows ids replaced by x)."""
+    n, N, d, heads, (xptr, ldx), (hptr, ldh, h16) = _pull_operands("spattn_pull", A, ids_dev, map_dev, x, H, heads)
+    if out is None:
+        out = _attn_out(n, d, x.device, heads)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != n or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), n, d))
+    lse = torch.empty((n,) if heads == 1 else (n, heads), dtype=torch.float32, device=x.device) if want_lse else None
+    check((lib.sgcn_spattn_pull_h16 if h16 else lib.sgcn_spattn_pull_f32)(
+        A.rowptr.data_ptr(), _ptr(A.col), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, heads, xptr, ldx, hptr, ldh,
+        float(scale), cptr, ldc, _ptr(lse), _stream()))
+    return out, lse
+
+
+def spattn_pull_bwd_q(A, ids_dev, map_dev, x, H, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1):
+    """(dq, delta): the query's half of the gradient of ``spattn_pull`` for g = dL/dout, from the forward's ``out_fwd`` and
+    ``lse`` -- sgcn_spattn_pull_bwd_q_f32 / _h16: delta[i, h] = <g[i], out_fwd[i]>_h and dq[i] = scale * sum_e e_e B_e over ALL
+    stored entries of row ids[i] (+ add[i] on the first ``add_rows`` rows).  delta is (n * heads,) floats, row-major (n, heads):
+    what the keys' / values' half (sgcn_spattn_*_bwd_kv over the transposed induced block) reads.  Stored rows are constants:
+    nothing flows into ``H``."""
+    n, N, d, heads, (xptr, ldx), (hptr, ldh, h16) = _pull_operands("spattn_pull_bwd_q", A, ids_dev, map_dev, x, H, heads)
+    gptr, ldg = _rows2d(g, "g")
+    cptr, ldc = _rows2d(out_fwd, "out_fwd")
+    if tuple(g.shape) != (n, d) or out_fwd.shape[0] != n or out_fwd.shape[1] < d:
+        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (n, d, tuple(g.shape), tuple(out_fwd.shape)))
+    _dev(lse, torch.float32, "lse")
+    if tuple(lse.shape) != ((n,) if heads == 1 else (n, heads)) or not lse.is_contiguous():
+        raise ValueError("lse must be what spattn_pull returned: contiguous, (%d,) at one head, else (%d, %d)" % (n, n, heads))
+    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
+    add_rows = int(add_rows) if add is not None else 0
+    delta = torch.empty((n * heads,), dtype=torch.float32, device=x.device)
+    dq = _attn_out(n, d, x.device, heads)
+    check((lib.sgcn_spattn_pull_bwd_q_h16 if h16 else lib.sgcn_spattn_pull_bwd_q_f32)(
+        A.rowptr.data_ptr(), _ptr(A.col), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, heads, xptr, ldx, hptr, ldh,
+        float(scale), gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), _rows2d(dq, "dq")[1], aptr, ldadd,
+        add_rows, _stream()))
+    return dq, delta
+
+
+def spattn_pull_bwd_kv(At, x, g, lse, delta, dq, scale, heads=1):
+    """dx = dB + dq: the keys' / values' half of ``spattn_pull``'s gradient, through in-part entries only -- the one-table
+    sgcn_spattn_*_bwd_kv over ``At``, the transposed induced block A[S, S]^T (n x n), with queries = keys = ``x`` and the
+    ``lse`` / ``delta`` of the two pull launches (the coefficients it recomputes are those of the FULL row); ``dq`` is the
+    launch's addend."""
+    n = int(At.shape[0])
+    if tuple(At.shape) != (n, n) or int(x.shape[0]) != n:
+        raise ValueError("At must be the square transposed block over the %d rows of x, got %s" % (int(x.shape[0]), tuple(At.shape)))
+    b = _rows2d(x, "x")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    gp = _rows2d(g, "g")
+    if tuple(g.shape) != (n, d) or tuple(dq.shape) != (n, d):
+        raise ValueError("g and dq must be (%d, %d), got %s and %s" % (n, d, tuple(g.shape), tuple(dq.shape)))
+    _dev(lse, torch.float32, "lse")
+    _dev(delta, torch.float32, "delta")
+    if lse.numel() != n * heads or delta.numel() != n * heads or not lse.is_contiguous() or not delta.is_contiguous():
+        raise ValueError("lse and delta must hold %d x %d contiguous floats" % (n, heads))
+    return _spattn_bwd_kv(At, d, heads, 1.0, 0, b, b, scale, gp, lse, delta, x.device, dq)
 
 
 def adam_step(theta, grad, m, v, lr_t, beta1, beta2, eps=1e-8):

@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
 from .full_batch import (InducedMatrix, PartBatch, PartSchedule, PulledMatrix, check_full_batch_parts, check_part_history,
-                         part_stats, partition,
+                         check_part_pull, part_stats, partition,
                          StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
@@ -240,6 +240,11 @@ class Trainer(object):
         self.parts, self.parts_per_step, self.part_norm = check_full_batch_parts()
         # (--full_batch_part_history without parts, with --aggregator max / attn, --reverse or a bfloat16 operand: too)
         self.part_history, self.part_history_bf16 = check_part_history()
+        # (--full_batch_part_pull without parts, with --aggregator max, --attn_score gat, --attn_dropout, --reverse or a bfloat16
+        # operand: too.  Either flag turns the part-history machinery on; with both, check_part_history has spoken first)
+        self.part_pull, pull_bf16 = check_part_pull()
+        if self.part_pull:
+            self.part_history, self.part_history_bf16 = True, self.part_history_bf16 or pull_bf16
         # (--aggregator max without both full-graph modes, with a bfloat16 table or an edge mask: too)
         self.max_aggregator = check_aggregator()
         # (--aggregator attn likewise; --attn_scale negative, non-finite, or set without attn: too)
@@ -456,10 +461,14 @@ class Trainer(object):
             # out-of-part neighbours read stored rows: one table per aggregation layer, on the training model
             nbytes = self.train_model.alloc_part_history(self.part_history_bf16)
             tables, owned = self.train_model.part_history
-            self.log('[sgcn] --full_batch_part_history: a step sums over every stored entry of its rows -- fresh rows inside its '
+            what = '--full_batch_part_history: a step sums over'
+            if self.part_pull:
+                what = '--full_batch_part_pull (--aggregator {}): a step {} over'.format(
+                    FLAGS.aggregator, 'attends' if FLAGS.aggregator == 'attn' else 'sums')
+            self.log('[sgcn] {} every stored entry of its rows -- fresh rows inside its '
                      'vertex set, stored rows outside (nothing dropped, nothing rescaled) | {} table(s) of {} rows, {}: {:.1f} '
                      'MiB, zero-filled{} | a group without a training vertex runs the forward only and pushes its rows'.format(
-                         sum(owned), N, 'bf16' if self.part_history_bf16 else 'fp32', nbytes / 2.0 ** 20,
+                         what, sum(owned), N, 'bf16' if self.part_history_bf16 else 'fp32', nbytes / 2.0 ** 20,
                          '' if all(owned) else '; the first aggregation layer reads the resident feature table'))
 
     def part_batch(self, ids):
