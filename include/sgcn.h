@@ -889,6 +889,58 @@ int sgcn_spattn_pull_bwd_q_h16(const int32_t* dev_rowptr, const int32_t* dev_col
                                const uint16_t* dev_H, int64_t ldh, float scale, const float* dev_G, int64_t ldg,
                                const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dQ,
                                int64_t lddq, const float* dev_add, int64_t ldadd, int32_t add_rows, void* stream);
+/* Two-table attention with learned additive scores (GAT) of a part step that keeps its out-of-part entries
+ * (--full_batch_part_pull_gat; sgcn_spgat_pull.hip).  The setting, X and H are those of sgcn_spattn_pull_*; U and V (n x heads,
+ * pitches ldu, ldv) are the fresh score tables of sgcn_gat_scores_f32 on X, and VH (N x heads, fp32, pitch ldvh) holds the
+ * last-seen destination score of every vertex.  For a stored entry e of row ids[i], with c = col[e] and m = map[c], per head h:
+ *
+ *   B_e = m >= 0 ? X[m] : H[c]          v_e = m >= 0 ? V[m, h] : VH[c, h]
+ *   z_e = U[i, h] + v_e  (ONE fp32 addition),   s_e = z_e > 0 ? z_e : slope z_e,
+ *   lse[i, h] = log sum_e exp(s_e),   C[i]^h = sum_e exp(s_e - lse[i, h]) B_e^h
+ *
+ * The stale score is STORED, never recomputed from H[c].  Everything else is sgcn_spgat_csr_f32's definition without a mask:
+ * online softmax, true division acc / l, lse = m + log l in fp64 rounded once, an empty row gives +0.0 and -inf, a chunk's
+ * pads have weight exactly 0.  lse is n x heads, nullable.  One lane group owns one selected row: no plan, no split rows, no
+ * workspace, and a launch gives, bit for bit, what sgcn_spgat_csr_f32 without a plan gives on (the rows ids of the CSR,
+ * B = H with the rows of S replaced by X, U, V = VH with the rows of S replaced by V).  Rows of H and VH inside S are never
+ * read.  No atomics, nothing nnz-sized is written: the same bits on every run.  _h16 gives the bits of _f32 on the widened
+ * table.  The vector width is the widest that X, H (_f32), C and the three pitches allow and that divides d / heads;
+ * d <= 256 * VW.  SGCN_ERR_INVALID, before any HIP call and with nothing written, for a negative size, n > N, d <= 0, heads
+ * outside 1/2/4/8 or not dividing d, a slope outside [0, 1] or not finite, a pitch below d (ldx, ldh, ldc) or below heads
+ * (ldu, ldv, ldvh), a null operand with n > 0, a width over the limit, a malformed bfloat16 table; n == 0 returns SGCN_OK
+ * without a launch. */
+int sgcn_spgat_pull_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                        const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx, const float* dev_H,
+                        int64_t ldh, const float* dev_U, int64_t ldu, const float* dev_V, int64_t ldv, const float* dev_VH,
+                        int64_t ldvh, float slope, float* dev_C, int64_t ldc, float* dev_lse, void* stream);
+int sgcn_spgat_pull_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                        const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx, const uint16_t* dev_H,
+                        int64_t ldh, const float* dev_U, int64_t ldu, const float* dev_V, int64_t ldv, const float* dev_VH,
+                        int64_t ldvh, float slope, float* dev_C, int64_t ldc, float* dev_lse, void* stream);
+/* The source score's half of that attention's backward, for G = dL/dC (n x d) with the forward's C and lse:
+ *
+ *   delta[i, h] = <G[i], C[i]>_h,   e_e = exp(s_e - lse[i, h]) (<G[i], B_e>_h - delta[i, h]),
+ *   dU[i, h] = sum_e e_e (z_e > 0 ? 1 : slope)
+ *
+ * over ALL stored entries of row ids[i]: stored rows and scores are constants, but the source score's gradient sees them.
+ * delta and dU (out) are n x heads, contiguous; delta and t = <G[i], B_e> go through one reduction tree in one per-lane
+ * order.  The gradient to values and destination scores flows through in-part entries only: sgcn_spgat_csr_bwd_v_f32 over
+ * the transposed induced block A[S, S]^T with U, V, B = X, G, this lse and delta gives dB and dV (n x heads), and
+ * sgcn_gat_scores_bwd_f32 takes dU and dV on to X and a -- so da[0] sees every stored entry and da[1] in-part entries only.
+ * Geometry, restrictions, reproducibility and the bit identity with sgcn_spgat_csr_bwd_u_f32 on the merged tables as above;
+ * the vector width also looks at G, C and their pitches.  SGCN_ERR_INVALID as above (ldg and ldc count as pitches of d). */
+int sgcn_spgat_pull_bwd_u_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                              const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx,
+                              const float* dev_H, int64_t ldh, const float* dev_U, int64_t ldu, const float* dev_V, int64_t ldv,
+                              const float* dev_VH, int64_t ldvh, float slope, const float* dev_G, int64_t ldg,
+                              const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dU,
+                              void* stream);
+int sgcn_spgat_pull_bwd_u_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                              const int32_t* dev_map, int32_t d, int32_t heads, const float* dev_X, int64_t ldx,
+                              const uint16_t* dev_H, int64_t ldh, const float* dev_U, int64_t ldu, const float* dev_V,
+                              int64_t ldv, const float* dev_VH, int64_t ldvh, float slope, const float* dev_G, int64_t ldg,
+                              const float* dev_C, int64_t ldc, const float* dev_lse, float* dev_delta, float* dev_dU,
+                              void* stream);
 /* out[i] = src[idx[i]] */
 int sgcn_gather_f32(const float* dev_src, const int32_t* dev_idx, int64_t n, float* dev_out, void* stream);
 

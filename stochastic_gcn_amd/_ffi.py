@@ -294,6 +294,16 @@ SIGNATURES = {
     "sgcn_spattn_pull_bwd_q_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
                                              C.c_float, P, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int32,
                                              P]),
+    "sgcn_spgat_pull_f32": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                      P, C.c_int64, P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, P]),
+    "sgcn_spgat_pull_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                      P, C.c_int64, P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, P]),
+    "sgcn_spgat_pull_bwd_u_f32": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                            P, C.c_int64, P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, C.c_int64,
+                                            P, P, P, P]),
+    "sgcn_spgat_pull_bwd_u_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int64, P, C.c_int64,
+                                            P, C.c_int64, P, C.c_int64, P, C.c_int64, C.c_float, P, C.c_int64, P, C.c_int64,
+                                            P, P, P, P]),
     "sgcn_step_run": (C.c_int, [C.POINTER(StepOp), C.c_int32, P, C.c_int32, P]),
     "sgcn_step_fill": (C.c_int, [C.POINTER(StepFill), P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                                  P, C.c_int64]),

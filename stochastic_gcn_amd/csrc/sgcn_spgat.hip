@@ -16,36 +16,13 @@
 // delta and t go through the SAME reduction tree in the same per-lane order, so where C[i] holds the bits of one B[j] (a
 // saturated softmax) t - delta is exactly 0 for it.  Nothing nnz-sized is written and there are no atomics.
 // The host side is sgcn_attn_dev.h's as well: slot widths, opening checks, lane geometry and fix-up step (attn_run), over the
-// plan checks and the ladders of sgcn_seg.h; this file adds the launcher that names its kernels (Gat), slope_ok and each export's own operand checks.
+// plan checks and the ladders of sgcn_seg.h; this file adds the launcher that names its kernels (Gat) and each export's own operand checks
+// (GatX, the LeakyReLU and slope_ok: sgcn_gat_dev.h, shared with sgcn_spgat_pull.hip).
 #include <cmath>
-#include "sgcn_attn_dev.h"
+#include "sgcn_gat_dev.h"
 
 namespace sgcn {
 namespace {
-
-// the score tables and the score gradients, a second kernel argument (AttnArgs keeps its layout); the mask is the third
-struct GatX {
-    const float* U;          // u: element [i * ldu + h], i a row of P
-    int64_t ldu;
-    const float* V;          // v: element [j * ldv + h], j a column of P
-    int64_t ldv;
-    float slope;
-    float* dU;               // bwd_u: M x H, contiguous
-    float* dV;               // bwd_v: K x H, contiguous
-};
-
-__device__ __forceinline__ float leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
-__device__ __forceinline__ float leaky_d(float z, float slope) { return z > 0.f ? 1.f : slope; }
-
-template <int G, bool MH>
-__device__ __forceinline__ float head_total(float v, int gh) {
-    float s[1] = {v};
-    if constexpr (MH) head_sum<G, 1>(s, gh); else group_sum<G, 1>(s);
-    return s[0];
-}
-
-template <int NV>
-struct GatUnroll { static constexpr int fwd = 4, bwd = NV >= 3 ? 2 : 4; };
 
 // ---- forward ------------------------------------------------------------------------------------------------------------
 template <int G, int NV, int VW, bool MH, bool DR>
@@ -452,11 +429,6 @@ struct Gat {
         }
     }
 };
-
-int slope_ok(const char* who, float slope) {
-    SGCN_REQUIRE(std::isfinite(slope) && slope >= 0.f && slope <= 1.f, "%s: slope must lie in [0, 1] (got %g)", who, (double)slope);
-    return SGCN_OK;
-}
 
 }  // namespace
 }  // namespace sgcn

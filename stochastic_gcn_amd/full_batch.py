@@ -835,6 +835,39 @@ def check_part_pull(flags=None):
     return True, hd == 'bf16'
 
 
+def check_part_pull_gat(flags=None):
+    """(on, bf16) of --full_batch_part_pull_gat / --history_dtype: part steps of the attention aggregator with learned
+    additive scores (--attn_score gat) that read stored rows AND stored destination scores for their out-of-part
+    neighbours (ops.spgat_pull).  What the two-table kernels have no form or no meaning for is refused.  Needs no device;
+    called beside check_part_pull, which keeps its own contract and, with both flags on, speaks first."""
+    f = FLAGS if flags is None else flags
+    if not bool(getattr(f, 'full_batch_part_pull_gat', False)):
+        return False, False
+    if int(getattr(f, 'full_batch_parts', 0) or 0) <= 0:
+        raise ValueError("--full_batch_part_pull_gat needs --full_batch_parts > 0: it is the estimator of a part step's "
+                         "out-of-part neighbours, and no other mode has them")
+    agg = getattr(f, 'aggregator', 'sum')
+    if agg != 'attn':
+        raise ValueError("--full_batch_part_pull_gat needs --aggregator attn (got %s): it is the two-table form of the "
+                         "attention with learned scores; --full_batch_part_pull serves the sum" % agg)
+    if getattr(f, 'attn_score', 'dot') != 'gat':
+        raise ValueError("--full_batch_part_pull_gat needs --attn_score gat: --full_batch_part_pull is the two-table form "
+                         "of dot-product attention")
+    if float(getattr(f, 'attn_dropout', 0.0) or 0.0) > 0:
+        raise ValueError("--full_batch_part_pull_gat is not supported with --attn_dropout > 0: in this version the mask of "
+                         "out-of-part entries is not defined")
+    if getattr(f, 'reverse', False):
+        raise ValueError("--full_batch_part_pull_gat is not supported with --reverse: the aggregator's input would be a "
+                         "dropout-masked table, and the stored rows and scores would hold one step's mask")
+    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
+        raise ValueError("--full_batch_part_pull_gat is not supported with --full_batch_dtype bf16: the pull kernels' fresh "
+                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)")
+    hd = getattr(f, 'history_dtype', 'fp32')
+    if hd not in _CHOICES['history_dtype']:
+        raise ValueError("--history_dtype must be one of %s, got %r" % ('/'.join(_CHOICES['history_dtype']), hd))
+    return True, hd == 'bf16'
+
+
 def partition(adj, P, seed=1):
     """The vertices of ``adj`` cut into P parts, as P ascending int32 id arrays; deterministic in (adj, P, seed).
 
@@ -926,7 +959,7 @@ class PulledMatrix(InducedMatrix):
     launches take their operands as they are: nothing is staged, so a table too wide for its alignment (602 columns on a pitch
     of 602 floats) is refused with the kernels' width message."""
 
-    def __init__(self, block, resident, ids_dev, tables, owned, device=None):
+    def __init__(self, block, resident, ids_dev, tables, owned, device=None, scores=None):
         if getattr(block, 'map', None) is None:
             raise ValueError("a PulledMatrix needs the block's position map (ops.csr_induce)")
         super(PulledMatrix, self).__init__(block, device, bf16=False)
@@ -935,6 +968,10 @@ class PulledMatrix(InducedMatrix):
         if len(tables) != len(owned):
             raise ValueError("a PulledMatrix needs one owned flag per history table")
         self.resident, self.ids_dev, self.map, self.tables, self.owned = resident, ids_dev, block.map, list(tables), list(owned)
+        # --full_batch_part_pull_gat: one N x H fp32 table of last-seen destination scores per aggregation layer, always owned
+        if scores is not None and len(scores) != len(tables):
+            raise ValueError("a PulledMatrix needs one score table per history table")
+        self.scores = None if scores is None else list(scores)
 
     def pull_product(self, x, l, out=None):
         return ops.spmm_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], out=out)
@@ -963,6 +1000,46 @@ class PulledMatrix(InducedMatrix):
     def push(self, x, l):
         if self.owned[l]:
             ops.scatter_rows(self.tables[l], self.ids_dev, x)
+
+    def _score_table(self, l):
+        if self.scores is None:
+            raise RuntimeError("this PulledMatrix carries no score tables (--full_batch_part_pull_gat allocates them)")
+        return self.scores[l]
+
+    def pull_gat_product(self, x, a, l, slope, out=None, want_lse=True, heads=1):
+        """(out, lse, S) of layer l's attention with learned scores over EVERY stored entry of the rows of S
+        (ops.gat_scores + ops.spgat_pull): S = the fresh score table of ``x`` under the layer's vectors ``a`` (2, d); a
+        value row and its destination score are the fresh ones for a column in S, and those of row table l and score
+        table l for the others.  ``out`` may be a pitched view.  lse (n, H) and S are what ``pull_gat_backward`` needs."""
+        if x.dtype != torch.float32:
+            raise ValueError("attention has no bfloat16-operand form")
+        H = int(heads)
+        S = ops.gat_scores(x, a, heads=H)
+        res, lse = ops.spgat_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], S[:, :H], S[:, H:], self._score_table(l),
+                                  slope, out=out, want_lse=want_lse, heads=H)
+        return res, lse, S
+
+    def pull_gat_backward(self, x, a, S, l, g, out_fwd, lse, slope, add=None, add_rows=0, heads=1, need_dx=True):
+        """(dX or None, da) of ``pull_gat_product(x, a, l, slope)`` for g = dL/dout (+ add on dX's first ``add_rows`` rows):
+        dU over all stored entries (ops.spgat_pull_bwd_u; stored rows and scores are constants, but the source score's
+        gradient sees them), then dB and dV through in-part entries only -- the block's one-table bwd_v over A[S, S]^T with
+        the full rows' lse and delta (ops.spgat_pull_bwd_v) -- then ops.gat_scores_bwd: da[0] sees every stored entry,
+        da[1] in-part entries only.  Called after ``push`` / ``push_scores``: the backward re-reads only rows outside S."""
+        if x.dtype != torch.float32:
+            raise ValueError("attention has no bfloat16-operand form")
+        H = int(heads)
+        U, V = S[:, :H], S[:, H:]
+        dU, delta = ops.spgat_pull_bwd_u(self.resident, self.ids_dev, self.map, x, self.tables[l], U, V, self._score_table(l), g,
+                                         out_fwd, lse, slope, heads=H)
+        dB, dV = ops.spgat_pull_bwd_v(self.transpose.rows_csr, x, U, V, g, lse, delta, slope, add=add if need_dx else None,
+                                      add_rows=add_rows if need_dx else 0, heads=H)
+        da = ops.gat_scores_bwd(x, a, dU, dV, dx=dB if need_dx else None, heads=H)
+        return (dB if need_dx else None), da
+
+    def push_scores(self, S, l):
+        """store the destination half of the fresh score table ``S`` (n, 2 H) into score table l at the rows of S"""
+        T = self._score_table(l)
+        ops.scatter_rows(T, self.ids_dev, S[:, int(T.shape[1]):])
 
     def describe(self, d):
         return dict(plan_from_cache=False, pace=None, kernel="sgcn::spmm_pull_kernel", products=self.products)

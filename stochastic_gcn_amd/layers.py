@@ -464,8 +464,21 @@ class PlainAggregator(Layer):
                 if concat:
                     out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
                     out[:, :d] = x[:n1]
-                res, lse, S = A.gat_product(x, a, slope, out=out[:, d:] if concat else None, want_lse=want, heads=heads,
-                                            **self._drop)
+                # --full_batch_part_pull_gat: the step's matrix (full_batch.PulledMatrix with score tables) attends over EVERY
+                # stored entry of its rows -- fresh rows and scores for columns inside the step's vertex set, this layer's
+                # stored rows and stored destination scores for the others -- and the layer then pushes its input rows and
+                # its destination scores (push-after-pull is safe: columns inside the set never read either table)
+                self._pull = hasattr(A, 'pull_gat_product') and getattr(A, 'scores', None) is not None
+                if self._pull:
+                    if self._drop:
+                        raise RuntimeError("--attn_dropout has no two-table form: the mask of out-of-part entries is not defined")
+                    res, lse, S = A.pull_gat_product(x, a, self.l, slope, out=out[:, d:] if concat else None, want_lse=want,
+                                                     heads=heads)
+                    A.push(x, self.l)
+                    A.push_scores(S, self.l)
+                else:
+                    res, lse, S = A.gat_product(x, a, slope, out=out[:, d:] if concat else None, want_lse=want, heads=heads,
+                                                **self._drop)
                 self._out, self._lse, self._S = res, lse, (S if want else None)
                 return out if concat else res
             # --full_batch_part_pull: the step's matrix (full_batch.PulledMatrix) attends over EVERY stored entry of its rows --
@@ -531,7 +544,14 @@ class PlainAggregator(Layer):
             # and attn_vec's gradient; as the model's first parametrised layer (--nopreprocess) nothing consumes dX
             a = self.vars['attn_vec']
             kw = dict(heads=self._heads, need_dx=self.need_dx, **self._drop)
-            if not self._concat:
+            if self._pull:
+                # --full_batch_part_pull_gat: dU over every stored entry, dB and dV through the in-part block
+                if not self._concat:
+                    dx, da = A.pull_gat_backward(self._x, a, self._S, self.l, g, self._out, self._lse, self._slope, **kw)
+                else:
+                    dx, da = A.pull_gat_backward(self._x, a, self._S, self.l, g[:, d:], self._out, self._lse, self._slope,
+                                                 add=g[:, :d], add_rows=A.shape[0], **kw)
+            elif not self._concat:
                 dx, da = A.gat_backward(self._x, a, self._S, g, self._out, self._lse, self._slope, **kw)
             else:
                 dx, da = A.gat_backward(self._x, a, self._S, g[:, d:], self._out, self._lse, self._slope, add=g[:, :d],

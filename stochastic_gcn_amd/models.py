@@ -413,6 +413,16 @@ class GCN(Model):
         self.part_history = (tables, owned)
         return nbytes
 
+    # --full_batch_part_pull_gat: the last-seen destination scores of every vertex, one N x H fp32 table per aggregation layer.
+    # None without the flag.  Always owned -- layer 0 under --nopreprocess too: its rows are exact, its scores are not.
+    part_scores = None
+
+    def alloc_part_scores(self, heads):
+        """Allocates ``part_scores`` and returns the bytes it took: per aggregation layer one zero-filled N x heads fp32 table."""
+        self.part_scores = [torch.zeros((int(self.num_data), int(heads)), dtype=torch.float32, device=self.device)
+                            for _ in range(self.L)]
+        return self.L * int(self.num_data) * int(heads) * 4
+
     def _build_aggregators(self):
         pass
 
@@ -1098,6 +1108,11 @@ class GCN(Model):
             self.forward(cur, stop=last)
             if feed_dict.matrix.owned[self.L - 1]:
                 feed_dict.matrix.push(dense_of(self.activations[-1]), self.L - 1)
+            if getattr(feed_dict.matrix, 'scores', None) is not None:
+                # --full_batch_part_pull_gat: the last layer's destination scores as well (the layers in front pushed theirs)
+                x = dense_of(self.activations[-1])
+                S = ops.gat_scores(x, self.layers[last].vars['attn_vec'], heads=int(getattr(FLAGS, 'attn_heads', 1)))
+                feed_dict.matrix.push_scores(S, self.L - 1)
         finally:
             ops.unpin_stream()
         self.dropout_step += 1

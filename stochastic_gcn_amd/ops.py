@@ -1154,6 +1154,94 @@ def spattn_pull_bwd_kv(At, x, g, lse, delta, dq, scale, heads=1):
     return _spattn_bwd_kv(At, d, heads, 1.0, 0, b, b, scale, gp, lse, delta, x.device, dq)
 
 
+def _gat_pull_operands(who, A, ids_dev, map_dev, x, H, u, v, vh, slope, heads):
+    """``_pull_operands``, then the slope and the three score tables: u, v (n, heads) fresh, vh (>= N, heads) stored.  Returns
+    what ``_pull_operands`` does, the slope, and the (ptr, pitch) pairs of u, v and vh as one flat tuple."""
+    n, N, d, heads, xp, hp = _pull_operands(who, A, ids_dev, map_dev, x, H, heads)
+    slope = _attn_slope(slope)
+    tabs = _gat_table(u, n, heads, "u") + _gat_table(v, n, heads, "v") + _gat_table(vh, N, heads, "vh")
+    return n, N, d, heads, xp, hp, slope, tabs
+
+
+def spgat_pull(A, ids_dev, map_dev, x, H, u, v, vh, slope, out=None, want_lse=True, heads=1):
+    """(out, lse): attention with learned additive scores of the n selected rows ``ids_dev`` of the RESIDENT square DeviceCSR
+    ``A`` over EVERY stored entry e of row ids[i]: with c = col[e] and m = map[c], the entry's value row is x[m] if m >= 0 else
+    H[c] and its destination score v[m] if m >= 0 else vh[c]; z_e = u[i] + v_e per head, then as ``spgat``
+    (sgcn_spgat_pull_f32 / _h16; --full_batch_part_pull_gat).
+
+    ``ids_dev``, ``map_dev``, ``x`` and ``H`` as in ``spattn_pull``; ``u`` and ``v`` (n, H): the fresh score tables (views of
+    ``gat_scores(x, a)``'s result serve); ``vh`` (>= N, H) fp32: the stored destination scores, constants.  lse is (n, heads),
+    as in ``spgat``.  ``A`` is read in place: no cut, no plan, no synchronisation.  The result has the bits of ``spgat``
+    without a plan on the rows ``ids`` of ``A`` and the merged tables."""
+    n, N, d, heads, (xptr, ldx), (hptr, ldh, h16), slope, (uptr, ldu, vptr, ldv, vhptr, ldvh) = _gat_pull_operands(
+        "spgat_pull", A, ids_dev, map_dev, x, H, u, v, vh, slope, heads)
+    if out is None:
+        out = _attn_out(n, d, x.device, heads)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != n or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), n, d))
+    lse = torch.empty((n, heads), dtype=torch.float32, device=x.device) if want_lse else None
+    check((lib.sgcn_spgat_pull_h16 if h16 else lib.sgcn_spgat_pull_f32)(
+        A.rowptr.data_ptr(), _ptr(A.col), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, heads, xptr, ldx, hptr, ldh,
+        uptr, ldu, vptr, ldv, vhptr, ldvh, slope, cptr, ldc, _ptr(lse), _stream()))
+    return out, lse
+
+
+def spgat_pull_bwd_u(A, ids_dev, map_dev, x, H, u, v, vh, g, out_fwd, lse, slope, heads=1):
+    """(dU, delta): the source score's half of the gradient of ``spgat_pull`` for g = dL/dout, from the forward's ``out_fwd``
+    and ``lse`` -- sgcn_spgat_pull_bwd_u_f32 / _h16: delta[i, h] = <g[i], out_fwd[i]>_h and dU[i, h] = sum_e dz_e over ALL
+    stored entries of row ids[i].  Both are (n, heads): what ``spgat_pull_bwd_v`` and ``gat_scores_bwd`` read.  Stored rows
+    and scores are constants: nothing flows into ``H`` or ``vh``."""
+    n, N, d, heads, (xptr, ldx), (hptr, ldh, h16), slope, (uptr, ldu, vptr, ldv, vhptr, ldvh) = _gat_pull_operands(
+        "spgat_pull_bwd_u", A, ids_dev, map_dev, x, H, u, v, vh, slope, heads)
+    gptr, ldg = _rows2d(g, "g")
+    cptr, ldc = _rows2d(out_fwd, "out_fwd")
+    if tuple(g.shape) != (n, d) or out_fwd.shape[0] != n or out_fwd.shape[1] < d:
+        raise ValueError("g and out_fwd must be (%d, %d), got %s and %s" % (n, d, tuple(g.shape), tuple(out_fwd.shape)))
+    _dev(lse, torch.float32, "lse")
+    if tuple(lse.shape) != (n, heads) or not lse.is_contiguous():
+        raise ValueError("lse must be what spgat_pull returned: a contiguous (%d, %d) table of floats" % (n, heads))
+    delta = torch.empty((n, heads), dtype=torch.float32, device=x.device)
+    dU = torch.empty((n, heads), dtype=torch.float32, device=x.device)
+    check((lib.sgcn_spgat_pull_bwd_u_h16 if h16 else lib.sgcn_spgat_pull_bwd_u_f32)(
+        A.rowptr.data_ptr(), _ptr(A.col), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, heads, xptr, ldx, hptr, ldh,
+        uptr, ldu, vptr, ldv, vhptr, ldvh, slope, gptr, ldg, cptr, ldc, lse.data_ptr(), delta.data_ptr(), dU.data_ptr(),
+        _stream()))
+    return dU, delta
+
+
+def spgat_pull_bwd_v(At, x, u, v, g, lse, delta, slope, add=None, add_rows=0, heads=1):
+    """(dB, dV): the values' and destination scores' half of ``spgat_pull``'s gradient, through in-part entries only -- the
+    one-table sgcn_spgat_csr_bwd_v_f32 alone over ``At``, the transposed induced block A[S, S]^T (n x n) with its plan, with
+    B = ``x``, the fresh ``u`` / ``v`` and the ``lse`` / ``delta`` of the two pull launches (the coefficients it recomputes are
+    those of the FULL row).  ``add`` (its first ``add_rows`` rows) joins dB in the launch's epilogue."""
+    n = int(At.shape[0])
+    if tuple(At.shape) != (n, n) or int(x.shape[0]) != n:
+        raise ValueError("At must be the square transposed block over the %d rows of x, got %s" % (int(x.shape[0]), tuple(At.shape)))
+    slope = _attn_slope(slope)
+    bptr, ldb = _rows2d(x, "x")
+    d = int(x.shape[1])
+    heads = _attn_heads(d, heads)
+    uptr, ldu = _gat_table(u, n, heads, "u")
+    vptr, ldv = _gat_table(v, n, heads, "v")
+    gptr, ldg = _rows2d(g, "g")
+    if tuple(g.shape) != (n, d):
+        raise ValueError("g must be (%d, %d), got %s" % (n, d, tuple(g.shape)))
+    for t, name in ((lse, "lse"), (delta, "delta")):
+        _dev(t, torch.float32, name)
+        if tuple(t.shape) != (n, heads) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous (%d, %d) table of floats" % (name, n, heads))
+    aptr, ldadd = _rows2d(add, "add") if add is not None else (None, 0)
+    add_rows = int(add_rows) if add is not None else 0
+    dV = torch.empty((n, heads), dtype=torch.float32, device=x.device)
+    dB = _attn_out(n, d, x.device, heads)
+    tplan = At.plan.struct(attn_slot('gat_bwd_v', d)) if At.plan is not None else None
+    check(lib.sgcn_spgat_csr_bwd_v_f32(At.rowptr.data_ptr(), _ptr(At.col), n, n, d, heads, 1.0, 0, uptr, ldu, vptr, ldv, bptr,
+                                       ldb, slope, gptr, ldg, lse.data_ptr(), delta.data_ptr(), dB.data_ptr(),
+                                       _rows2d(dB, "dB")[1], dV.data_ptr(), aptr, ldadd, add_rows, _byref(tplan), _stream()))
+    return dB, dV
+
+
 def adam_step(theta, grad, m, v, lr_t, beta1, beta2, eps=1e-8):
     check(lib.sgcn_adam_f32(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(),
                             int(theta.numel()), float(lr_t), float(beta1), float(beta2), float(eps),

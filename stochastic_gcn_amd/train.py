@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
 from .full_batch import (InducedMatrix, PartBatch, PartSchedule, PulledMatrix, check_full_batch_parts, check_part_history,
-                         check_part_pull, part_stats, partition,
+                         check_part_pull, check_part_pull_gat, part_stats, partition,
                          StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
@@ -245,6 +245,11 @@ class Trainer(object):
         self.part_pull, pull_bf16 = check_part_pull()
         if self.part_pull:
             self.part_history, self.part_history_bf16 = True, self.part_history_bf16 or pull_bf16
+        # (--full_batch_part_pull_gat without parts, without --aggregator attn --attn_score gat, with --attn_dropout, --reverse or
+        # a bfloat16 operand: too.  It turns the same machinery on, with one score table per aggregation layer beside the rows)
+        self.part_pull_gat, gat_bf16 = check_part_pull_gat()
+        if self.part_pull_gat:
+            self.part_history, self.part_history_bf16 = True, self.part_history_bf16 or gat_bf16
         # (--aggregator max without both full-graph modes, with a bfloat16 table or an edge mask: too)
         self.max_aggregator = check_aggregator()
         # (--aggregator attn likewise; --attn_scale negative, non-finite, or set without attn: too)
@@ -461,15 +466,28 @@ class Trainer(object):
             # out-of-part neighbours read stored rows: one table per aggregation layer, on the training model
             nbytes = self.train_model.alloc_part_history(self.part_history_bf16)
             tables, owned = self.train_model.part_history
-            what = '--full_batch_part_history: a step sums over'
-            if self.part_pull:
-                what = '--full_batch_part_pull (--aggregator {}): a step {} over'.format(
-                    FLAGS.aggregator, 'attends' if FLAGS.aggregator == 'attn' else 'sums')
-            self.log('[sgcn] {} every stored entry of its rows -- fresh rows inside its '
-                     'vertex set, stored rows outside (nothing dropped, nothing rescaled) | {} table(s) of {} rows, {}: {:.1f} '
-                     'MiB, zero-filled{} | a group without a training vertex runs the forward only and pushes its rows'.format(
-                         what, sum(owned), N, 'bf16' if self.part_history_bf16 else 'fp32', nbytes / 2.0 ** 20,
-                         '' if all(owned) else '; the first aggregation layer reads the resident feature table'))
+            if self.part_pull_gat:
+                heads = int(getattr(FLAGS, 'attn_heads', 1))
+                sbytes = self.train_model.alloc_part_scores(heads)
+                self.log('[sgcn] --full_batch_part_pull_gat: a step attends over every stored entry of its rows with learned '
+                         'scores -- fresh rows and scores inside its vertex set, stored rows and stored scores outside | {} row '
+                         'table(s) of {} rows, {}: {:.1f} MiB, zero-filled{} | {} score table(s) of {} x {} fp32: {:.2f} MiB, '
+                         'zero-filled | the source scores\' gradient sees every stored entry, the values\' and destination '
+                         'scores\' in-part entries only | a group without a training vertex runs the forward only and pushes '
+                         'its rows and scores'.format(
+                             sum(owned), N, 'bf16' if self.part_history_bf16 else 'fp32', nbytes / 2.0 ** 20,
+                             '' if all(owned) else '; the first aggregation layer reads the resident feature table',
+                             len(self.train_model.part_scores), N, heads, sbytes / 2.0 ** 20))
+            else:
+                what = '--full_batch_part_history: a step sums over'
+                if self.part_pull:
+                    what = '--full_batch_part_pull (--aggregator {}): a step {} over'.format(
+                        FLAGS.aggregator, 'attends' if FLAGS.aggregator == 'attn' else 'sums')
+                self.log('[sgcn] {} every stored entry of its rows -- fresh rows inside its '
+                         'vertex set, stored rows outside (nothing dropped, nothing rescaled) | {} table(s) of {} rows, {}: {:.1f} '
+                         'MiB, zero-filled{} | a group without a training vertex runs the forward only and pushes its rows'.format(
+                             what, sum(owned), N, 'bf16' if self.part_history_bf16 else 'fp32', nbytes / 2.0 ** 20,
+                             '' if all(owned) else '; the first aggregation layer reads the resident feature table'))
 
     def part_batch(self, ids):
         """The batch of one step over the vertex set ``ids`` (ascending): the block cut out of the resident adjacency with its
@@ -485,7 +503,8 @@ class Trainer(object):
         if self.part_history:
             block = ops.csr_induce(self.train_csr, ids, ids_dev, norm='keep')
             tables, owned = self.train_model.part_history
-            matrix = PulledMatrix(block, self.train_csr, ids_dev, tables, owned, self.device)
+            matrix = PulledMatrix(block, self.train_csr, ids_dev, tables, owned, self.device,
+                                  scores=self.train_model.part_scores if self.part_pull_gat else None)
             if rows.size == 0:
                 return PartBatch(ids, ids_dev, matrix, None, None, self.train_model.L, self.device)
             return PartBatch(ids, ids_dev, matrix, self._labels_dev, rows, self.train_model.L, self.device)
