@@ -34,6 +34,7 @@ two products).
                  the rows of S, fresh rows for columns in S and stored rows for the others (ops.spmm_pull); under
                  --full_batch_part_pull with --aggregator attn ``pull_attn_product`` / ``pull_attn_backward`` attend over
                  the same entries (ops.spattn_pull, ops.spattn_pull_bwd_q, then the block's bwd_kv)
+  PulledLayer    that matrix as aggregation layer l multiplies by it (PartBatch.adj[l]): one-table calls that pull, then push
 """
 import numpy as np
 import torch
@@ -772,30 +773,37 @@ def check_full_batch_parts(flags=None, num_vertices=None):
     return P, q, norm
 
 
-def check_part_history(flags=None):
-    """(on, bf16) of --full_batch_part_history / --history_dtype: part steps that read stored rows for their out-of-part
-    neighbours (GNNAutoScale), with what the two-table product has no kernel or no meaning for refused.  Needs no device; a
-    sibling of check_full_batch_parts, called beside it."""
+def _check_part_tables(flags, flag, refuse_aggregator, stored="rows", kernels="kernels'"):
+    """(on, bf16) of the part-step flag ``flag`` / --history_dtype: what every two-table mode refuses, in one order -- no parts,
+    what ``refuse_aggregator(f, agg)`` speaks for, --reverse, --full_batch_dtype bf16, an unknown --history_dtype."""
     f = FLAGS if flags is None else flags
-    if not bool(getattr(f, 'full_batch_part_history', False)):
+    if not bool(getattr(f, flag, False)):
         return False, False
     if int(getattr(f, 'full_batch_parts', 0) or 0) <= 0:
-        raise ValueError("--full_batch_part_history needs --full_batch_parts > 0: it is the estimator of a part step's "
-                         "out-of-part neighbours, and no other mode has them")
-    agg = getattr(f, 'aggregator', 'sum')
-    if agg != 'sum':
-        raise ValueError("--full_batch_part_history is not supported with --aggregator %s: the maximum and the attention "
-                         "kernels gather from one table; a two-table form is a follow-up" % agg)
+        raise ValueError("--%s needs --full_batch_parts > 0: it is the estimator of a part step's "
+                         "out-of-part neighbours, and no other mode has them" % flag)
+    refuse_aggregator(f, getattr(f, 'aggregator', 'sum'))
     if getattr(f, 'reverse', False):
-        raise ValueError("--full_batch_part_history is not supported with --reverse: the aggregator's input would be a "
-                         "dropout-masked table, and the stored rows would hold one step's mask")
+        raise ValueError("--%s is not supported with --reverse: the aggregator's input would be a "
+                         "dropout-masked table, and the stored %s would hold one step's mask" % (flag, stored))
     if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
-        raise ValueError("--full_batch_part_history is not supported with --full_batch_dtype bf16: the pull kernel's fresh "
-                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)")
+        raise ValueError("--%s is not supported with --full_batch_dtype bf16: the pull %s fresh "
+                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)" % (flag, kernels))
     hd = getattr(f, 'history_dtype', 'fp32')
     if hd not in _CHOICES['history_dtype']:
         raise ValueError("--history_dtype must be one of %s, got %r" % ('/'.join(_CHOICES['history_dtype']), hd))
     return True, hd == 'bf16'
+
+
+def check_part_history(flags=None):
+    """(on, bf16) of --full_batch_part_history / --history_dtype: part steps that read stored rows for their out-of-part
+    neighbours (GNNAutoScale), with what the two-table product has no kernel or no meaning for refused.  Needs no device; a
+    sibling of check_full_batch_parts, called beside it."""
+    def aggregator(f, agg):
+        if agg != 'sum':
+            raise ValueError("--full_batch_part_history is not supported with --aggregator %s: the maximum and the attention "
+                             "kernels gather from one table; a two-table form is a follow-up" % agg)
+    return _check_part_tables(flags, 'full_batch_part_history', aggregator, kernels="kernel's")
 
 
 def check_part_pull(flags=None):
@@ -804,35 +812,20 @@ def check_part_pull(flags=None):
     --aggregator attn every aggregation layer attends over every stored neighbour (ops.spattn_pull).  What the two-table
     kernels have no form or no meaning for is refused.  Needs no device; called beside check_part_history, which keeps its
     own contract and, with both flags on, speaks first."""
-    f = FLAGS if flags is None else flags
-    if not bool(getattr(f, 'full_batch_part_pull', False)):
-        return False, False
-    if int(getattr(f, 'full_batch_parts', 0) or 0) <= 0:
-        raise ValueError("--full_batch_part_pull needs --full_batch_parts > 0: it is the estimator of a part step's "
-                         "out-of-part neighbours, and no other mode has them")
-    agg = getattr(f, 'aggregator', 'sum')
-    if agg == 'max':
-        raise ValueError("--full_batch_part_pull is not supported with --aggregator max: the maximum kernel gathers from one "
-                         "table; a two-table maximum is a follow-up")
-    if agg not in ('sum', 'attn'):
-        raise ValueError("--full_batch_part_pull is not supported with --aggregator %s" % agg)
-    if agg == 'attn':
-        if getattr(f, 'attn_score', 'dot') == 'gat':
-            raise ValueError("--full_batch_part_pull is not supported with --attn_score gat: its score table would need "
-                             "stale scores for the out-of-part neighbours; a two-table form is a follow-up")
-        if float(getattr(f, 'attn_dropout', 0.0) or 0.0) > 0:
-            raise ValueError("--full_batch_part_pull is not supported with --attn_dropout > 0: in this version the mask of "
-                             "out-of-part entries is not defined")
-    if getattr(f, 'reverse', False):
-        raise ValueError("--full_batch_part_pull is not supported with --reverse: the aggregator's input would be a "
-                         "dropout-masked table, and the stored rows would hold one step's mask")
-    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
-        raise ValueError("--full_batch_part_pull is not supported with --full_batch_dtype bf16: the pull kernels' fresh "
-                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)")
-    hd = getattr(f, 'history_dtype', 'fp32')
-    if hd not in _CHOICES['history_dtype']:
-        raise ValueError("--history_dtype must be one of %s, got %r" % ('/'.join(_CHOICES['history_dtype']), hd))
-    return True, hd == 'bf16'
+    def aggregator(f, agg):
+        if agg == 'max':
+            raise ValueError("--full_batch_part_pull is not supported with --aggregator max: the maximum kernel gathers from one "
+                             "table; a two-table maximum is a follow-up")
+        if agg not in ('sum', 'attn'):
+            raise ValueError("--full_batch_part_pull is not supported with --aggregator %s" % agg)
+        if agg == 'attn':
+            if getattr(f, 'attn_score', 'dot') == 'gat':
+                raise ValueError("--full_batch_part_pull is not supported with --attn_score gat: its score table would need "
+                                 "stale scores for the out-of-part neighbours; a two-table form is a follow-up")
+            if float(getattr(f, 'attn_dropout', 0.0) or 0.0) > 0:
+                raise ValueError("--full_batch_part_pull is not supported with --attn_dropout > 0: in this version the mask of "
+                                 "out-of-part entries is not defined")
+    return _check_part_tables(flags, 'full_batch_part_pull', aggregator)
 
 
 def check_part_pull_gat(flags=None):
@@ -840,32 +833,17 @@ def check_part_pull_gat(flags=None):
     additive scores (--attn_score gat) that read stored rows AND stored destination scores for their out-of-part
     neighbours (ops.spgat_pull).  What the two-table kernels have no form or no meaning for is refused.  Needs no device;
     called beside check_part_pull, which keeps its own contract and, with both flags on, speaks first."""
-    f = FLAGS if flags is None else flags
-    if not bool(getattr(f, 'full_batch_part_pull_gat', False)):
-        return False, False
-    if int(getattr(f, 'full_batch_parts', 0) or 0) <= 0:
-        raise ValueError("--full_batch_part_pull_gat needs --full_batch_parts > 0: it is the estimator of a part step's "
-                         "out-of-part neighbours, and no other mode has them")
-    agg = getattr(f, 'aggregator', 'sum')
-    if agg != 'attn':
-        raise ValueError("--full_batch_part_pull_gat needs --aggregator attn (got %s): it is the two-table form of the "
-                         "attention with learned scores; --full_batch_part_pull serves the sum" % agg)
-    if getattr(f, 'attn_score', 'dot') != 'gat':
-        raise ValueError("--full_batch_part_pull_gat needs --attn_score gat: --full_batch_part_pull is the two-table form "
-                         "of dot-product attention")
-    if float(getattr(f, 'attn_dropout', 0.0) or 0.0) > 0:
-        raise ValueError("--full_batch_part_pull_gat is not supported with --attn_dropout > 0: in this version the mask of "
-                         "out-of-part entries is not defined")
-    if getattr(f, 'reverse', False):
-        raise ValueError("--full_batch_part_pull_gat is not supported with --reverse: the aggregator's input would be a "
-                         "dropout-masked table, and the stored rows and scores would hold one step's mask")
-    if getattr(f, 'full_batch_dtype', 'fp32') == 'bf16':
-        raise ValueError("--full_batch_part_pull_gat is not supported with --full_batch_dtype bf16: the pull kernels' fresh "
-                         "operand is fp32 (--history_dtype bf16 halves the stored rows instead)")
-    hd = getattr(f, 'history_dtype', 'fp32')
-    if hd not in _CHOICES['history_dtype']:
-        raise ValueError("--history_dtype must be one of %s, got %r" % ('/'.join(_CHOICES['history_dtype']), hd))
-    return True, hd == 'bf16'
+    def aggregator(f, agg):
+        if agg != 'attn':
+            raise ValueError("--full_batch_part_pull_gat needs --aggregator attn (got %s): it is the two-table form of the "
+                             "attention with learned scores; --full_batch_part_pull serves the sum" % agg)
+        if getattr(f, 'attn_score', 'dot') != 'gat':
+            raise ValueError("--full_batch_part_pull_gat needs --attn_score gat: --full_batch_part_pull is the two-table form "
+                             "of dot-product attention")
+        if float(getattr(f, 'attn_dropout', 0.0) or 0.0) > 0:
+            raise ValueError("--full_batch_part_pull_gat is not supported with --attn_dropout > 0: in this version the mask of "
+                             "out-of-part entries is not defined")
+    return _check_part_tables(flags, 'full_batch_part_pull_gat', aggregator, stored="rows and scores")
 
 
 def partition(adj, P, seed=1):
@@ -957,7 +935,8 @@ class PulledMatrix(InducedMatrix):
     ``owned`` (the resident feature table under an aggregation layer with no layer in front of it) is exact and never written.
     ``pull_attn_product`` / ``pull_attn_backward`` are the attention over the same entries (--full_batch_part_pull).  The pull
     launches take their operands as they are: nothing is staged, so a table too wide for its alignment (602 columns on a pitch
-    of 602 floats) is refused with the kernels' width message."""
+    of 602 floats) is refused with the kernels' width message.  These methods take the layer's index and push nothing; an
+    aggregation layer is handed ``layer(l)``, which pulls, then pushes, behind StaticMatrix's one-table signatures."""
 
     def __init__(self, block, resident, ids_dev, tables, owned, device=None, scores=None):
         if getattr(block, 'map', None) is None:
@@ -1041,14 +1020,72 @@ class PulledMatrix(InducedMatrix):
         T = self._score_table(l)
         ops.scatter_rows(T, self.ids_dev, S[:, int(T.shape[1]):])
 
+    def layer(self, l):
+        return PulledLayer(self, l)
+
     def describe(self, d):
         return dict(plan_from_cache=False, pace=None, kernel="sgcn::spmm_pull_kernel", products=self.products)
+
+
+class PulledLayer(object):
+    """A PulledMatrix as aggregation layer ``l`` sees it: StaticMatrix's one-table signatures, answered by the two-table launches
+    over table l.  Every forward pulls and THEN pushes the layer's input rows (with score tables: its fresh destination scores
+    too) -- columns inside the step's vertex set never read either table, and a backward re-reads only rows outside it.
+    ``shape``, ``transpose`` and the maximum are the block's: in-part entries only.  So are ``gat_product`` / ``gat_backward``
+    of a matrix WITHOUT score tables, which push nothing."""
+
+    def __init__(self, matrix, l):
+        self.matrix, self.l, self.shape = matrix, int(l), matrix.shape
+
+    @property
+    def transpose(self):
+        return self.matrix.transpose
+
+    def _no_dropout(self, keep):
+        if keep != 1.0:
+            raise RuntimeError("--attn_dropout has no two-table form: the mask of out-of-part entries is not defined")
+
+    def product(self, x, out=None):
+        out = self.matrix.pull_product(x, self.l, out)
+        self.matrix.push(x, self.l)
+        return out
+
+    def max_product(self, x, out=None, want_arg=True):
+        return self.matrix.max_product(x, out=out, want_arg=want_arg)
+
+    def attn_product(self, x, scale, out=None, want_lse=True, heads=1, keep=1.0, key=0):
+        self._no_dropout(keep)
+        res = self.matrix.pull_attn_product(x, self.l, scale, out=out, want_lse=want_lse, heads=heads)
+        self.matrix.push(x, self.l)
+        return res
+
+    def attn_backward(self, x, g, out_fwd, lse, scale, add=None, add_rows=0, heads=1, keep=1.0, key=0):
+        return self.matrix.pull_attn_backward(x, self.l, g, out_fwd, lse, scale, add=add, add_rows=add_rows, heads=heads)
+
+    def gat_product(self, x, a, slope, out=None, want_lse=True, heads=1, keep=1.0, key=0):
+        M = self.matrix
+        if M.scores is None:
+            return M.gat_product(x, a, slope, out=out, want_lse=want_lse, heads=heads, keep=keep, key=key)
+        self._no_dropout(keep)
+        res, lse, S = M.pull_gat_product(x, a, self.l, slope, out=out, want_lse=want_lse, heads=heads)
+        M.push(x, self.l)
+        M.push_scores(S, self.l)
+        return res, lse, S
+
+    def gat_backward(self, x, a, S, g, out_fwd, lse, slope, add=None, add_rows=0, heads=1, keep=1.0, key=0, need_dx=True):
+        M = self.matrix
+        if M.scores is None:
+            return M.gat_backward(x, a, S, g, out_fwd, lse, slope, add=add, add_rows=add_rows, heads=heads, keep=keep, key=key,
+                                  need_dx=need_dx)
+        return M.pull_gat_backward(x, a, S, self.l, g, out_fwd, lse, slope, add=add, add_rows=add_rows, heads=heads,
+                                   need_dx=need_dx)
 
 
 class PartBatch(StaticBatch):
     """One Cluster-GCN step's batch: the static batch of the induced subgraph over ``ids`` (ascending, unique) -- the
     InducedMatrix, labels[ids] (ops.gather_rows of the resident N x C table) and the loss rows, the POSITIONS within ``ids``
-    of the vertices the loss runs over.  ``ids_dev`` are the ids on the device: the model gathers its input rows by them."""
+    of the vertices the loss runs over.  ``ids_dev`` are the ids on the device: the model gathers its input rows by them.
+    Over a PulledMatrix ``adj[l]`` is its view for layer l (``PulledMatrix.layer``); ``matrix`` stays the matrix itself."""
 
     def __init__(self, ids, ids_dev, matrix, labels, rows, L, device=None):
         n = int(matrix.shape[0])
@@ -1057,6 +1094,8 @@ class PartBatch(StaticBatch):
         # (labels and rows both None: a batch for forward passes only -- the refresh of a group without a training vertex)
         super(PartBatch, self).__init__(matrix, None if labels is None else ops.gather_rows(labels, ids_dev), rows, L, device)
         self.ids, self.ids_dev = np.asarray(ids, dtype=np.int32), ids_dev
+        if isinstance(matrix, PulledMatrix):
+            self.adj = [matrix.layer(l) for l in range(self.L)]
 
 
 def part_stats(adj, parts, train_ids):

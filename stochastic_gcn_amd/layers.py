@@ -374,7 +374,12 @@ def _squared(A):
 
 class PlainAggregator(Layer):
     """gcn/layers.py:214-257: Z = A.H, or concat(H[:n1], A.H); on (mu, var): A.mu and A^2.var.  The products go through the
-    adjacency object (``A.product``): ops.spmm for a minibatch DeviceCSR, a static-graph kernel for a full-graph matrix."""
+    adjacency object (``A.product``): ops.spmm for a minibatch DeviceCSR, a static-graph kernel for a full-graph matrix.
+
+    --aggregator / --attn_score choose the KIND -- sum, max, attn, gat: two short methods each, one call on the adjacency
+    object in StaticMatrix's one-table signature.  The concatenation is not theirs (``_self_half``, ``_self_grad``), nor the
+    matrix's make: a part step over stored rows hands the layer full_batch.PulledLayer, which reads its tables, stores into
+    them and refuses what has no two-table form behind the same signatures."""
 
     def __init__(self, model, l, **kw):
         super(PlainAggregator, self).__init__(**kw)
@@ -411,120 +416,14 @@ class PlainAggregator(Layer):
             ops.spmm(self._A2, var, out=ov[:, d:])
             return om, ov
         x = dense_of(x)
-        n1, d = A.shape[0], x.shape[1]
-        self._A, self._concat, self._d = A, concat, d
-        # --aggregator max on a full-graph matrix: the element-wise maximum over the adjacency's pattern in place of its
-        # linear map; a training model keeps the winners' ids for the backward, an evaluation model allocates none
-        self._max = FLAGS.aggregator == 'max'
-        if self._max:
-            if not hasattr(A, 'max_product'):
-                raise RuntimeError("--aggregator max runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
-                                   "minibatch adjacency has no maximum kernel")
-            want = bool(getattr(self.model, 'is_training', True))
-            if not concat:
-                out, self._arg = A.max_product(x, want_arg=want)
-                return out
-            out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
-            out[:, :d] = x[:n1]
-            _, self._arg = A.max_product(x, out=out[:, d:], want_arg=want)
-            return out
-        # --aggregator attn: softmax dot-product attention over the same pattern, the queries the layer's own input rows; a
-        # training model keeps the input, the output and the rows' log-sum-exp for the backward, an evaluation model no lse
-        self._attn = FLAGS.aggregator == 'attn'
-        if self._attn:
-            if not hasattr(A, 'attn_product'):
-                raise RuntimeError("--aggregator attn runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
-                                   "minibatch adjacency has no attention kernel")
-            want = bool(getattr(self.model, 'is_training', True))
-            # --attn_heads H: every head an attention over its own d / H columns, the default scale 1 / sqrt(d / H)
-            heads = self._heads = int(getattr(FLAGS, 'attn_heads', 1))
-            from .full_batch import attn_heads_divide
-            attn_heads_divide(heads, d, self.name)
-            scale = float(FLAGS.attn_scale) if float(FLAGS.attn_scale) > 0 else float(d // heads) ** -0.5
-            self._x, self._scale = (x if want else None), scale
-            # --attn_dropout P: a training step drops coefficients under a mask keyed by (seed, this layer's index, step); the
-            # key is drawn here, once, and kept for the backward.  An evaluation model never masks.
-            self._drop = {}
-            p_drop = float(getattr(FLAGS, 'attn_dropout', 0.0))
-            if want and p_drop > 0:
-                m = self.model
-                self._drop = dict(keep=1.0 - p_drop, key=ops.attn_key(getattr(m, 'dropout_seed', FLAGS.seed), self.index,
-                                                                      getattr(m, 'dropout_step', 0)))
-            # --attn_score gat: the scores are LeakyReLU(u_i + v_j) of the layer's own vectors -- one launch for the score
-            # table, then the product; a training model keeps the table beside the input, the output and lse
-            self._gat_on = self._gat()
-            if self._gat_on:
-                if not hasattr(A, 'gat_product'):
-                    raise RuntimeError("--attn_score gat runs on a full-graph matrix only (full_batch.StaticMatrix)")
-                a, slope = self.vars['attn_vec'], float(getattr(FLAGS, 'attn_slope', 0.2))
-                if tuple(a.shape) != (2, d):
-                    raise ValueError("%s: attn_vec is %s, the input is %d columns wide" % (self.name, tuple(a.shape), d))
-                self._slope = slope
-                out = None
-                if concat:
-                    out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
-                    out[:, :d] = x[:n1]
-                # --full_batch_part_pull_gat: the step's matrix (full_batch.PulledMatrix with score tables) attends over EVERY
-                # stored entry of its rows -- fresh rows and scores for columns inside the step's vertex set, this layer's
-                # stored rows and stored destination scores for the others -- and the layer then pushes its input rows and
-                # its destination scores (push-after-pull is safe: columns inside the set never read either table)
-                self._pull = hasattr(A, 'pull_gat_product') and getattr(A, 'scores', None) is not None
-                if self._pull:
-                    if self._drop:
-                        raise RuntimeError("--attn_dropout has no two-table form: the mask of out-of-part entries is not defined")
-                    res, lse, S = A.pull_gat_product(x, a, self.l, slope, out=out[:, d:] if concat else None, want_lse=want,
-                                                     heads=heads)
-                    A.push(x, self.l)
-                    A.push_scores(S, self.l)
-                else:
-                    res, lse, S = A.gat_product(x, a, slope, out=out[:, d:] if concat else None, want_lse=want, heads=heads,
-                                                **self._drop)
-                self._out, self._lse, self._S = res, lse, (S if want else None)
-                return out if concat else res
-            # --full_batch_part_pull: the step's matrix (full_batch.PulledMatrix) attends over EVERY stored entry of its rows --
-            # fresh rows of x for columns inside the step's vertex set, this layer's stored rows for the others -- and the
-            # layer then pushes its input rows (push-after-pull is safe: columns inside the set never read the table, and the
-            # backward re-reads only rows outside it)
-            self._pull = hasattr(A, 'pull_attn_product')
-            if self._pull and self._drop:
-                raise RuntimeError("--attn_dropout has no two-table form: the mask of out-of-part entries is not defined")
-            if not concat:
-                if self._pull:
-                    self._out, self._lse = A.pull_attn_product(x, self.l, scale, want_lse=want, heads=heads)
-                    A.push(x, self.l)
-                else:
-                    self._out, self._lse = A.attn_product(x, scale, want_lse=want, heads=heads, **self._drop)
-                return self._out
-            out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
-            out[:, :d] = x[:n1]
-            if self._pull:
-                self._out, self._lse = A.pull_attn_product(x, self.l, scale, out=out[:, d:], want_lse=want, heads=heads)
-                A.push(x, self.l)
-            else:
-                self._out, self._lse = A.attn_product(x, scale, out=out[:, d:], want_lse=want, heads=heads, **self._drop)
-            return out
-        # --full_batch_part_history: the step's matrix (full_batch.PulledMatrix) sums over EVERY stored entry of its rows --
-        # fresh rows of x for columns inside the step's vertex set, this layer's stored rows for the others -- and the layer
-        # then pushes its input rows into that table (columns inside the set never read it: push-after-pull is safe).  The
-        # backward stays A.transpose.product: the 'keep' block, in-part entries only
-        pull = hasattr(A, 'pull_product')
-        if not concat:
-            if not pull:
-                return A.product(x)
-            out = A.pull_product(x, self.l)
-            A.push(x, self.l)
-            return out
-        out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
-        if x.dtype == torch.bfloat16:       # the feature table under --feature_dtype bf16: the self half widened in place
-            ops.gather_rows(x[:n1], None, out=out[:, :d])
-        else:
-            out[:, :d] = x[:n1]
-        if pull:
-            A.pull_product(x, self.l, out=out[:, d:])
-            A.push(x, self.l)
-        else:
-            A.product(x, out=out[:, d:])
-        return out
+        self._A, self._concat, self._d = A, concat, x.shape[1]
+        self._max, self._attn = FLAGS.aggregator == 'max', FLAGS.aggregator == 'attn'
+        self._gat_on = self._attn and self._gat()
+        self._kind = 'max' if self._max else 'gat' if self._gat_on else 'attn' if self._attn else 'sum'
+        out, nbr = self._self_half(x)
+        # a training model keeps what the kind's backward needs; an evaluation model allocates none of it
+        res = getattr(self, '_forward_' + self._kind)(A, x, nbr, bool(getattr(self.model, 'is_training', True)))
+        return res if out is None else out
 
     def backward(self, g):
         A, d = self._A, self._d
@@ -534,47 +433,102 @@ class PlainAggregator(Layer):
                 return ops.spmm(A.transpose, g[0]), ops.spmm(A2.transpose, g[1])
             return (ops.spmm(A.transpose, g[0][:, d:], add=g[0][:, :d], add_rows=n1),
                     ops.spmm(A2.transpose, g[1][:, d:], add=g[1][:, :d], add_rows=n1))
-        if self._max:
-            # the maximum's gradient goes to each element's winner: one gather over A^T, the self half in its epilogue
-            if not self._concat:
-                return A.transpose.max_backward(g, self._arg)
-            return A.transpose.max_backward(g[:, d:], self._arg, add=g[:, :d], add_rows=A.shape[0])
-        if self._attn and self._gat_on:
-            # launches 3, 4, 5: dU over A, dB (+ g_self in the epilogue) and dV over A^T, then back through the scores into dX
-            # and attn_vec's gradient; as the model's first parametrised layer (--nopreprocess) nothing consumes dX
-            a = self.vars['attn_vec']
-            kw = dict(heads=self._heads, need_dx=self.need_dx, **self._drop)
-            if self._pull:
-                # --full_batch_part_pull_gat: dU over every stored entry, dB and dV through the in-part block
-                if not self._concat:
-                    dx, da = A.pull_gat_backward(self._x, a, self._S, self.l, g, self._out, self._lse, self._slope, **kw)
-                else:
-                    dx, da = A.pull_gat_backward(self._x, a, self._S, self.l, g[:, d:], self._out, self._lse, self._slope,
-                                                 add=g[:, :d], add_rows=A.shape[0], **kw)
-            elif not self._concat:
-                dx, da = A.gat_backward(self._x, a, self._S, g, self._out, self._lse, self._slope, **kw)
-            else:
-                dx, da = A.gat_backward(self._x, a, self._S, g[:, d:], self._out, self._lse, self._slope, add=g[:, :d],
-                                        add_rows=A.shape[0], **kw)
-            self.grads['attn_vec'].copy_(da)
-            return dx
-        if self._attn:
-            # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
-            if self._pull:
-                # --full_batch_part_pull: dQ over every stored entry, dB through the in-part block with dQ as its addend
-                if not self._concat:
-                    return A.pull_attn_backward(self._x, self.l, g, self._out, self._lse, self._scale, heads=self._heads)
-                return A.pull_attn_backward(self._x, self.l, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d],
-                                            add_rows=A.shape[0], heads=self._heads)
-            if not self._concat:
-                return A.attn_backward(self._x, g, self._out, self._lse, self._scale, heads=self._heads, **self._drop)
-            return A.attn_backward(self._x, g[:, d:], self._out, self._lse, self._scale, add=g[:, :d], add_rows=A.shape[0],
-                                   heads=self._heads, **self._drop)
+        g, add = self._self_grad(g)
+        return getattr(self, '_backward_' + self._kind)(A, g, add)
+
+    # ---- concat(H[:n1], .): written once per direction ---------------------------------------------------------------------
+    def _self_half(self, x):
+        """(out, its neighbour half) with the self half filled in, or (None, None) without concat"""
         if not self._concat:
-            return A.transpose.product(g)
-        # dX = A^T g_nbr + [g_self ; 0]: the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep
-        # kernel stores it first and multiplies with beta = 1 (full_batch.StaticMatrix.product)
-        return A.transpose.product(g[:, d:], add=g[:, :d], add_rows=A.shape[0])
+            return None, None
+        n1, d = self._A.shape[0], self._d
+        out = torch.empty((n1, 2 * d), dtype=torch.float32, device=x.device)
+        if x.dtype == torch.bfloat16:       # the feature table under --feature_dtype bf16: the self half widened in place
+            ops.gather_rows(x[:n1], None, out=out[:, :d])
+        else:
+            out[:, :d] = x[:n1]
+        return out, out[:, d:]
+
+    def _self_grad(self, g):
+        """(g's neighbour half, the keywords that add its self half to dX's first rows in the launch's epilogue), or (g, {})"""
+        if not self._concat:
+            return g, {}
+        d = self._d
+        return g[:, d:], dict(add=g[:, :d], add_rows=self._A.shape[0])
+
+    # ---- the kinds: _forward_K(A, x, nbr, want) -> A's result, _backward_K(A, g, add) -> dX ------------------------------------
+    def _forward_sum(self, A, x, nbr, want):
+        return A.product(x, out=nbr)
+
+    def _backward_sum(self, A, g, add):
+        # the self term rides in the SpMM epilogue (one launch); a static matrix on a sweep kernel stores it first and
+        # multiplies with beta = 1 (full_batch.StaticMatrix.product)
+        return A.transpose.product(g, **add)
+
+    def _forward_max(self, A, x, nbr, want):
+        # --aggregator max on a full-graph matrix: the element-wise maximum over the adjacency's pattern in place of its
+        # linear map; a training model keeps the winners' ids for the backward
+        if not hasattr(A, 'max_product'):
+            raise RuntimeError("--aggregator max runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
+                               "minibatch adjacency has no maximum kernel")
+        res, self._arg = A.max_product(x, out=nbr, want_arg=want)
+        return res
+
+    def _backward_max(self, A, g, add):
+        # the maximum's gradient goes to each element's winner: one gather over A^T, the self half in its epilogue
+        return A.transpose.max_backward(g, self._arg, **add)
+
+    def _attention(self, A, x, want):
+        """what both attentions settle before their launch: heads, scale, the input kept for the backward, the step's mask"""
+        if not hasattr(A, 'attn_product'):
+            raise RuntimeError("--aggregator attn runs on a full-graph matrix only (full_batch.StaticMatrix): a sampled "
+                               "minibatch adjacency has no attention kernel")
+        # --attn_heads H: every head an attention over its own d / H columns, the default scale 1 / sqrt(d / H)
+        d, heads = self._d, int(getattr(FLAGS, 'attn_heads', 1))
+        from .full_batch import attn_heads_divide
+        attn_heads_divide(heads, d, self.name)
+        scale = float(FLAGS.attn_scale) if float(FLAGS.attn_scale) > 0 else float(d // heads) ** -0.5
+        self._heads, self._x, self._scale = heads, (x if want else None), scale
+        # --attn_dropout P: a training step drops coefficients under a mask keyed by (seed, this layer's index, step); the
+        # key is drawn here, once, and kept for the backward.  An evaluation model never masks.
+        self._drop = {}
+        p_drop = float(getattr(FLAGS, 'attn_dropout', 0.0))
+        if want and p_drop > 0:
+            m = self.model
+            self._drop = dict(keep=1.0 - p_drop, key=ops.attn_key(getattr(m, 'dropout_seed', FLAGS.seed), self.index,
+                                                                  getattr(m, 'dropout_step', 0)))
+
+    def _forward_attn(self, A, x, nbr, want):
+        # --aggregator attn: softmax dot-product attention over the adjacency's pattern, the queries the layer's own input
+        # rows; a training model keeps the input, the output and the rows' log-sum-exp for the backward
+        self._attention(A, x, want)
+        self._out, self._lse = A.attn_product(x, self._scale, out=nbr, want_lse=want, heads=self._heads, **self._drop)
+        return self._out
+
+    def _backward_attn(self, A, g, add):
+        # dX = dB + [dQ + g_self ; 0]: a gather over A for dQ, one over A^T for dB with the first one's result as addend
+        return A.attn_backward(self._x, g, self._out, self._lse, self._scale, heads=self._heads, **add, **self._drop)
+
+    def _forward_gat(self, A, x, nbr, want):
+        # --attn_score gat: the scores are LeakyReLU(u_i + v_j) of the layer's own vectors -- one launch for the score
+        # table, then the product; a training model keeps the table beside the input, the output and lse
+        self._attention(A, x, want)
+        if not hasattr(A, 'gat_product'):
+            raise RuntimeError("--attn_score gat runs on a full-graph matrix only (full_batch.StaticMatrix)")
+        a, self._slope = self.vars['attn_vec'], float(getattr(FLAGS, 'attn_slope', 0.2))
+        if tuple(a.shape) != (2, self._d):
+            raise ValueError("%s: attn_vec is %s, the input is %d columns wide" % (self.name, tuple(a.shape), self._d))
+        self._out, self._lse, S = A.gat_product(x, a, self._slope, out=nbr, want_lse=want, heads=self._heads, **self._drop)
+        self._S = S if want else None
+        return self._out
+
+    def _backward_gat(self, A, g, add):
+        # launches 3, 4, 5: dU over A, dB (+ g_self in the epilogue) and dV over A^T, then back through the scores into dX
+        # and attn_vec's gradient; as the model's first parametrised layer (--nopreprocess) nothing consumes dX
+        dx, da = A.gat_backward(self._x, self.vars['attn_vec'], self._S, g, self._out, self._lse, self._slope,
+                                heads=self._heads, need_dx=self.need_dx, **add, **self._drop)
+        self.grads['attn_vec'].copy_(da)
+        return dx
 
 
 class VRAggregator(Layer):

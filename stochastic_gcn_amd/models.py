@@ -1096,7 +1096,7 @@ class GCN(Model):
     def refresh_part_history(self, feed_dict):
         """--full_batch_part_history, a group without a training vertex: the training-mode forward of the part batch up to the
         LAST aggregation layer's input, so that every table takes the group's rows -- the layers in front push their own
-        (layers.PlainAggregator), the last layer's input is pushed here.  No loss, no backward, no optimizer step."""
+        (behind their matrix, full_batch.PulledLayer), the last layer's input is pushed here.  No loss, no backward, no step."""
         from .layers import PlainAggregator, dense_of
         if not hasattr(feed_dict.matrix, 'push'):
             raise ValueError("refresh_part_history needs a part batch over a full_batch.PulledMatrix")
@@ -1106,13 +1106,15 @@ class GCN(Model):
         ops.pin_stream()
         try:
             self.forward(cur, stop=last)
-            if feed_dict.matrix.owned[self.L - 1]:
-                feed_dict.matrix.push(dense_of(self.activations[-1]), self.L - 1)
-            if getattr(feed_dict.matrix, 'scores', None) is not None:
-                # --full_batch_part_pull_gat: the last layer's destination scores as well (the layers in front pushed theirs)
+            M, l = feed_dict.matrix, self.L - 1
+            scored = getattr(M, 'scores', None) is not None
+            if M.owned[l] or scored:
                 x = dense_of(self.activations[-1])
-                S = ops.gat_scores(x, self.layers[last].vars['attn_vec'], heads=int(getattr(FLAGS, 'attn_heads', 1)))
-                feed_dict.matrix.push_scores(S, self.L - 1)
+                M.push(x, l)
+                if scored:
+                    # --full_batch_part_pull_gat: the last layer's destination scores as well (the layers in front stored theirs)
+                    a = self.layers[last].vars['attn_vec']
+                    M.push_scores(ops.gat_scores(x, a, heads=int(getattr(FLAGS, 'attn_heads', 1))), l)
         finally:
             ops.unpin_stream()
         self.dropout_step += 1
