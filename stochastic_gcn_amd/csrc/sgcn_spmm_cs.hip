@@ -104,6 +104,38 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 #define SGCN_CS_ROWS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 
+// Cache policy of the epilogue's stores, one per destination, fixed when the library is built ("The end of
+// a launch": the measured table).  0 plain, 1 nt, 2 sc1 (write-through: the line does not stay dirty in the XCD's L2),
+// 3 sc0 sc1.  The macros exist for the probe builds of profiles/cs_boundary_probe.py; the product ships the defaults:
+// nt for the rows of C (no sweep launch reads back what one has stored, and the lock-step then holds at a clock 4 % faster:
+// -1.2 % per fwd + bwd pair; write-through measured SLOWER than plain), plain for the workspace slots, which cs_fix_kernel
+// reads back in the next launch (no policy there measured outside the noise).
+#ifndef SGCN_CS_STORE_C
+#define SGCN_CS_STORE_C 1
+#endif
+#ifndef SGCN_CS_STORE_WS
+#define SGCN_CS_STORE_WS 0
+#endif
+// One store of the epilogue, 16 or 4 bytes, on a 64-bit global address.  The compiler has no spelling for a write-through
+// store of 16 bytes on such an address, so 2 and 3 are asm statements: hipcc does not count them in vmcnt, which makes
+// every wait it places behind one wait for MORE than it believes is outstanding (the counter retires in order) -- never for
+// less; the 16-byte form ends in the two wait states a store of more than 64 bits needs before its data registers may be
+// written again.
+template <int POL, class T>
+__device__ __forceinline__ void cs_store(__attribute__((address_space(1))) T* p, T v) {
+    static_assert(POL >= 0 && POL <= 3, "plain, nt, sc1, sc0 sc1");
+    static_assert(sizeof(T) == 16 || sizeof(T) == 4, "a float4 or a float");
+    if constexpr (POL == 0) *p = v;
+    else if constexpr (POL == 1) __builtin_nontemporal_store(v, p);
+    else if constexpr (sizeof(T) == 16) {
+        if constexpr (POL == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+        else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+    } else {
+        if constexpr (POL == 2) asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+        else asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
+    }
+}
+
 // ---- the epilogue of the two- and four-group sweep kernels ----------------------------------------------------------------
 // All waves of a launch reach the end of the sweep together (that is the design), so whatever a wave waits for here it waits
 // for behind 4,095 others.  On gfx9 the vector memory counter counts stores as well as loads: an epilogue that reads a row's
@@ -159,13 +191,19 @@ __device__ __forceinline__ void cs_epilogue(const CsArgs& a, Acc&& acc) {
         return w;
     };
     const int left = a.d - f4;
+    auto store_as = [&](auto pol, const Row& w, VT res) {
+        constexpr int kPol = decltype(pol)::value;
+        if (left >= 4) cs_store<kPol>((gvec*)(w.p + f4), res);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (k < left) cs_store<kPol>(w.p + f4 + k, res[k]);
+        }
+    };
     auto store = [&](const Row& w, VT res) {
         if (w.on && act4) {
-            if (left >= 4) *(gvec*)(w.p + f4) = res;
-            else {
-#pragma unroll
-                for (int k = 0; k < 4; k++) if (k < left) w.p[f4 + k] = res[k];
-            }
+            if constexpr (SGCN_CS_STORE_C == SGCN_CS_STORE_WS) store_as(std::integral_constant<int, SGCN_CS_STORE_C>{}, w, res);
+            else if (w.ws) store_as(std::integral_constant<int, SGCN_CS_STORE_WS>{}, w, res);
+            else store_as(std::integral_constant<int, SGCN_CS_STORE_C>{}, w, res);
         }
     };
     if (a.beta == 0.f) {
@@ -408,7 +446,7 @@ __global__ __launch_bounds__(kBlock) void cs_spmm16_kernel(CsArgs a) {
 // DICT (a dictionary plan, sgcn_csplan_t.dict_bits): the one compulsory stream of a launch that is pure overhead is the
 // plan entries, fetched again in every pass, and half of it is the fp32 value of each entry -- which on a normalised
 // adjacency is one of a few dozen (A) or a few hundred (A^T) bit patterns per tile.  The wave copies its tile's table
-// (at most 1,024 floats) into its own 4 KiB of LDS in the prologue, beside the tile_ptr load, and an entry's value is one
+// (at most 1,024 floats) into its own 4 KiB of LDS in the prologue, in front of the entries' loads, and an entry's value is one
 // ds_read_b32 at the index that rides in the column word; the word alone is fetched.  The lookup of a chunk's entries is
 // made where the chunk's words are first needed anyway (the last batch of the chunk in front of it gathers from them),
 // never right behind their load, and it strips the index from the word, so everything that takes a column from the word
@@ -451,7 +489,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     // columns per tick in 16.16 fixed point (a launch lasts < 2^16 ticks of 10 ns; K / ticks < 2^15)
     const uint32_t cpt16 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.cols_per_tick * 65536.0f));
     const uint32_t slack = (uint32_t)a.slack_cols;
-    // DICT: the table's length first -- its loads then run beside the tile_ptr -> entries chain, not behind it
+    // DICT: the table's length is loaded together with tile_ptr.  What the compiler makes of the copy below is NOT a set of
+    // loads beside the tile_ptr -> entries chain: every quarter is a load under its branch with an s_waitcnt vmcnt(0) behind
+    // it, and the entries' loads are issued behind the last -- four dependent round trips in front of the first gather for
+    // A, five for A^T (tables of more than 256 values).  A branch-free form with three was measured at -0.009 / -0.037 ms
+    // per fwd + bwd pair, under the bar for a sweep change, and dropped: DESIGN.md 3.2, profiles/HISTORY.md.
     typedef __attribute__((address_space(3))) float lds_float;
     typedef __attribute__((address_space(3))) VT lds_vec;
     lds_float* tab = nullptr;
