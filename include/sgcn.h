@@ -842,6 +842,31 @@ int sgcn_spmm_pull_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const 
 int sgcn_spmm_pull_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, const int32_t* dev_ids,
                        int32_t n, int32_t N, const int32_t* dev_map, int32_t d, const float* dev_X, int64_t ldx,
                        const uint16_t* dev_H, int64_t ldh, float* dev_C, int64_t ldc, void* stream);
+/* The two-table element-wise neighbour maximum of a part step that keeps its out-of-part entries (--full_batch_part_pull_max;
+ * sgcn_spmax_pull.hip).  Setting and operands are those of sgcn_spmm_pull_*, the stored values left out (the pattern alone
+ * says who the neighbours are; column ids unique per row).  For selected row i, over every stored entry e of row ids[i] in
+ * stored order, with B_e = map[col[e]] >= 0 ? X[map[col[e]], :] : H[col[e], :]:
+ *
+ *   C[i, c]   = the FIRST maximum of B_e[c] under sgcn_spmax_csr_f32's rule: the best starts as the first entry, a later
+ *               entry replaces it only on strict >, so the first of +-0.0 or of equal values wins whichever table it comes
+ *               from; +-inf are ordinary values; NaN-free input is the caller's promise; an empty row gives +0.0
+ *   arg[i, c] = the winner (nullable: an evaluation):  >= 0 fresh, its POSITION in ids;  -1 the row is empty;
+ *               <= -2 stale, global column -2 - arg
+ *
+ * No arithmetic: C holds the bits sgcn_spmax_csr_f32 without a plan gives on the rows ids of the matrix and the merged
+ * table (H with the rows ids replaced by X), _h16 those of _f32 on the widened table.  arg is what the EXISTING backward
+ * reads: sgcn_spmax_csr_bwd_f32 over the transposed in-part block A[S, S]^T adds G[i, c] to row j where arg[i, c] == j; a
+ * stale winner is a constant of the step, and a negative word never matches a row.  C and arg may be pitched views.  One
+ * lane group owns one selected row: NO plan and NO split rows in this version.  No atomics: the same bits on every run.
+ * The vector width is the widest that the alignment of X, H (_f32), C, arg and the four pitches allow.  SGCN_ERR_INVALID,
+ * before any HIP call, for a negative size, n > N, d <= 0, a pitch below d (ldarg where arg is given), a null operand with
+ * n > 0, a bfloat16 table off its layout; n == 0 returns SGCN_OK without a launch. */
+int sgcn_spmax_pull_f32(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                        const int32_t* dev_map, int32_t d, const float* dev_X, int64_t ldx, const float* dev_H, int64_t ldh,
+                        float* dev_C, int64_t ldc, int32_t* dev_arg, int64_t ldarg, void* stream);
+int sgcn_spmax_pull_h16(const int32_t* dev_rowptr, const int32_t* dev_col, const int32_t* dev_ids, int32_t n, int32_t N,
+                        const int32_t* dev_map, int32_t d, const float* dev_X, int64_t ldx, const uint16_t* dev_H, int64_t ldh,
+                        float* dev_C, int64_t ldc, int32_t* dev_arg, int64_t ldarg, void* stream);
 /* Two-table softmax dot-product attention of a part step that keeps its out-of-part entries (--full_batch_part_pull with
  * --aggregator attn; sgcn_spattn_pull.hip).  The setting is that of sgcn_spmm_pull_*: the CSR is the RESIDENT N x N adjacency,
  * read in place (stored values are not read; column ids unique per row), ids the n ids of S, ascending and unique, map what

@@ -280,6 +280,12 @@ SIGNATURES = {
     # (rowptr, col, val, ids, n, N, map, d, X, ldx, H, ldh, C, ldc, stream)
     "sgcn_spmm_pull_f32": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P]),
     "sgcn_spmm_pull_h16": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P]),
+    # the two-table element-wise maximum of a part step with stale rows (--full_batch_part_pull_max):
+    # (rowptr, col, ids, n, N, map, d, X, ldx, H, ldh, C, ldc, arg, ldarg, stream)
+    "sgcn_spmax_pull_f32": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P,
+                                      C.c_int64, P]),
+    "sgcn_spmax_pull_h16": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_int64, P, C.c_int64, P, C.c_int64, P,
+                                      C.c_int64, P]),
     # two-table attention of a part step with stale rows (--full_batch_part_pull, --aggregator attn):
     # (rowptr, col, ids, n, N, map, d, heads, X, ldx, H, ldh, scale, C, ldc, lse, stream),
     # (rowptr, col, ids, n, N, map, d, heads, X, ldx, H, ldh, scale, G, ldg, C, ldc, lse, delta, dQ, lddq, add, ldadd, add_rows,

@@ -33,7 +33,9 @@ two products).
                  adjacency, the ids and map of S and the model's history tables; ``pull_product`` sums over every stored entry of
                  the rows of S, fresh rows for columns in S and stored rows for the others (ops.spmm_pull); under
                  --full_batch_part_pull with --aggregator attn ``pull_attn_product`` / ``pull_attn_backward`` attend over
-                 the same entries (ops.spattn_pull, ops.spattn_pull_bwd_q, then the block's bwd_kv)
+                 the same entries (ops.spattn_pull, ops.spattn_pull_bwd_q, then the block's bwd_kv); under
+                 --full_batch_part_pull_max ``pull_max_product`` takes the element-wise maximum over them (ops.spmax_pull),
+                 the backward being the block's own
   PulledLayer    that matrix as aggregation layer l multiplies by it (PartBatch.adj[l]): one-table calls that pull, then push
 """
 import numpy as np
@@ -846,6 +848,25 @@ def check_part_pull_gat(flags=None):
     return _check_part_tables(flags, 'full_batch_part_pull_gat', aggregator, stored="rows and scores")
 
 
+def check_part_pull_max(flags=None):
+    """(on, bf16) of --full_batch_part_pull_max / --history_dtype: part steps of the maximum aggregator that read stored rows
+    for their out-of-part neighbours (ops.spmax_pull): every aggregation layer takes the element-wise maximum over every
+    stored entry of its rows.  What the two-table kernel has no form or no meaning for is refused.  Needs no device; called
+    beside check_part_pull_gat.  The three older checks keep their own contracts and, where the aggregator is not theirs,
+    speak first."""
+    def aggregator(f, agg):
+        if agg != 'max':
+            raise ValueError("--full_batch_part_pull_max needs --aggregator max (got %s): it is the two-table form of the "
+                             "element-wise maximum; --full_batch_part_pull serves the sum and dot-product attention, "
+                             "--full_batch_part_pull_gat the learned scores" % agg)
+        for other in ('full_batch_part_history', 'full_batch_part_pull', 'full_batch_part_pull_gat'):
+            if getattr(f, other, False):
+                raise ValueError("--full_batch_part_pull_max is not supported together with --%s: not together with "
+                                 "--full_batch_part_history, --full_batch_part_pull or --full_batch_part_pull_gat, which "
+                                 "are the two-table forms of the other aggregators" % other)
+    return _check_part_tables(flags, 'full_batch_part_pull_max', aggregator, kernels="kernel's")
+
+
 def partition(adj, P, seed=1):
     """The vertices of ``adj`` cut into P parts, as P ascending int32 id arrays; deterministic in (adj, P, seed).
 
@@ -936,9 +957,12 @@ class PulledMatrix(InducedMatrix):
     ``pull_attn_product`` / ``pull_attn_backward`` are the attention over the same entries (--full_batch_part_pull).  The pull
     launches take their operands as they are: nothing is staged, so a table too wide for its alignment (602 columns on a pitch
     of 602 floats) is refused with the kernels' width message.  These methods take the layer's index and push nothing; an
-    aggregation layer is handed ``layer(l)``, which pulls, then pushes, behind StaticMatrix's one-table signatures."""
+    aggregation layer is handed ``layer(l)``, which pulls, then pushes, behind StaticMatrix's one-table signatures.
+    ``pull_max`` (--full_batch_part_pull_max; off by default): the switch ``layer(l).max_product`` reads -- on, the maximum
+    is ``pull_max_product``, the element-wise maximum over the same entries (ops.spmax_pull) with winners recorded for the
+    block's own ``transpose.max_backward``; off, the inherited ``max_product``, the block's in-part maximum."""
 
-    def __init__(self, block, resident, ids_dev, tables, owned, device=None, scores=None):
+    def __init__(self, block, resident, ids_dev, tables, owned, device=None, scores=None, pull_max=False):
         if getattr(block, 'map', None) is None:
             raise ValueError("a PulledMatrix needs the block's position map (ops.csr_induce)")
         super(PulledMatrix, self).__init__(block, device, bf16=False)
@@ -951,9 +975,20 @@ class PulledMatrix(InducedMatrix):
         if scores is not None and len(scores) != len(tables):
             raise ValueError("a PulledMatrix needs one score table per history table")
         self.scores = None if scores is None else list(scores)
+        self.pull_max = bool(pull_max)
 
     def pull_product(self, x, l, out=None):
         return ops.spmm_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], out=out)
+
+    def pull_max_product(self, x, l, out=None, want_arg=True):
+        """(out, arg) of layer l's element-wise maximum over EVERY stored entry of the rows of S (ops.spmax_pull): a fresh row
+        of ``x`` for a column in S, the row of table l for the others, the first maximum in stored order whichever table it
+        comes from.  arg holds a fresh winner's position in S, -1 for an empty row and -2 - column for a stale winner, so
+        ``transpose.max_backward(g, arg)`` -- the block's one-table backward over A[S, S]^T -- sends the gradient to in-part
+        winners and nothing to stored rows.  ``out`` may be a pitched view.  --full_batch_part_pull_max."""
+        if x.dtype != torch.float32:
+            raise ValueError("the two-table element-wise maximum has no bfloat16-operand form")
+        return ops.spmax_pull(self.resident, self.ids_dev, self.map, x, self.tables[l], out=out, want_arg=want_arg)
 
     def pull_attn_product(self, x, l, scale, out=None, want_lse=True, heads=1):
         """(out, lse) of layer l's attention over EVERY stored entry of the rows of S (ops.spattn_pull): the queries are the
@@ -1031,8 +1066,10 @@ class PulledLayer(object):
     """A PulledMatrix as aggregation layer ``l`` sees it: StaticMatrix's one-table signatures, answered by the two-table launches
     over table l.  Every forward pulls and THEN pushes the layer's input rows (with score tables: its fresh destination scores
     too) -- columns inside the step's vertex set never read either table, and a backward re-reads only rows outside it.
-    ``shape``, ``transpose`` and the maximum are the block's: in-part entries only.  So are ``gat_product`` / ``gat_backward``
-    of a matrix WITHOUT score tables, which push nothing."""
+    ``shape`` and ``transpose`` are the block's: in-part entries only.  So is the maximum of a matrix whose ``pull_max`` is off
+    (nothing read, nothing pushed); with it on (--full_batch_part_pull_max) ``max_product`` is the two-table maximum and
+    pushes, and its ``arg`` is made for ``transpose.max_backward``, which stays the block's.  ``gat_product`` /
+    ``gat_backward`` of a matrix WITHOUT score tables are the block's too and push nothing."""
 
     def __init__(self, matrix, l):
         self.matrix, self.l, self.shape = matrix, int(l), matrix.shape
@@ -1051,7 +1088,12 @@ class PulledLayer(object):
         return out
 
     def max_product(self, x, out=None, want_arg=True):
-        return self.matrix.max_product(x, out=out, want_arg=want_arg)
+        M = self.matrix
+        if not M.pull_max:
+            return M.max_product(x, out=out, want_arg=want_arg)
+        res = M.pull_max_product(x, self.l, out=out, want_arg=want_arg)
+        M.push(x, self.l)
+        return res
 
     def attn_product(self, x, scale, out=None, want_lse=True, heads=1, keep=1.0, key=0):
         self._no_dropout(keep)

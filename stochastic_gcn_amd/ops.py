@@ -1085,6 +1085,41 @@ def _pull_operands(who, A, ids_dev, map_dev, x, H, heads):
     return n, N, d, heads, xp, hp
 
 
+def spmax_pull(A, ids_dev, map_dev, x, H, out=None, want_arg=True, arg=None):
+    """(out, arg): the element-wise maximum of the n selected rows ``ids_dev`` of the RESIDENT square DeviceCSR ``A`` over EVERY
+    stored entry e of row ids[i] in stored order, the entry's row being x[map[col[e]]] if map[col[e]] >= 0 else H[col[e]]
+    (sgcn_spmax_pull_f32 / _h16; --full_batch_part_pull_max).  The first maximum wins under ``spmax``'s rule, whichever table
+    it comes from; an empty row gives +0.0.
+
+    arg[i, c] (int32) records the winner for ``spmax_bwd`` over the TRANSPOSED in-part block: >= 0 -- fresh, its POSITION in
+    ``ids_dev`` (the block's column); -1 -- empty row; <= -2 -- stale, global column -2 - arg (a constant of the step: no row
+    of the block matches it).  ``ids_dev``, ``map_dev``, ``x`` (n x d fp32) and ``H`` (N x d: fp32, or a bfloat16 table of
+    ``history_alloc(..., bf16=True)``'s layout, widened exactly) as in ``spmm_pull``; ``out`` (may be a pitched (n, >= d)
+    view), ``want_arg`` and ``arg`` as in ``spmax``.  ``A`` is read in place, its values not at all: no cut, no plan, no
+    synchronisation; one lane group per selected row, however long.  The result has the bits of ``spmax`` without a plan on
+    the rows ``ids`` of ``A`` and the merged table (H with the rows ids replaced by x)."""
+    n, N, d, _, (xptr, ldx), (hptr, ldh, h16) = _pull_operands("spmax_pull", A, ids_dev, map_dev, x, H, 1)
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    cptr, ldc = _rows2d(out, "out")
+    if out.shape[0] != n or out.shape[1] < d:
+        raise ValueError("out has shape %s, need (%d, >=%d)" % (tuple(out.shape), n, d))
+    ldarg = d
+    if not want_arg:
+        arg = None
+    elif arg is None:
+        arg = torch.empty((n, d), dtype=torch.int32, device=x.device)
+    else:
+        _dev(arg, torch.int32, "arg")
+        if arg.dim() != 2 or arg.shape[0] != n or arg.shape[1] < d or (arg.shape[1] > 1 and arg.stride(1) != 1):
+            raise ValueError("arg has shape %s, need (%d, >=%d) with unit column stride" % (tuple(arg.shape), n, d))
+        ldarg = arg.stride(0) if n > 1 else max(arg.stride(0), arg.shape[1])
+    check((lib.sgcn_spmax_pull_h16 if h16 else lib.sgcn_spmax_pull_f32)(
+        A.rowptr.data_ptr(), _ptr(A.col), ids_dev.data_ptr(), n, N, map_dev.data_ptr(), d, xptr, ldx, hptr, ldh, cptr, ldc,
+        _ptr(arg), ldarg, _stream()))
+    return out, arg
+
+
 def spattn_pull(A, ids_dev, map_dev, x, H, scale, out=None, want_lse=True, heads=1):
     """(out, lse): softmax dot-product attention of the n selected rows ``ids_dev`` of the RESIDENT square DeviceCSR ``A`` over
     EVERY stored entry e of row ids[i], the entry's key / value row being x[map[col[e]]] if map[col[e]] >= 0 else H[col[e]]

@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .flags import FLAGS, check_exact_history, check_history_dtype, check_polyak
 from .full_batch import (InducedMatrix, PartBatch, PartSchedule, PulledMatrix, check_full_batch_parts, check_part_history,
-                         check_part_pull, check_part_pull_gat, part_stats, partition,
+                         check_part_pull, check_part_pull_gat, check_part_pull_max, part_stats, partition,
                          StaticBatch, StaticMatrix, attn_heads_divide, check_aggregator, check_attention, check_attn_dropout, check_attn_heads, check_attn_score, check_edge_dropout, check_feature_dtype, check_full_batch, full_batch_bf16,
                          full_batch_products,
                          model_matrix, static_kernel_for)  # noqa: F401  (static_kernel_for: named as train.static_kernel_for elsewhere)
@@ -250,6 +250,11 @@ class Trainer(object):
         self.part_pull_gat, gat_bf16 = check_part_pull_gat()
         if self.part_pull_gat:
             self.part_history, self.part_history_bf16 = True, self.part_history_bf16 or gat_bf16
+        # (--full_batch_part_pull_max without parts, without --aggregator max, with --reverse, a bfloat16 operand or one of the
+        # three flags above: too.  It turns the same machinery on; the matrix of a step then takes the two-table maximum)
+        self.part_pull_max, max_bf16 = check_part_pull_max()
+        if self.part_pull_max:
+            self.part_history, self.part_history_bf16 = True, self.part_history_bf16 or max_bf16
         # (--aggregator max without both full-graph modes, with a bfloat16 table or an edge mask: too)
         self.max_aggregator = check_aggregator()
         # (--aggregator attn likewise; --attn_scale negative, non-finite, or set without attn: too)
@@ -483,6 +488,8 @@ class Trainer(object):
                 if self.part_pull:
                     what = '--full_batch_part_pull (--aggregator {}): a step {} over'.format(
                         FLAGS.aggregator, 'attends' if FLAGS.aggregator == 'attn' else 'sums')
+                if self.part_pull_max:
+                    what = '--full_batch_part_pull_max: a step takes the maximum over'
                 self.log('[sgcn] {} every stored entry of its rows -- fresh rows inside its '
                          'vertex set, stored rows outside (nothing dropped, nothing rescaled) | {} table(s) of {} rows, {}: {:.1f} '
                          'MiB, zero-filled{} | a group without a training vertex runs the forward only and pushes its rows'.format(
@@ -504,7 +511,8 @@ class Trainer(object):
             block = ops.csr_induce(self.train_csr, ids, ids_dev, norm='keep')
             tables, owned = self.train_model.part_history
             matrix = PulledMatrix(block, self.train_csr, ids_dev, tables, owned, self.device,
-                                  scores=self.train_model.part_scores if self.part_pull_gat else None)
+                                  scores=self.train_model.part_scores if self.part_pull_gat else None,
+                                  pull_max=self.part_pull_max)
             if rows.size == 0:
                 return PartBatch(ids, ids_dev, matrix, None, None, self.train_model.L, self.device)
             return PartBatch(ids, ids_dev, matrix, self._labels_dev, rows, self.train_model.L, self.device)
