@@ -1375,7 +1375,9 @@ enum {
                                  * layer) */
     SGCN_OP_MODE = 23,          /* (overlap, fuse), constants, anywhere in the program: this RUN uses the auxiliary stream iff
                                  * overlap != 0 and, when fuse >= 0, the fusion bits `fuse` -- instead of the process-wide
-                                 * knobs step_overlap / step_fuse (which stay the defaults of programs without this op) */
+                                 * knobs step_overlap / step_fuse (which stay the defaults of programs without this op).  The
+                                 * two words are taken from add[0], add[1] ahead of the loop (they hold for the WHOLE run):
+                                 * the op itself, in its place, reads no argument and does nothing */
     /* the sparse-input first layer (gcn/layers.py:125,401-402 with sparse_inputs), ABI v11: */
     SGCN_OP_CSR_SLICE = 24,     /* sgcn_csr_slice_indptr_dev + sgcn_csr_slice_f32: (n, rows, a_val, a_col, a_rowptr, o_p, o_d, o_col, o_row) */
     SGCN_OP_LN_ACT_FWD = 25,    /* sgcn_ln_act_fwd_f32 */

@@ -85,7 +85,8 @@ class Plan(C.Structure):
 P = C.c_void_p  # raw address (host or device), passed as integers from data_ptr()/ctypes.data
 
 # name -> (restype, argtypes).  Must list every symbol of include/sgcn.h
-# (tests/test_abi.py cross-checks this table against the header).
+# (tests/test_abi.py cross-checks the names of this table against the header; tests/test_abi_types.py every
+# result and parameter TYPE, the layouts of the structs above and step_program.OP, with the compiler as the parser).
 SIGNATURES = {
     "sgcn_last_error": (C.c_char_p, []),
     "sgcn_abi_version": (C.c_int, []),

@@ -58,6 +58,16 @@ int dense_fwd_pair(int32_t M, int32_t N, int32_t K, const float* X, int64_t ldx,
                    void* stream, int* fused);
 }  // namespace sgcn
 
+// tests/step_trace links this file against recording stubs and defines SGCN_STEP_TRACE: once per executed op, behind the
+// switch, the hook gets the op's index, code and argument count, how many arguments its case consumed and how many reads
+// went past the list.  In every other build the macro is empty and Args counts nothing.
+#ifdef SGCN_STEP_TRACE
+void sgcn_step_trace_op(int k, int op, int nargs, int pos, int overread);
+#define SGCN_STEP_TRACE_OP(k, op, nargs, pos, overread) sgcn_step_trace_op(k, op, nargs, pos, overread)
+#else
+#define SGCN_STEP_TRACE_OP(k, op, nargs, pos, overread)
+#endif
+
 namespace {
 
 inline float f32(int64_t v) {
@@ -71,7 +81,12 @@ template <class T> inline T* ptr(int64_t v) { return reinterpret_cast<T*>((uintp
 struct Args {
     int64_t v[SGCN_STEP_MAX_ARGS];
     int n, pos;
+#ifdef SGCN_STEP_TRACE
+    int over = 0;
+    int64_t next() { if (pos < n) return v[pos++]; over++; return 0; }
+#else
     int64_t next() { return pos < n ? v[pos++] : 0; }
+#endif
     template <class T> T* p() { return ptr<T>(next()); }
     int32_t i() { return (int32_t)next(); }
     float f() { return f32(next()); }
@@ -856,6 +871,7 @@ extern "C" int sgcn_step_run(const sgcn_step_op_t* ops, int32_t nops, const int6
         default:
             return sgcn::fail(SGCN_ERR_INVALID, "step_run: unknown opcode %d at op %d", op.op, k);
         }
+        SGCN_STEP_TRACE_OP(k, op.op, a.n, a.pos, a.over);
         if (rc != SGCN_OK) { sgcn::aux_join(stream); xchg_join(stream); return rc; }       // the failing entry point has set the message
     }
     const int rj = sgcn::aux_join(stream);  // a run never returns with work pending on the auxiliary stream
